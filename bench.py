@@ -1,8 +1,17 @@
 """Headline benchmark: DDIM steps/s of the ViewCrafter denoising loop on MI355X (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-N > 1: one process per GPU over RCCL.  Started as a plain `python bench.py --gpus N` the script re-executes itself under
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps (no profiling events, no telemetry
+thread), and one JSON line with the driver contract (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`,
+...).  `--full` adds everything else described below, as it ran before the split: HIP-event profiling inside the timed
+region, telemetry, decode / gather, the measured video, the other configurations, parity, the eager and CPU baselines.
+
+`--dump-outputs DIR` writes what the last timed step returned - `x_prev` (the next latent) and `pred_x0`, float32 - as
+DIR/<name>.npy (N > 1: every rank its own, as <name>_rank<r>.npy).  Weights, inputs and noise are seeded, so the same
+arguments give the same inputs in every run and two builds can be compared output for output.
+
+N > 1: one process per GPU over RCCL.  Started as a plain `python bench.py --gpus N` the script runs itself as a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` (the same line
 the driver uses; under that launcher - WORLD_SIZE set - it just runs as one rank).  Either way the line it prints carries
 `n_gpus` = the world size it really ran with, which must equal --gpus, and the backend must be nccl (= RCCL).
@@ -13,7 +22,7 @@ evaluations (cond + uncond, run as one B=2 forward) + the fused CFG / guidance-r
 x_{t-1} update, eta = 1 (fresh noise every step), fp16 storage with fp32 accumulation.  Weights are synthetic (no
 checkpoints offline), data is synthetic of the real shapes; inputs are resident in HBM before the timed region.
 
-Printed JSON (rank 0): the driver contract + `roofline` (dominant kernel = the MFMA GEMM/conv engine, measured with HIP
+Printed JSON (rank 0) with --full: the driver contract + `roofline` (dominant kernel = the MFMA GEMM/conv engine, measured with HIP
 events on the launch stream over the timed region) + `roofline_flash` (second family, same method) + `cpu_baseline` (the
 reference's own code from oracle/_ref - or, if that tree is not built, the fp32 oracle port - timed on the host cores at
 BASELINE configs[0]'s shapes 16x40x64 and FLOP-scaled) + `gpu_eager_baseline` (the reference's own UNetModel.forward, or
@@ -194,19 +203,20 @@ def gpu_legs(model, hp, dd, T, h, w, device, x, ts, ctx, fs, z_dec):
 
 
 def self_launch(argv, n):
-    """`python bench.py --gpus N` (N > 1) without a launcher: become `python -m torch.distributed.run ... bench.py <same args>`,
-    one rank per GPU on this node, rendezvous on 127.0.0.1 (the container hostname may not resolve)."""
+    """`python bench.py --gpus N` (N > 1) without a launcher: run `python -m torch.distributed.run ... bench.py <same args>` as a
+    child and exit with its status, one rank per GPU on this node, rendezvous on 127.0.0.1 (the container hostname may not resolve)."""
     import socket
+    import subprocess
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
-    print(f"[bench] --gpus {n} without a launcher: re-executing as {' '.join(cmd[1:8])} bench.py ...", file=sys.stderr)
+    print(f"[bench] --gpus {n} without a launcher: running {' '.join(cmd[1:8])} bench.py ...", file=sys.stderr)
     sys.stderr.flush()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def per_rank_rates(elapsed_local, steps, device):
@@ -265,6 +275,11 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="ViewCrafter_25_576x1024x25", choices=list(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: profiling events in the timed region, "
+                    "telemetry, decode / gather, video, other configurations, parity, eager and CPU baselines (the --no-* "
+                    "options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write x_prev and pred_x0 of the last timed step as "
+                    "float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--graph", action="store_true", help="replay the UNet forward as a hipGraph in the timed region "
@@ -347,6 +362,7 @@ def main():
     sampler.share_cfg_prefix = not args.no_shared_prefix
     n_sched = len(sampler.ddim_timesteps)
     x_start = x.clone()
+    last = {}
 
     def one_step(x, i):
         # step i of back-to-back 50-step trajectories: a request for more than 50 steps starts the next trajectory from the same x_T
@@ -354,9 +370,9 @@ def main():
             x = x_start.clone()
         index = n_sched - 1 - (i % n_sched)
         ts = torch.full((1,), int(sampler.ddim_timesteps[index]), device=device, dtype=torch.long)
-        x, _ = sampler.p_sample_ddim(x, cond, ts, index=index, unconditional_guidance_scale=7.5,
-                                     unconditional_conditioning=uc, fs=fs, guidance_rescale=0.7,
-                                     cfg_img=None, unconditional_conditioning_img_nonetext=None)
+        x, last["pred_x0"] = sampler.p_sample_ddim(x, cond, ts, index=index, unconditional_guidance_scale=7.5,
+                                                   unconditional_conditioning=uc, fs=fs, guidance_rescale=0.7,
+                                                   cfg_img=None, unconditional_conditioning_img_nonetext=None)
         return x
 
     def sync():
@@ -367,11 +383,11 @@ def main():
 
     unet = model.model.diffusion_model
     unet.use_hip_graph = bool(args.graph)
-    profile_in_region = not (args.graph or args.no_profile)
+    profile_in_region = args.full and not (args.graph or args.no_profile)
     # graphics clock / socket power sampled every 50 ms by a side thread from the warm-up on (tools/telemetry.py: amdsmi gpu_metrics or
     # sysfs hwmon); the statistics of the samples that fall inside the timed region go into the line as `telemetry`
     from tools.telemetry import Telemetry
-    tm = Telemetry(device_index=dev_index, period_s=0.05) if rank == 0 and not args.no_telemetry else None
+    tm = Telemetry(device_index=dev_index, period_s=0.05) if rank == 0 and args.full and not args.no_telemetry else None
     if tm is not None:
         tm.__enter__()
     with torch.no_grad():
@@ -389,7 +405,7 @@ def main():
             tm.__exit__(None, None, None)
         if profile_in_region:
             prof = ops.profile_end()
-        else:   # per-family HIP-event timing on extra eager steps of the same loop (not part of `value`)
+        elif args.full:   # per-family HIP-event timing on extra eager steps of the same loop (not part of `value`)
             unet.use_hip_graph = False
             n_extra = 2
             ops.profile_begin(1 << 16)
@@ -402,12 +418,18 @@ def main():
                 for k in ("launches", "ms", "flops", "bytes"):
                     v[k] = v[k] * args.steps / max(n_extra, 1)
     assert torch.isfinite(x).all(), "non-finite latent after the timed steps"
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        for name, t in (("x_prev", x), ("pred_x0", last["pred_x0"])):
+            np.save(os.path.join(args.dump_outputs, name + sfx + ".npy"), t.detach().float().cpu().numpy())
     rank_rates = [args.steps / elapsed]
     if world > 1:
         elapsed, rank_rates = per_rank_rates(elapsed, args.steps, device if dist.get_backend() == "nccl" else "cpu")
 
     gather_s = None
-    if world > 1 and not args.no_decode:
+    if world > 1 and args.full and not args.no_decode:
         # the product's end: every rank decodes its own trajectory, rank 0 receives all clips in one all_gather (uint8 frames)
         from viewcrafter_amd import parallel
         with torch.no_grad():
@@ -434,13 +456,14 @@ def main():
         "dtype": "f16", "data": "synthetic", "backend": (dist.get_backend() + (" (RCCL over xGMI)" if dist.get_backend() == "nccl" else
                                                                              " (SHARED-GPU SMOKE TEST: not a measurement)")) if world > 1 else None,
         "per_rank_steps_per_s": rank_rates, "tune": ops.tune_report(), "launch_mode": "hipGraph replay" if args.graph else "eager",
-        "roofline_measured_on": "the timed region" if profile_in_region else "extra eager steps after the timed region",
+        "full": args.full,
         "config": {"workload": args.workload, "trajectories_per_gpu": 1, "frames": T, "latent": [T, h, w],
                    "guidance": "CFG 7.5 + rescale 0.7, cond/uncond batched as B=2" + ("" if args.no_shared_prefix else
                                "; layers ahead of the first cross-attention (identical inputs in both evaluations) computed once"), "eta": 1.0,
                    "parallelism": f"trajectory-sharded x{world} (no in-step collective)"},
     }
-    if rank == 0:
+    if rank == 0 and args.full:
+        out["roofline_measured_on"] = "the timed region" if profile_in_region else "extra eager steps after the timed region"
         if tm is not None:
             out["telemetry"] = tm.summary(t0, t0 + elapsed)
             out["telemetry"]["scope"] = "rank 0's GPU, samples inside the timed region"
@@ -634,6 +657,7 @@ def main():
             out["gather_s"] = gather_s
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, hp, dict(mp_["first_stage_config"]["params"]["ddconfig"]), flops_per_step)
+    if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -200,7 +200,7 @@ def test_bench_gpus_2_launch_line_on_this_one_gpu_is_a_marked_smoke_test():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(VCX_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload",
-                        "ViewCrafter_25_512_320x512x25", "--no-cpu-baseline", "--no-gpu-legs", "--no-extra", "--no-video"],
+                        "ViewCrafter_25_512_320x512x25", "--full", "--no-cpu-baseline", "--no-gpu-legs", "--no-extra", "--no-video"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -210,3 +210,29 @@ def test_bench_gpus_2_launch_line_on_this_one_gpu_is_a_marked_smoke_test():
     assert "SMOKE TEST" in out["backend"] and "not a measurement" in out["backend"]
     assert out["value"] > 0 and out["gather_s"] is not None
     assert "torch.distributed.run" in r.stderr
+
+
+def test_plain_bench_run_prints_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`python bench.py` without --full: warm-up, timed steps and the contract line - no roofline, telemetry or baselines - and
+    --dump-outputs writes the last timed step's x_prev / pred_x0 as float32 .npy files of the latent's shape."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload",
+                        "ViewCrafter_25_512_320x512x25", "--dump-outputs", str(dump)],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert k in out, k
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["n_gpus"] == 1 and out["full"] is False
+    assert out["unit"] == "DDIM steps/s" and out["higher_is_better"] is True and out["dtype"] == "f16"
+    assert out["value"] == pytest.approx(1e3 / out["ms_per_step"], rel=1e-6)
+    for k in ("roofline", "telemetry", "cpu_baseline", "gpu_eager_baseline", "parity", "extra", "sec_per_video"):
+        assert k not in out, k
+    assert sorted(os.listdir(dump)) == ["pred_x0.npy", "x_prev.npy"]
+    for name in ("x_prev", "pred_x0"):
+        a = np.load(dump / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (1, 4, 25, 40, 64) and np.isfinite(a).all(), name
