@@ -151,8 +151,9 @@ int vcx_gemm_f16(const vcx_gemm_desc* desc_host, void* stream);
 /* The same linear layer with ONE weight / bias set per `unit_rows` consecutive rows: rows [u unit_rows, (u + 1) unit_rows) use
  * W + u w_unit_stride and bias + u bias_unit_stride (element strides) - the (Wn, bn) sets of vcx_groupnorm_fold_linear_f16, one per
  * frame (SpatialTransformer.norm -> proj_in, attention.py:265-269,299) or per video (TemporalTransformer, attention.py:331-336,369-372).
- * Linear mode, VCX_GEMM_BIAS_N at most, M a whole number of units.  N = K = 320 with unit_rows % 32 == 0 runs as ONE launch of the
- * weight-stationary kernel (a block keeps its unit's weights in registers); every other shape unit by unit through vcx_gemm_f16. */
+ * Linear mode, VCX_GEMM_BIAS_N at most, M a whole number of units.  N = K = 320 with unit_rows % 32 == 0, >= 1024 and M >= 8192 runs as
+ * ONE launch of the weight-stationary kernel (a block keeps its unit's weights in registers); every other shape unit by unit through
+ * vcx_gemm_f16.  VCX_GEMM_ROWSTATS: in the one-launch form, or with one unit (vcx_gemm_f16's weight-stationary kernel, the same bits). */
 int vcx_gemm_units_f16(const vcx_gemm_desc* desc_host, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------

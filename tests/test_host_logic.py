@@ -669,3 +669,133 @@ def test_folded_packs_follow_the_parent_blocks_layernorm_and_lnfold_ok_mirrors_t
     assert not ops.lnfold_ok(1_200_000, 2560, 320)                  # output rows x ldc beyond 4 GiB
     monkeypatch.setattr(ops, "tune_get", lambda name: 0)
     assert not ops.lnfold_ok(460800, 960, 320)                      # knob GEMM_DMA = 0: register-staged kernel, no folded epilogue
+
+
+# ------------------------------------------------------------------ batch invariance of the host's route decisions (full width, no GPU)
+class _RouteRecorder:
+    """Shape-only stand-ins for the ops launchers that record, per launch, what selects a kernel route: the entry point, rows per unit,
+    which by-products (row statistics, column moments, folded LayerNorm statistics, K tail) are asked for.  Activations live on the
+    meta device, so the full-width blocks of the 1.44 B model run in milliseconds without allocating a byte."""
+
+    def __init__(self):
+        self.log = []
+
+    def install(self, monkeypatch):
+        from viewcrafter_amd import _lib, ops
+        meta = torch.device("meta")
+        rec = self.log.append
+
+        def gemm(a, w, *, M, N, K, out=None, geglu=False, out_f32=False, conv=None, ln_stats=None, colstats=None, rowstats=None, tail=None,
+                 residual=None, rowadd=None, bias_m=False, **kw):
+            rec(("gemm", "conv" if conv else "linear", M if bias_m else N, K, geglu, ln_stats is not None, colstats is not None, rowstats is not None,
+                 len(tail or ()), residual is not None, rowadd is not None))      # (N of the transposed V^T projection counts tokens)
+            n_out = N // 2 if geglu else N
+            return out if out is not None else torch.empty((M, n_out), dtype=torch.float32 if out_f32 else torch.float16, device=meta)
+
+        def gemm_units(a, wn, bn, *, unit_rows, out=None, rowstats=None, rowstats_eps=1e-5):
+            rec(("gemm_units", unit_rows, rowstats is not None))
+            return out if out is not None else torch.empty((a.shape[0], wn.shape[1]), dtype=torch.float16, device=meta)
+
+        def gn_stats(x, groups=32):
+            rec(("group_norm_stats", x.shape[1]))
+            return torch.empty((x.shape[0], groups, 2), device=meta)
+
+        def gn_from_cs(cs, n_outer, pixels, C, groups=32):
+            rec(("group_norm_stats_from_colstats", pixels, C))
+            return torch.empty((n_outer, groups, 2), device=meta)
+
+        def gn_fold(w32, bias, gamma, beta, stats, eps, groups=32):
+            rec(("group_norm_fold_linear",))
+            n, (N, C) = stats.shape[0], w32.shape
+            return torch.empty((n, N, C), dtype=torch.float16, device=meta), torch.empty((n, N), device=meta)
+
+        def group_norm(x, gamma, beta, eps, silu, groups=32, out=None, stats=None, x2=None):
+            rec(("group_norm", x.shape[1], stats is not None, x2 is not None))
+            C = x.shape[2] + (0 if x2 is None else x2.shape[2])
+            return out if out is not None else torch.empty((x.shape[0], x.shape[1], C), dtype=torch.float16, device=meta)
+
+        def row_stats(x, eps=1e-5):
+            rec(("row_stats",))
+            return torch.empty((x.shape[0], 2), device=meta)
+
+        def layer_norm(x, gamma, beta, eps=1e-5):
+            rec(("layer_norm",))
+            return torch.empty_like(x)
+
+        def attention(name):
+            def run(*a, **kw):
+                rec((name, kw.get("nq"), kw.get("T"), kw.get("P")))
+                return a[3] if name == "flash_attn" else (a[5] if name == "flash_attn_dual" else a[1])
+            return run
+        table = dict(require_gpu=lambda: None, gemm=gemm, gemm_units=gemm_units, group_norm_stats=gn_stats, group_norm_stats_from_colstats=gn_from_cs,
+                     group_norm_fold_linear=gn_fold, group_norm=group_norm, row_stats=row_stats, layer_norm=layer_norm,
+                     flash_attn=attention("flash_attn"), flash_attn_dual=attention("flash_attn_dual"), temporal_attn=attention("temporal_attn"),
+                     copy2d=lambda *a, **k: None, tune_get=lambda name: _lib.TUNE[name][1])
+        for name, fn in table.items():
+            monkeypatch.setattr(ops, name, fn)
+
+
+def _meta_unet(yaml_name):
+    from viewcrafter_amd.lvdm.modules.networks.openaimodel3d import UNetModel
+    params = dict(load_yaml(os.path.join(ROOT, "configs", yaml_name))["model"]["params"]["unet_config"]["params"])
+    params["use_checkpoint"] = False
+    with torch.device("meta"):
+        return UNetModel(**params).eval()
+
+
+_UNETS = {}
+
+
+def _block_routes(monkeypatch, yaml_name, level, B, T, h, w, r=1):
+    """The launches of input block 1 (level 0, C = 320) or 4 (level 1, C = 640) - ResBlock, SpatialTransformer (shared CFG prefix when
+    r > 1), TemporalTransformer - for B videos of T x h x w latents (level 1: h / 2 x w / 2)."""
+    from viewcrafter_amd.lvdm.modules.attention import SpatialTransformer
+    if yaml_name not in _UNETS:
+        _UNETS[yaml_name] = _meta_unet(yaml_name)
+    unet = _UNETS[yaml_name]
+    blk = unet.input_blocks[1 if level == 0 else 4]
+    rb, st, tt = list(blk)
+    rec = _RouteRecorder()
+    rec.install(monkeypatch)
+    meta = torch.device("meta")
+    hh, ww = (h, w) if level == 0 else (h // 2, w // 2)
+    x = torch.empty((B * T, hh, ww, rb.channels), dtype=torch.float16, device=meta)
+    emb = torch.empty((B, rb.emb_channels), dtype=torch.float16, device=meta)
+    ctx = dict(txt=torch.empty((r * B * 80, 1024), dtype=torch.float16, device=meta), img=torch.empty((r * B * 256, 1024), dtype=torch.float16, device=meta),
+               n_img=256, per_frame=False)
+    with torch.no_grad():
+        kv = st.project_context(ctx)
+        del rec.log[:]
+        out = blk(x, emb, context={id(st): kv}, batch_size=B, cfg_repeat=r)
+    assert out.shape == (r * B * T, hh, ww, st.in_channels) and isinstance(st, SpatialTransformer)
+    return rec.log
+
+
+# (T, h, w): 40 x 64 = level 0 of the 320 x 512 model; 3 frames are 7680 rows alone and 15360 in a pair (8192 rows: epilogue row statistics), 6
+# frames 9.8 MB alone and 19.7 MB in a pair (16 MiB: the spatial GroupNorm fold); 16 x 40 x 64 and 25 x 72 x 128 are the shipped latents
+ROUTE_GRID = [("inference_pvd_512.yaml", 3, 40, 64), ("inference_pvd_512.yaml", 6, 40, 64), ("inference_pvd_512.yaml", 16, 40, 64),
+              ("inference_pvd_512.yaml", 25, 40, 64), ("inference_pvd_1024.yaml", 2, 72, 128), ("inference_pvd_1024.yaml", 25, 72, 128)]
+
+
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("yaml_name,T,h,w", ROUTE_GRID)
+def test_batch_routes_do_not_depend_on_the_batch(monkeypatch, yaml_name, T, h, w, level):
+    """Every batch-size-dependent decision of the host graph is made on per-video quantities: the launch sequence of a level-0 / level-1 block is
+    the same for B = 1, B = 2 and the shared CFG prefix (cfg_repeat 2 / 3) - entry points, rows per unit, requested by-products.  (Bits of
+    one route against another are the GPU suite's business: tests/test_batch_invariance_gpu.py.)"""
+    one = _block_routes(monkeypatch, yaml_name, level, 1, T, h, w)
+    assert _block_routes(monkeypatch, yaml_name, level, 2, T, h, w) == one, "B = 2 takes other routes than B = 1"
+    for r in (2, 3):
+        assert _block_routes(monkeypatch, yaml_name, level, 1, T, h, w, r=r) == one, f"the shared CFG prefix (r = {r}) takes other routes"
+
+
+@pytest.mark.parametrize("yaml_name,T,h,w", [("inference_pvd_1024.yaml", 25, 72, 128), ("inference_pvd_512.yaml", 16, 40, 64)])
+def test_batch_routes_at_the_shipped_latents_keep_the_fast_paths(monkeypatch, yaml_name, T, h, w):
+    """At the benchmark's latents (B = 2: cond + uncond) level 0 keeps the spatial and temporal GroupNorm folds (proj_in as one
+    vcx_gemm_units_f16 launch with per-frame / per-video weights) and LayerNorm statistics from the producers' epilogues."""
+    log = _block_routes(monkeypatch, yaml_name, 0, 2, T, h, w)
+    units = [e for e in log if e[0] == "gemm_units"]
+    assert units == [("gemm_units", h * w, True), ("gemm_units", T * h * w, True)], units
+    rowstats_linear = [e for e in log if e[0] == "gemm" and e[7]]
+    assert len(rowstats_linear) == 2, rowstats_linear          # attn1's output projection, spatial and temporal
+    assert not [e for e in log if e[0] == "row_stats"], "a LayerNorm statistics pass at level 0"

@@ -653,7 +653,8 @@ def test_linear_colstats_and_concat_moments(M, pixels, K, c1, c2, offset):
     out = ops.group_norm(cat.view(n_outer, pixels, ct), g, be, 1e-5, True, stats=st)
     ref = F.silu(F.group_norm(cat.double().view(n_outer, pixels, ct).permute(0, 2, 1), 32, g.double(), be.double(), 1e-5)).permute(0, 2, 1)
     check(out, ref.float(), tol=3e-3 if offset else 2e-3, name="groupnorm over a concat from two producers' moments")
-    # (3) bit-reproducible, and every tile configuration writes the same moments to within rounding
+    # (3) bit-reproducible, and every tile configuration writes the same moments, bit for bit (which configuration computes a strip depends
+    # on the total M: tests/test_batch_invariance_gpu.py)
     try:
         base = None
         for cfg in (-1, 0, 1, 2, 3):
@@ -664,7 +665,7 @@ def test_linear_colstats_and_concat_moments(M, pixels, K, c1, c2, offset):
             assert torch.equal(ops.linear(xa, wa, ba, residual=res, colstats=c2_), yy) and torch.equal(c, c2_), cfg
             assert torch.equal(yy, y), cfg
             base = c if base is None else base
-            assert rel_l2(c[..., 0], base[..., 0]) <= 1e-6 and rel_l2(c[..., 1], base[..., 1]) <= 1e-4, cfg
+            assert torch.equal(c, base), cfg
     finally:
         ops.tune_set("GEMM_CFG", -1)
 

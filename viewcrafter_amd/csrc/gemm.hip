@@ -604,7 +604,9 @@ extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
 }
 
 // One weight / bias set per unit of rows (include/vcx.h): the weight-stationary kernel in ONE launch where it applies (N = K = 320, the
-// level-0 projections: a block keeps its unit's weights in registers anyway), otherwise unit by unit through vcx_gemm_f16.
+// level-0 projections: a block keeps its unit's weights in registers anyway), otherwise unit by unit through vcx_gemm_f16.  ONE unit (a single
+// video, B = 1) goes to vcx_gemm_f16 with ROWSTATS too: the same pipelined weight-stationary kernel and epilogue, so its rows and statistics
+// are the bits of the same video inside a batch (B = 2); that kernel's own grid measured faster than the one-launch form's for one unit.
 extern "C" int vcx_gemm_units_f16(const vcx_gemm_desc* d, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, void* stream) {
     VCX_REQUIRE(d != nullptr && d->struct_size == sizeof(vcx_gemm_desc), "vcx_gemm_units_f16: null descriptor or wrong struct_size");
     VCX_REQUIRE(d->A && d->W && d->C && d->M > 0 && d->N > 0 && d->K > 0, "vcx_gemm_units_f16: null A/W/C or empty problem");
@@ -633,7 +635,7 @@ extern "C" int vcx_gemm_units_f16(const vcx_gemm_desc* d, int unit_rows, int64_t
         VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * d->M * (double)d->N * d->K, 2.0 * ((double)d->M * d->K + (double)units * d->N * d->K + (double)d->M * d->N));
         return launch_ws320_units(a, s);
     }
-    VCX_REQUIRE(!(d->flags & VCX_GEMM_ROWSTATS), "vcx_gemm_units_f16: ROWSTATS needs the one-launch weight-stationary form (N = K = 320, unit_rows %% 32 == 0, >= 1024, M >= 8192); M=%d N=%d K=%d unit_rows=%d",
+    VCX_REQUIRE(units == 1 || !(d->flags & VCX_GEMM_ROWSTATS), "vcx_gemm_units_f16: ROWSTATS needs the one-launch weight-stationary form (N = K = 320, unit_rows %% 32 == 0, >= 1024, M >= 8192); M=%d N=%d K=%d unit_rows=%d",
                 d->M, d->N, d->K, unit_rows);
     for (int u = 0; u < units; ++u) {
         vcx_gemm_desc du = *d;

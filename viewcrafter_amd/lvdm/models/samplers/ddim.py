@@ -26,7 +26,8 @@ class DDIMSampler(object):
         self.counter = 0
         self._cfg_cache = None          # p_sample_ddim is public (decode() and bench.py call it without ddim_sampling)
         # classifier-free guidance evaluates the denoiser on the SAME x / t / c_concat under several c_crossattn: the layers
-        # ahead of the first cross-attention are computed once (UNetModel._forward, cfg_repeat) - bit-identical results
+        # ahead of the first cross-attention are computed once (UNetModel._forward, cfg_repeat) - bit-identical results: every route decision
+        # of the host graph is made per video (tests/test_batch_invariance_gpu.py checks both routes against each other at full width)
         self.share_cfg_prefix = True
 
     def register_buffer(self, name, attr):

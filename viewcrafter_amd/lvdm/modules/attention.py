@@ -56,10 +56,18 @@ GN_FOLD_SPATIAL = os.environ.get("VCX_GN_FOLD_SPATIAL", "1") != "0"
 
 
 def spatial_fold_ok(n, pixels, C, D):
-    """Does vcx_gemm_units_f16 take n frames of `pixels` rows in ONE weight-stationary launch (csrc/gemm.hip)?"""
-    return (GN_FOLD and GN_FOLD_SPATIAL and n > 1 and C == 320 and D == 320 and pixels % 32 == 0 and pixels >= 1024 and n * pixels >= 8192
-            and 2 * n * pixels * C >= GN_FOLD_MIN_BYTES and 2 * (n * pixels + 256) * C < 0xFFFF0000 and ops.tune_get("GEMM_DMA") != 0
+    """Does vcx_gemm_units_f16 take the frames of a video, n frames of `pixels` rows, in ONE weight-stationary launch (csrc/gemm.hip)?
+    Decided per VIDEO (n = frames per video, not frames per call): a frame's bits must not depend on how many videos share the call
+    (B = 2 against two B = 1, the shared CFG prefix against the replicated batch), so the size thresholds look at one video and the
+    kernel's own M >= 8192 follows from them for every batch.  The caller checks the 4 GiB extents of the whole call (fold_extent_ok)."""
+    return (GN_FOLD and GN_FOLD_SPATIAL and C == 320 and D == 320 and pixels % 32 == 0 and pixels >= 1024 and n * pixels >= 8192
+            and 2 * n * pixels * C >= GN_FOLD_MIN_BYTES and fold_extent_ok(n * pixels, C) and ops.tune_get("GEMM_DMA") != 0
             and ops.tune_get("GEMM_WS") != 0 and ops.tune_get("GEMM_CFG") < 0)      # (a forced tile configuration means the tiled engine: ADVICE r5)
+
+
+def fold_extent_ok(rows, C):
+    """32-bit byte offsets of the one-launch vcx_gemm_units_f16 over `rows` rows of C channels (output up to 256 rows past the end)."""
+    return 2 * (rows + 256) * C < 0xFFFF0000
 
 
 def _folded(pj, rows, K, lda, transposed=False):
@@ -398,7 +406,7 @@ class SpatialTransformer(PackedModule):
         # colstats: column moments of x from the convolution that produced it (ResBlock): the norm then needs no statistics pass
         stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, N_img, C)
         D_in = pk["win"].shape[0]
-        fold = N_img % 8 == 0 and spatial_fold_ok(n, N_img, C, D_in)      # the norm as per-frame weights / bias of proj_in
+        fold = N_img % 8 == 0 and spatial_fold_ok(frames_per_video, N_img, C, D_in) and fold_extent_ok(n * N_img, C)     # the norm as per-frame weights / bias of proj_in
         a = None if fold else ops.group_norm(x.view(n, N_img, C), pk["gn_w"], pk["gn_b"], self.norm.eps, False, stats=stats)
         # The attention kernels address a frame's keys / values at 16-byte granularity: h*w must be a multiple of 8.  It is at every
         # level of 576x1024 and 320x512; for other --height / --width (e.g. 384x640: 6x10 = 60 tokens at the deepest level) each
@@ -419,11 +427,14 @@ class SpatialTransformer(PackedModule):
             wn, bn = ops.group_norm_fold_linear(pk["win32"], pk["bin"], pk["gn_w"], pk["gn_b"], stats, self.norm.eps)
         # LayerNorm statistics of the token stream from the layer that writes it (VCX_GEMM_ROWSTATS, round 6): proj_in for norm1 of the
         # first block, attn1's output projection for norm2 - where the producer is the weight-stationary kernel (C = 320) and the
-        # consumer a folded projection; row_stats (one read of the tensor) otherwise
+        # consumer a folded projection; row_stats (one read of the tensor) otherwise.  Decided on the rows of one video, like the fold: the two
+        # routes differ in the last bits, and the shared CFG prefix (n = t frames) must match the replicated batch (r t frames) bit for bit
         blk0 = self.transformer_blocks[0]
         rs_eps = blk0.norm1.eps
         rs = None
-        if _folded(blk0.attn1.packed()["qk"], tokens, D_in, D_in) and ops.rowstats_ok(tokens, D_in, C, lda=C, unit_rows=N_img if fold else None):
+        video_rows = frames_per_video * N
+        if _folded(blk0.attn1.packed()["qk"], tokens, D_in, D_in) and ops.rowstats_ok(tokens, D_in, C, lda=C, unit_rows=N_img if fold else None,
+                                                                                      video_rows=video_rows):
             rs = ops.rowstats_buffer(tokens, x.device)
         if fold:
             t = ops.gemm_units(xin, wn, bn, unit_rows=N_img, rowstats=rs, rowstats_eps=rs_eps)
@@ -445,7 +456,7 @@ class SpatialTransformer(PackedModule):
             o = torch.empty((tokens, D), dtype=torch.float16, device=x.device)
             ops.flash_attn(qk, qk[:, D:], vt, o, n_groups=n, heads=heads, nq=N, nk=N_img, kv_rows=N, kv_div=1, ldq=2 * D,
                            ldk=2 * D, ldvt=tokens, ldo=D, scale=blk.attn1.scale, log2_logits=True)
-            st2 = ops.rowstats_buffer(tokens, x.device) if (_folded(a2["q"], tokens, D, D) and ops.rowstats_ok(tokens, D, D, ldr=D)) else None
+            st2 = ops.rowstats_buffer(tokens, x.device) if (_folded(a2["q"], tokens, D, D) and ops.rowstats_ok(tokens, D, D, ldr=D, video_rows=video_rows)) else None
             t = ops.linear(o, a1["wo"], a1["bo"], residual=t, rowstats=st2, rowstats_eps=ln[1][2])
             # ---- cross-attention: softmax(Q K_txt) V_txt + softmax(Q K_img) V_img
             q2 = ln_linear(t, a2["q"], ln[1], alpha=blk.attn2.scale * ops.LOG2E, stats=st2)
@@ -545,7 +556,7 @@ class TemporalTransformer(PackedModule):
         # LayerNorm statistics from the producing layer (VCX_GEMM_ROWSTATS): proj_in for norm1, attn1's output projection for norm2
         blk0 = self.transformer_blocks[0]
         st = None
-        if _folded(blk0.attn1.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, C, lda=C, unit_rows=rows if fold else None):
+        if _folded(blk0.attn1.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, C, lda=C, unit_rows=rows if fold else None, video_rows=rows):
             st = ops.rowstats_buffer(tokens, x.device)
         if fold:
             t = ops.gemm_units(xin, wn, bn, unit_rows=rows, rowstats=st, rowstats_eps=blk0.norm1.eps)
@@ -571,7 +582,7 @@ class TemporalTransformer(PackedModule):
                     ops.temporal_attn(qkv, o, B=B, T=T, P=P, heads=heads, ld=3 * D, k_off=D, v_off=2 * D, ldo=D,
                                       scale=attn.scale, causal=self.causal_attention)
                 st = None
-                if ai == 0 and _folded(blk.attn2.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, D, ldr=D):
+                if ai == 0 and _folded(blk.attn2.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, D, ldr=D, video_rows=rows):
                     st = ops.rowstats_buffer(tokens, x.device)
                 t = ops.linear(o, ap["wo"], ap["bo"], residual=t, rowstats=st, rowstats_eps=ln[1][2])
             t = blk.ff.run(t, ln[2])

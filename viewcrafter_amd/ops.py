@@ -141,17 +141,21 @@ def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, res
     return out
 
 
-def rowstats_ok(M, N, K, *, lda=None, ldc=None, ldr=0, unit_rows=None):
+def rowstats_ok(M, N, K, *, lda=None, ldc=None, ldr=0, unit_rows=None, video_rows=None):
     """Will the layer producing an [M, N] output - vcx_gemm_f16 (bias / residual at most), or vcx_gemm_units_f16 with `unit_rows` rows per
     weight set - write LayerNorm's row statistics of its output (VCX_GEMM_ROWSTATS)?  Only the pipelined weight-stationary kernel has
     that epilogue: a mirror of its dispatch conditions in csrc/gemm.hip (N = K = 320, M >= 8192, 32-bit extents, knobs GEMM_DMA /
-    GEMM_WS on and no forced tile configuration); elsewhere the consumer makes its statistics pass (row_stats)."""
+    GEMM_WS on and no forced tile configuration); elsewhere the consumer makes its statistics pass (row_stats).
+    The epilogue's statistics and row_stats agree to rounding, not bit for bit, so a row's route must not depend on the batch it runs
+    in: the size threshold is decided on `video_rows`, the rows of ONE video (default M), and M >= 8192 follows from it for every
+    batch.  Only the 4 GiB extents are checked on the whole call."""
     lim = 0xFFFF0000
     lda, ldc = K if lda is None else lda, N if ldc is None else ldc
-    ok = (LN_ROWSTATS and N == 320 and K == 320 and M >= 8192 and tune_get("GEMM_DMA") != 0 and tune_get("GEMM_WS") != 0 and tune_get("GEMM_CFG") < 0
-          and 2 * ((M - 1) * lda + K) < lim and 2 * (M + 256) * ldc < lim and 2 * (M + 256) * ldr < lim and 8 * M < lim)
+    per_video = M if video_rows is None else video_rows
+    ok = (LN_ROWSTATS and N == 320 and K == 320 and per_video >= 8192 and M >= per_video and tune_get("GEMM_DMA") != 0 and tune_get("GEMM_WS") != 0
+          and tune_get("GEMM_CFG") < 0 and 2 * ((M - 1) * lda + K) < lim and 2 * (M + 256) * ldc < lim and 2 * (M + 256) * ldr < lim and 8 * M < lim)
     if unit_rows is not None:
-        ok = ok and M // unit_rows > 1 and M // unit_rows <= 65535 and unit_rows % 32 == 0 and unit_rows >= 1024
+        ok = ok and M % unit_rows == 0 and M // unit_rows <= 65535 and unit_rows % 32 == 0 and unit_rows >= 1024
     return ok
 
 
@@ -162,7 +166,7 @@ def rowstats_buffer(M, device):
 def gemm_units(a, wn, bn, *, unit_rows, out=None, rowstats=None, rowstats_eps=1e-5):
     """out[M, N] = a[M, K] Wn[u]^T + bn[u] for the rows of unit u = m // unit_rows: wn [units, N, K] fp16, bn [units, N] fp32 (the
     sets of group_norm_fold_linear).  One launch of the weight-stationary kernel where it applies, else unit by unit (include/vcx.h).
-    `rowstats`: as in gemm (one-launch form only, see rowstats_ok)."""
+    `rowstats`: as in gemm (the one-launch form, or a single unit; see rowstats_ok)."""
     M, K = a.shape
     units, N, K2 = wn.shape
     _dev16(a, wn, out)
