@@ -14,9 +14,9 @@ import sys
 import numpy as np
 import torch
 
-from viewcrafter_amd import parallel
+from viewcrafter_amd import clip_batch, parallel
 from viewcrafter_amd.builder import build_diffusion_model
-from viewcrafter_amd.utils.diffusion_utils import image_guided_synthesis
+from viewcrafter_amd.utils.diffusion_utils import image_guided_synthesis, image_guided_synthesis_clips
 
 
 def _reference_root(opts):
@@ -82,6 +82,20 @@ class ViewCrafter:
                 condition_index)
         return torch.clamp(batch_samples[0][0].permute(1, 2, 3, 0), -1., 1.)
 
+    def _synthesis_args(self):
+        o = self.opts
+        return (o.n_samples, o.ddim_steps, o.ddim_eta, o.unconditional_guidance_scale, o.cfg_img, o.frame_stride, o.text_input,
+                o.multiple_cond_cfg, o.timestep_spacing, o.guidance_rescale)
+
+    def run_diffusion_clips(self, clips, streams):
+        """run_diffusion for several clips in ONE DDIM loop (VCX_CLIP_BATCH): `streams` is a clip_batch.ClipStreams of len(clips) clips.
+        Returns the list of [T, H, W, 3] results, each bit-identical to run_diffusion of that clip after its clip's seed."""
+        videos = [(r * 2. - 1.).permute(3, 0, 1, 2).unsqueeze(0).to(self.device) for r in clips]
+        with torch.no_grad():
+            outs = image_guided_synthesis_clips(self.diffusion, [self.opts.prompt], videos, self.noise_shape, *self._synthesis_args(),
+                                                condition_index=[0], streams=streams)
+        return [torch.clamp(o[0][0].permute(1, 2, 3, 0), -1., 1.) for o in outs]
+
     def run_diffusion_many(self, clips):
         """Independent trajectories / clips (each one `run_diffusion` call = one image_guided_synthesis) sharded over the
         ranks: rank r runs clips r, r + W, ... with NO collective inside the DDIM loop; the decoded clips are gathered on
@@ -89,8 +103,25 @@ class ViewCrafter:
         process it is a plain loop.  Clip i is seeded with opts.seed + i, so the result does not depend on the world size
         (clip 0 equals the reference's single-process run; later clips differ from the reference's one sequential generator
         stream - `nvs_sparse_view_interp` therefore keeps the reference's own loop when there is one process, and the
-        sharded launch is documented as a different, world-size-independent stream)."""
+        sharded launch is documented as a different, world-size-independent stream).
+
+        VCX_CLIP_BATCH=k (opt-in, default 1): a rank denoises its clips k at a time in ONE DDIM loop (run_diffusion_clips; k x 2 videos
+        per UNet forward with CFG), every clip drawing from its own generator state - the videos are bit-identical to the plain loop's.
+        k is capped where a forward would reach the GEMM engine's 4 GiB extents (clip_batch.max_clips_per_forward: k <= 3 with CFG at
+        576 x 1024 x 25, k <= 2 with multi-condition guidance).  Measured sign: README.md (multi-clip paragraph).  Not combined with
+        VCX_CLIPS_PER_GPU > 1 (refused)."""
         _, world = parallel.rank_world()
+        k = clip_batch.clip_batch_from_env()
+        if k > 1:      # capped per workload, never split inside a forward
+            copies = clip_batch.guidance_copies(self.opts.unconditional_guidance_scale, self.opts.multiple_cond_cfg, self.opts.cfg_img)
+            k = min(k, clip_batch.max_clips_per_forward(self.diffusion.model.diffusion_model, self.noise_shape, copies))
+        if k > 1:
+            def group(items, indices):
+                streams = clip_batch.ClipStreams([None if (world == 1 and i == 0) else self.opts.seed + i for i in indices])
+                outs = self.run_diffusion_clips(items, streams)
+                streams.finish()
+                return outs
+            return parallel.run_sharded_batched(group, list(clips), k, gather=True)
 
         def one(clip, index):
             if world > 1 or index > 0:

@@ -6,7 +6,10 @@ second stream can fill it - or get in its way: the builder's boxes measured +3.0
 clips (tools/two_stream_ab.py, profiles/r05q, r05ac, r05al, r05at), the driver's box of round 5 MINUS 8.7 % (BENCH_r05.json
 extra.two_clips_per_gpu: 5.329 steps/s one after the other, 4.865 on two streams, gain 0.913).  The sign depends on the box, so the mode
 is OPT-IN (VCX_CLIPS_PER_GPU=2; default 1 = one clip after the other); outputs are bit-identical either way.  Within one trajectory
-there is nothing independent to run (profiles/r05_experiments.md section 4).
+there is nothing independent to run (profiles/r05_experiments.md section 4).  The other opt-in way to run several clips per GPU is
+VCX_CLIP_BATCH=k (clip_batch.py): k clips stacked on the batch axis of ONE DDIM loop, also bit-identical; measured on one box at +3.3 / +5.5 %
+(k = 2 / 3, 576x1024x25) against +5.4 % for two streams (profiles/r07_clip_batch_ab.md).  The two modes are not combined: run_diffusion_many
+refuses VCX_CLIP_BATCH > 1 beside VCX_CLIPS_PER_GPU > 1.
 
 How: each clip runs the UNMODIFIED driver code (image_guided_synthesis: encoders, DDIM loop, decode) in its own host thread under its own
 `torch.cuda.stream`; a baton makes the threads take turns, and the sampler hands the baton on after every DDIM step (`step_yield`), so the

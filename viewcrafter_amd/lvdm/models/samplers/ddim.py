@@ -67,8 +67,10 @@ class DDIMSampler(object):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, schedule_verbose=False, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, precision=None, fs=None,
-               timestep_spacing="uniform", guidance_rescale=0.0, **kwargs):
-        """Reference ddim.py:62-134."""
+               timestep_spacing="uniform", guidance_rescale=0.0, noise_source=None, **kwargs):
+        """Reference ddim.py:62-134.  `noise_source` (not in the reference; default None = unchanged): a callable (shape, device) ->
+        Gaussian tensor that replaces the sampler's own draws of x_T (when x_T is not given) and of every step's noise - several clips in
+        one loop draw each clip's rows from that clip's generator (viewcrafter_amd/clip_batch.py)."""
         if conditioning is not None:
             first = conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning
             cbs = (first[0] if isinstance(first, (list, tuple)) else first).shape[0]
@@ -87,20 +89,23 @@ class DDIMSampler(object):
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
-                                  precision=precision, fs=fs, guidance_rescale=guidance_rescale, **kwargs)
+                                  precision=precision, fs=fs, guidance_rescale=guidance_rescale, noise_source=noise_source, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, verbose=True, precision=None, fs=None, guidance_rescale=0.0,
-                      **kwargs):
-        """Reference ddim.py:137-205."""
+                      noise_source=None, **kwargs):
+        """Reference ddim.py:137-205 (`noise_source`: see sample())."""
         if ddim_use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("DDPM-step / quantised / score-corrected sampling is not on the ViewCrafter path")
         device = self.model.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        if x_T is not None:
+            img = x_T.to(device=device, dtype=torch.float32)
+        else:
+            img = torch.randn(shape, device=device) if noise_source is None else noise_source(shape, device)
         if timesteps is None:
             timesteps = self.ddim_timesteps
         else:
@@ -121,7 +126,7 @@ class DDIMSampler(object):
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
-                                              fs=fs, guidance_rescale=guidance_rescale, **kwargs)
+                                              fs=fs, guidance_rescale=guidance_rescale, noise_source=noise_source, **kwargs)
             if callback:
                 callback(i)
             if img_callback:
@@ -196,8 +201,9 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, uc_type=None,
-                      conditional_guidance_scale_temporal=None, mask=None, x0=None, guidance_rescale=0.0, **kwargs):
-        """Reference ddim.py:208-281."""
+                      conditional_guidance_scale_temporal=None, mask=None, x0=None, guidance_rescale=0.0, noise_source=None,
+                      **kwargs):
+        """Reference ddim.py:208-281 (`noise_source`: see sample())."""
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("not on the ViewCrafter path")
         b, device = x.shape[0], x.device
@@ -215,7 +221,7 @@ class DDIMSampler(object):
             coef[0], coef[1] = float(np.sqrt(h["a"][index])), float(np.sqrt(1. - h["a"][index]))
         # the reference draws the noise unconditionally (ddim.py:275), also when sigma_t = 0 (eta = 0): draw it too, so that a
         # fixed seed leaves the generator in the same state (the x_T of a following sample() call); the kernel skips it
-        noise = noise_like(x.shape, device, repeat_noise)
+        noise = noise_like(x.shape, device, repeat_noise) if noise_source is None else noise_source(x.shape, device)
         noise = noise * temperature if sigma != 0.0 else None
         x_prev, pred_x0 = ops.ddim_step(x, v_c.contiguous(), v_u.contiguous() if v_u is not None else None, noise, coef,
                                         v_img=v_i.contiguous() if v_i is not None else None, cfg_img=cfg_img)

@@ -176,6 +176,20 @@ def run_sharded(fn, items, gather=True, lanes=1, model=None):
     return gather_results(local, len(items)) if gather else local
 
 
+def run_sharded_batched(fn, items, clip_batch, gather=True):
+    """run_sharded for a function of several items at once: fn(list of items, list of their indices) -> list of results.  The items this
+    rank owns go to fn `clip_batch` at a time, in order (the last group may be smaller; VCX_CLIP_BATCH, clip_batch.py)."""
+    from .clip_batch import groups
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+    local = {}
+    for group in groups(shard_indices(len(items), rank, world), max(1, int(clip_batch))):
+        outs = fn([items[i] for i in group], group)
+        if len(outs) != len(group):
+            raise ValueError(f"run_sharded_batched: {len(outs)} results for {len(group)} items")
+        local.update(zip(group, outs))
+    return gather_results(local, len(items)) if gather else local
+
+
 def shutdown(barrier=True):
     """(Barrier +) destroy_process_group when a group exists (end of a torchrun launch)."""
     if dist.is_initialized():

@@ -87,19 +87,10 @@ def get_latent_z(model, videos):
     return z.view(b, t, *z.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
 
 
-def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
-                           unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
-                           multiple_cond_cfg=False, timestep_spacing="uniform", guidance_rescale=0.0,
-                           condition_index=None, **kwargs):
-    """Reference diffusion_utils.py:117-201.  videos [B, 3, T, H, W] in [-1, 1]; returns [B, n_samples, 3, T, H, W]."""
-    from ..lvdm.models.samplers.ddim import DDIMSampler
-    if multiple_cond_cfg:
-        from ..lvdm.models.samplers.ddim_multiplecond import DDIMSampler as DDIMSamplerMulti
-        ddim_sampler = DDIMSamplerMulti(model)
-    else:
-        ddim_sampler = DDIMSampler(model)
-    batch_size = noise_shape[0]
-    fs = torch.tensor([fs] * batch_size, dtype=torch.long, device=model.device)
+def _conditioning(model, prompts, videos, batch_size, unconditional_guidance_scale, cfg_img, text_input, multiple_cond_cfg,
+                  condition_index):
+    """cond / uc / uc_2 of one image_guided_synthesis call (reference diffusion_utils.py:130-170): CLIP towers, Resampler and the VAE
+    encode of the hybrid concat input (which draws the posterior noise on the CPU generator)."""
     if not text_input:
         prompts = [""] * batch_size
     assert condition_index is not None, "Error: condition index is None!"
@@ -108,6 +99,7 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     img_emb = model.image_proj_model(model.embedder(img))
     cond_emb = model.get_learned_conditioning(prompts)
     cond = {"c_crossattn": [torch.cat([cond_emb, img_emb], dim=1)]}
+    img_cat_cond = None
     if model.model.conditioning_key == "hybrid":
         img_cat_cond = get_latent_z(model, videos)
         cond["c_concat"] = [img_cat_cond]
@@ -128,9 +120,30 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
         uc_2 = {"c_crossattn": [torch.cat([uc_emb, img_emb], dim=1)]}
         if model.model.conditioning_key == "hybrid":
             uc_2["c_concat"] = [img_cat_cond]
-        kwargs.update({"unconditional_conditioning_img_nonetext": uc_2})
     else:
-        kwargs.update({"unconditional_conditioning_img_nonetext": None})
+        uc_2 = None
+    return cond, uc, uc_2
+
+
+def _sampler(model, multiple_cond_cfg):
+    from ..lvdm.models.samplers.ddim import DDIMSampler
+    if multiple_cond_cfg:
+        from ..lvdm.models.samplers.ddim_multiplecond import DDIMSampler as DDIMSamplerMulti
+        return DDIMSamplerMulti(model)
+    return DDIMSampler(model)
+
+
+def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
+                           unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
+                           multiple_cond_cfg=False, timestep_spacing="uniform", guidance_rescale=0.0,
+                           condition_index=None, **kwargs):
+    """Reference diffusion_utils.py:117-201.  videos [B, 3, T, H, W] in [-1, 1]; returns [B, n_samples, 3, T, H, W]."""
+    ddim_sampler = _sampler(model, multiple_cond_cfg)
+    batch_size = noise_shape[0]
+    fs = torch.tensor([fs] * batch_size, dtype=torch.long, device=model.device)
+    cond, uc, uc_2 = _conditioning(model, prompts, videos, batch_size, unconditional_guidance_scale, cfg_img, text_input,
+                                   multiple_cond_cfg, condition_index)
+    kwargs.update({"unconditional_conditioning_img_nonetext": uc_2})
 
     batch_variants = []
     for _ in range(n_samples):
@@ -141,3 +154,61 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
                                          **kwargs)
         batch_variants.append(model.decode_first_stage(samples))
     return torch.stack(batch_variants).permute(1, 0, 2, 3, 4, 5)
+
+
+def _stack(conds):
+    """Per-clip conditioning dicts (or None) stacked on the batch axis, entry by entry."""
+    if conds[0] is None:
+        return None
+    return {key: [torch.cat([c[key][j] for c in conds], dim=0) for j in range(len(conds[0][key]))] for key in conds[0]}
+
+
+def image_guided_synthesis_clips(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
+                                 unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
+                                 multiple_cond_cfg=False, timestep_spacing="uniform", guidance_rescale=0.0,
+                                 condition_index=None, streams=None, **kwargs):
+    """k independent clips in ONE DDIM loop (VCX_CLIP_BATCH, viewcrafter_amd/clip_batch.py).  `videos`: a list of k tensors
+    [b, 3, T, H, W] (b = noise_shape[0]); `prompts`: one prompt list for every clip or a list of k such lists; `streams`: a
+    clip_batch.ClipStreams of k clips, whose contexts every random draw of clip i is made in.  Each clip's cond / uncond is built on its
+    own, the conditionings are stacked on the batch axis, one sampler runs over B = k b (k b x 2 videos per forward with CFG, x 3 with
+    multi-condition guidance) and each clip's latent is decoded on its own.  Returns a list of k tensors [b, n_samples, 3, T, H, W],
+    each bit-identical to image_guided_synthesis of that clip after its clip's seed."""
+    k = len(videos)
+    if streams is None or len(streams) != k:
+        raise ValueError(f"image_guided_synthesis_clips needs a ClipStreams of {k} clips")
+    if prompts and isinstance(prompts[0], (list, tuple)):
+        if len(prompts) != k:
+            raise ValueError(f"{len(prompts)} prompt lists for {k} clips")
+        per_clip_prompts = [list(p) for p in prompts]
+    else:
+        per_clip_prompts = [prompts] * k
+    b = noise_shape[0]
+    for v in videos:
+        if v.shape[0] != b:
+            raise ValueError(f"every clip needs batch {b} (noise_shape[0]), got {tuple(v.shape)}")
+    ddim_sampler = _sampler(model, multiple_cond_cfg)
+    parts = []
+    for i in range(k):
+        with streams.clip(i):
+            parts.append(_conditioning(model, per_clip_prompts[i], videos[i], b, unconditional_guidance_scale, cfg_img, text_input,
+                                       multiple_cond_cfg, condition_index))
+    cond = _stack([p[0] for p in parts])
+    uc, uc_2 = _stack([p[1] for p in parts]), _stack([p[2] for p in parts])
+    for c in (uc, uc_2):
+        if c is not None and "c_concat" in c:
+            c["c_concat"] = cond["c_concat"]        # one object, as within each clip: the sampler keeps the shared CFG prefix route
+    fs = torch.tensor([fs] * (k * b), dtype=torch.long, device=model.device)
+    kwargs.update({"unconditional_conditioning_img_nonetext": uc_2})
+
+    variants = [[] for _ in range(k)]
+    for _ in range(n_samples):
+        shape = [k * b] + list(noise_shape[1:])
+        x_T = streams.randn(shape, device=model.device)
+        samples, _ = ddim_sampler.sample(S=ddim_steps, conditioning=cond, batch_size=k * b, shape=noise_shape[1:],
+                                         verbose=False, unconditional_guidance_scale=unconditional_guidance_scale,
+                                         unconditional_conditioning=uc, eta=ddim_eta, cfg_img=cfg_img, mask=None, x0=None,
+                                         fs=fs, timestep_spacing=timestep_spacing, guidance_rescale=guidance_rescale,
+                                         x_T=x_T, noise_source=streams, **kwargs)
+        for i in range(k):
+            variants[i].append(model.decode_first_stage(samples[i * b:(i + 1) * b].contiguous()))
+    return [torch.stack(v).permute(1, 0, 2, 3, 4, 5) for v in variants]
