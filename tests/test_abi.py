@@ -193,3 +193,95 @@ def test_ddim_workspace_contract():
     fake = 1 << 20                                      # never dereferenced: the size check comes first
     rc = L.vcx_ddim_step3_f32(fake, fake, fake, None, None, fake, fake, fake, need - 8, 2, n, coef, None)
     assert rc == -1 and b"vcx_ddim_ws_bytes" in L.vcx_last_error()          # VCX_EINVAL
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Calls past the engine's extent limit that carry a flag only the 32-bit kernels implement must be REJECTED, not routed to the
+# register-staged kernel (which has no such epilogue) and not run on wrapped offsets.  Every check sits in front of the first launch,
+# so fake pointers serve (as in test_ddim_workspace_contract) and the cases run on a GPU-less host.
+# ---------------------------------------------------------------------------------------------------------------------------------
+LIM = 0xFFFF0000          # csrc/gemm.hip `lim`
+FAKE = 1 << 20            # 16-byte aligned, never dereferenced
+EINVAL = -1
+
+
+def _gemm_rc(units=None, **kw):
+    d = _lib.GemmDesc()
+    d.A = d.W = d.C = FAKE
+    d.alpha = 1.0
+    for k, v in kw.items():
+        setattr(d, k, v)
+    if not d.ldw:
+        d.ldw = d.K
+    L = _lib.lib()
+    rc = L.vcx_gemm_f16(ctypes.byref(d), None) if units is None else L.vcx_gemm_units_f16(ctypes.byref(d), units, d.N * d.K, d.N, None)
+    return rc, L.vcx_last_error()
+
+
+def _rows_at_limit(ld, K):
+    """the smallest M with 2 ((M - 1) ld + K) >= lim: the first row count whose operand extent leaves the 32-bit kernels"""
+    M = (LIM // 2 - K + ld - 1) // ld + 1
+    assert 2 * ((M - 1) * ld + K) >= LIM > 2 * ((M - 2) * ld + K)
+    return M
+
+
+def test_large_extent_flagged_gemm_calls_are_rejected_past_lim():
+    G = _lib
+    stats = dict(ln_stats=FAKE, ln_colsum=FAKE)
+    M = _rows_at_limit(4096, 64)                         # 524281 rows of 4096 elements: a_ext >= lim through the row stride
+    assert (M + 7) % 8 == 0
+    # LNFOLD: operand, weight-side operand (LNFOLD_T: the token rows are W) and output extents
+    for name, kw in [("lnfold_a_past_lim", dict(M=M, N=64, K=64, lda=4096, ldc=64, flags=G.GEMM_LNFOLD, **stats)),
+                     ("lnfold_out_past_lim", dict(M=(LIM // (2 * 4096)) - 256 + 1, N=64, K=64, lda=64, ldc=4096, flags=G.GEMM_LNFOLD, **stats)),
+                     ("lnfold_t_w_past_lim", dict(M=64, N=M + 7, K=64, lda=64, ldw=4096, ldc=M + 7, flags=G.GEMM_LNFOLD_T, **stats))]:
+        rc, msg = _gemm_rc(**kw)
+        assert rc == EINVAL and b"LNFOLD" in msg, (name, rc, msg)
+    # COLSTATS (M % 64 == 0): operand past lim; output past lim
+    Mc = (M + 63) // 64 * 64
+    for name, kw in [("colstats_a_past_lim", dict(M=Mc, N=64, K=64, lda=4096, ldc=64)), ("colstats_out_past_lim", dict(M=Mc, N=64, K=64, lda=64, ldc=4096))]:
+        rc, msg = _gemm_rc(flags=G.GEMM_COLSTATS, colstats=FAKE, **kw)
+        assert rc == EINVAL and b"COLSTATS" in msg, (name, rc, msg)
+    # ... and as a convolution whose 256-channel input is the 7.5 GB tensor of a 25-frame VAE decode
+    conv = dict(mode=1, in_h=576, in_w=1024, out_h=576, out_w=1024, cin=256, kh=3, kw=3, stride=1, pad_h=1, pad_w=1)
+    rc, msg = _gemm_rc(M=25 * 576 * 1024, N=128, K=9 * 256, lda=256, ldc=128, flags=G.GEMM_COLSTATS | G.GEMM_CONV_SLABK, colstats=FAKE, **conv)
+    assert rc == EINVAL and b"COLSTATS" in msg, (rc, msg)
+    # K tail: the image past lim; the tail source past lim
+    conv1 = dict(conv, cin=64, kh=1, kw=1, pad_h=0, pad_w=0)
+    rc, msg = _gemm_rc(M=25 * 576 * 1024, N=64, K=9 * 256 + 64, lda=256, ldc=64, flags=G.GEMM_CONV_SLABK, tail_a0=FAKE, tail_lda0=64, tail_k0=64, **conv)
+    assert rc == EINVAL and b"K tail" in msg, (rc, msg)
+    rc, msg = _gemm_rc(M=2 * 576 * 1024, N=64, K=64 + 64, lda=64, ldc=64, flags=G.GEMM_CONV_SLABK, tail_a0=FAKE, tail_lda0=4096, tail_k0=64, **conv1)
+    assert 2 * ((2 * 576 * 1024 - 1) * 4096 + 64) >= LIM and rc == EINVAL and b"K tail" in msg, (rc, msg)
+    # ROWSTATS (N = K = 320): operand through the row stride, output, residual, and the statistics buffer itself (8 M >= lim; a
+    # broadcast row, lda = ldc = 0, keeps every other extent small so that this guard is the one that answers)
+    M3 = _rows_at_limit(4096, 320)
+    rs = dict(N=320, K=320, rowstats=FAKE, rowstats_eps=1e-5)
+    for name, kw in [("rowstats_a_past_lim", dict(M=M3, lda=4096, ldc=320)), ("rowstats_out_past_lim", dict(M=M3, lda=320, ldc=4096)),
+                     ("rowstats_res_past_lim", dict(M=M3, lda=320, ldc=320, ldr=4096, residual=FAKE, flags=G.GEMM_RESIDUAL)),
+                     ("rowstats_buffer_past_lim", dict(M=LIM // 8, lda=0, ldc=0))]:
+        kw = dict(rs, **kw)
+        kw["flags"] = kw.get("flags", 0) | G.GEMM_ROWSTATS
+        rc, msg = _gemm_rc(**kw)
+        assert rc == EINVAL and b"ROWSTATS" in msg, (name, rc, msg)
+    # vcx_gemm_units_f16: more than one unit, operand past lim -> no one-launch form -> ROWSTATS has no kernel
+    Mu = (M3 + 1023) // 1024 * 1024
+    rc, msg = _gemm_rc(units=1024, M=Mu, lda=4096, ldc=320, bias=FAKE, flags=G.GEMM_BIAS_N | G.GEMM_ROWSTATS, **rs)
+    assert rc == EINVAL and b"ROWSTATS" in msg, (rc, msg)
+
+
+def test_large_extent_attention_and_row_kernels_reject_what_they_cannot_address():
+    L = _lib.lib()
+    nk = 9216
+    ldk = ((LIM // 2 - 64 + nk - 2) // (nk - 1) + 7) // 8 * 8          # first multiple of 8 with ((nk - 1) ldk + 64) 2 >= 4 GiB - 64 KiB
+    assert ((nk - 1) * ldk + 64) * 2 >= LIM > ((nk - 1) * (ldk - 8) + 64) * 2
+    ldvt = ((LIM // 2 - nk - 8 + 62) // 63 + 7) // 8 * 8
+    assert (63 * ldvt + nk + 8) * 2 >= LIM > (63 * (ldvt - 8) + nk + 8) * 2
+    for name, lk, lv in [("flash_k_past_lim", ldk, nk), ("flash_vt_past_lim", 960, ldvt)]:
+        rc = L.vcx_attn_flash_d64_f16(FAKE, FAKE, FAKE, FAKE, 1, 1, nk, nk, nk, 1, 960, lk, lv, 64, 0.125, 0, None)
+        assert rc == EINVAL and b"4 GiB" in L.vcx_last_error(), (name, rc, L.vcx_last_error())
+        rc = L.vcx_attn_flash_dual_d64_f16(FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, 1, 1, nk, 80, 80, 1, 64, 80, nk, nk, 1, lk, lv, 960, 64, 0.125, 0, None)
+        assert rc == EINVAL and b"4 GiB" in L.vcx_last_error(), (name, rc, L.vcx_last_error())
+    gamma = FAKE
+    rc = L.vcx_layernorm_f16(FAKE, FAKE, gamma, gamma, 1 << 31, 64, 1e-5, None)
+    assert rc == EINVAL and b"too many rows" in L.vcx_last_error()
+    rc = L.vcx_rowstats_f16(FAKE, FAKE, 1 << 31, 64, 1e-5, None)
+    assert rc == EINVAL and b"too many rows" in L.vcx_last_error()

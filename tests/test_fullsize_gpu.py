@@ -53,7 +53,7 @@ def test_conv_delta_kernel_is_a_shift_at_full_size(C, h, w, ups):
     n = B * T
     x = torch.randn(n, h, w, C, device=DEV).half()
     xu = x if not ups else x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
-    for ky, kx in ((0, 0), (1, 1), (2, 1), (0, 2)):
+    for ky, kx in ((ky, kx) for ky in range(3) for kx in range(3)):
         wt = torch.zeros(C, C, 3, 3, device=DEV)
         wt[torch.arange(C), torch.arange(C), ky, kx] = 1.0
         y = ops.conv2d(x, pack_conv(wt.half()), None, kh=3, kw=3, ups=ups)

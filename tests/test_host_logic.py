@@ -799,3 +799,71 @@ def test_batch_routes_at_the_shipped_latents_keep_the_fast_paths(monkeypatch, ya
     rowstats_linear = [e for e in log if e[0] == "gemm" and e[7]]
     assert len(rowstats_linear) == 2, rowstats_linear          # attn1's output projection, spatial and temporal
     assert not [e for e in log if e[0] == "row_stats"], "a LayerNorm statistics pass at level 0"
+
+
+def _first_false(ok, lo, hi):
+    """the smallest row count in (lo, hi] where the monotone predicate ok() turns false (ok(lo) true, ok(hi) false)"""
+    assert ok(lo) and not ok(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if ok(mid) else (lo, mid)
+    return hi
+
+
+def test_python_mirrors_of_the_extent_limit_flip_where_the_dispatcher_starts_rejecting():
+    """The host graph asks ops.lnfold_ok / colstats_ok / rowstats_ok / conv_tail_ok / attention.fold_extent_ok before it sends a flagged
+    call, and clip_batch caps a forward with its own copy of the limit.  Each mirror must turn false at exactly the row count where
+    vcx_gemm_f16 starts to reject the same call (one row below: mirror true; at it: mirror false and the C dispatcher rejects, checked
+    with fake pointers - the rejection comes before any launch), or a batched forward could send a flagged call across the line."""
+    from tests.test_abi import EINVAL, FAKE, LIM, _gemm_rc
+    from viewcrafter_amd import _lib as G, clip_batch, ops
+    from viewcrafter_amd.lvdm.modules import attention as A
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "viewcrafter_amd", "csrc", "gemm.hip")).read()
+    assert set(re.findall(r"lim = (0x[0-9A-Fa-f]+)ull", src)) == {"0xFFFF0000"} and LIM == clip_batch._LIM == 0xFFFF0000
+    stats = dict(ln_stats=FAKE, ln_colsum=FAKE)
+    # LNFOLD: operand extent through the row stride / output extent incl. the 256 rows past the end
+    m = _first_false(lambda r: ops.lnfold_ok(r, 64, 64, lda=4096), 1000, 1 << 22)
+    assert m == 524281 and _gemm_rc(M=m, N=64, K=64, lda=4096, ldc=64, flags=G.GEMM_LNFOLD, **stats)[0] == EINVAL
+    m = _first_false(lambda r: ops.lnfold_ok(r, 960, 320), 460800, 1 << 24)          # q | k | v of level 0: the output (ldc = 960) goes first
+    assert 2 * (m + 256) * 960 >= LIM > 2 * (m + 255) * 960 and _gemm_rc(M=m, N=960, K=320, lda=320, ldc=960, flags=G.GEMM_LNFOLD, **stats)[0] == EINVAL
+    m = _first_false(lambda r: ops.lnfold_ok(8 * r, 320, 320, transposed=True), 1000, 1 << 22) * 8      # LNFOLD_T: the token rows are the W operand
+    assert _gemm_rc(M=320, N=m, K=320, lda=320, ldw=320, ldc=m, flags=G.GEMM_LNFOLD_T | G.GEMM_BIAS_M, bias=FAKE, **stats)[0] == EINVAL
+    assert ops.lnfold_ok(m - 8, 320, 320, transposed=True)
+    # COLSTATS of a linear layer / a convolution (whole 64-row strips): output extent, then the input extent (in_rows)
+    m = _first_false(lambda s: ops.colstats_ok(64 * s, 64, 320, 2560), 100, 1 << 20) * 64
+    rc, msg = _gemm_rc(M=m, N=2560, K=320, lda=320, ldc=2560, flags=G.GEMM_COLSTATS, colstats=FAKE)
+    assert 2 * (m + 256) * 2560 >= LIM > 2 * (m - 64 + 256) * 2560 and rc == EINVAL and b"COLSTATS" in msg
+    n = _first_false(lambda k: ops.colstats_ok(k * 9216, 9216, 960, 320, in_rows=k * 9216), 50, 4000)      # frames of 72 x 128, 960 -> 320
+    conv = dict(mode=1, in_h=72, in_w=128, out_h=72, out_w=128, cin=960, kh=3, kw=3, stride=1, pad_h=1, pad_w=1)
+    rc, msg = _gemm_rc(M=n * 9216, N=320, K=9 * 960, lda=960, ldc=320, flags=G.GEMM_COLSTATS | G.GEMM_CONV_SLABK, colstats=FAKE, **conv)
+    assert 2 * n * 9216 * 960 >= LIM > 2 * (n - 1) * 9216 * 960 and n > 175 and rc == EINVAL and b"COLSTATS" in msg      # 175 frames = 7 videos pass
+    # K tail of that convolution (640 + 320 columns of the folded skip convolution)
+    n = _first_false(lambda k: ops.conv_tail_ok(k * 9216, 960, 320, 9, (640, 320)), 50, 4000)
+    rc, msg = _gemm_rc(M=n * 9216, N=320, K=9 * 960 + 960, lda=960, ldc=320, flags=G.GEMM_CONV_SLABK, tail_a0=FAKE, tail_lda0=640, tail_k0=640,
+                       tail_a1=FAKE, tail_lda1=320, tail_k1=320, **conv)
+    assert rc == EINVAL and b"K tail" in msg
+    # ROWSTATS: extents of the call, and the statistics buffer (8 M) on its own
+    rs = dict(N=320, K=320, rowstats=FAKE, rowstats_eps=1e-5, flags=G.GEMM_ROWSTATS)
+    m = _first_false(lambda r: ops.rowstats_ok(r, 320, 320), 460800, 1 << 24)
+    assert 2 * (m + 256) * 320 >= LIM > 2 * (m + 255) * 320 and _gemm_rc(M=m, lda=320, ldc=320, **rs)[0] == EINVAL
+    m = _first_false(lambda r: ops.rowstats_ok(r, 320, 320, lda=4096), 460800, 1 << 24)
+    assert 2 * ((m - 1) * 4096 + 320) >= LIM and _gemm_rc(M=m, lda=4096, ldc=320, **rs)[0] == EINVAL
+    m = _first_false(lambda r: ops.rowstats_ok(r, 320, 320, lda=0, ldc=0), 460800, 1 << 30)
+    assert m == LIM // 8 and _gemm_rc(M=m, lda=0, ldc=0, **rs)[0] == EINVAL
+    # the one-launch vcx_gemm_units_f16 (GroupNorm folded into proj_in): its output bound is fold_extent_ok
+    u = _first_false(lambda k: A.fold_extent_ok(k * 9216, 320), 50, 4000)
+    assert 2 * (u * 9216 + 256) * 320 >= LIM > 2 * ((u - 1) * 9216 + 256) * 320 and not ops.rowstats_ok(u * 9216, 320, 320, unit_rows=9216)
+    rc, msg = _gemm_rc(units=9216, M=u * 9216, lda=320, ldc=320, bias=FAKE, **dict(rs, flags=G.GEMM_ROWSTATS | G.GEMM_BIAS_N))
+    assert rc == EINVAL and b"ROWSTATS" in msg          # (without the flag the call would leave the one-launch form and run unit by unit)
+
+    # the clip-batch cap: the widest tensor of n videos (GEGLU output, 4 x 320 columns, and its 2560-column packed projection) stays
+    # on the 32-bit routes, n + 1 does not - by the dispatcher's own arithmetic (out_ok) and by the mirrors
+    class U:
+        model_channels, channel_mult, attention_resolutions = 320, (1, 2, 4, 4), (4, 2, 1)
+    V = 25 * 72 * 128
+    n = clip_batch.max_videos_per_forward(U, 25, 72, 128)
+    assert n == 7 and 2 * (n * V + 256) * 1280 < LIM <= 2 * ((n + 1) * V + 256) * 1280
+    assert ops.lnfold_ok(n * V, 1280, 320, ldc=1280) and not ops.lnfold_ok((n + 1) * V, 1280, 320, ldc=1280)
+    assert ops.colstats_ok(n * V, V, 1280, 320) and not ops.colstats_ok((n + 1) * V, V, 1280, 320)
+    rc, msg = _gemm_rc(M=(n + 1) * V, N=320, K=1280, lda=1280, ldc=320, flags=G.GEMM_COLSTATS, colstats=FAKE)       # the layer behind it, reading 8 videos
+    assert rc == EINVAL and b"COLSTATS" in msg
