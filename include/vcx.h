@@ -362,7 +362,11 @@ int vcx_profile_end(double* out_host);
  * launch.  vcx_tune_set returns the previous value.  bench.py prints every knob that is
  * not at its default next to the numbers it measured.
  * ---------------------------------------------------------------------------------- */
-#define VCX_TUNE_GEMM_CFG 0        /* -1 auto | 0..3 force tile config 128x128 / 128x160 / 256x256 / 256x320 */
+#define VCX_TUNE_GEMM_CFG 0        /* -1 auto (the tile plan) | 0..3 force tile config 128x128 / 128x160 / 256x256 / 256x320 |
+                                    * 4..6 force a 64-row tail config for the whole problem: 64x128, 64x64, 64x128 (GEGLU only); tests, A/Bs.
+                                    * Debug switch, not a knob: with VCX_GEMM_PLAN_TRACE set in the environment (read per call) vcx_gemm_f16
+                                    * prints one line per launch of the tiled engine to stderr,
+                                    * "[vcx] gemm plan M= N= K= seg i/n: cfg C rows BEGIN+ROWS grid G" (tools/gemm_cfg_scan.py, tests). */
 #define VCX_TUNE_GEMM_DMA 1        /* 1 | 0 = register-staged kernel everywhere                              */
 #define VCX_TUNE_FLASH_QB 2        /* 0 auto | 1 | 2 query blocks of 32 rows per wave (v1 kernel)            */
 #define VCX_TUNE_XATTN_RESIDENT 3  /* 1 | 0 = never use the LDS-resident cross-attention kernel | 2 = its first form */

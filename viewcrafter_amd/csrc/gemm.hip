@@ -354,6 +354,15 @@ __global__ void __launch_bounds__(NTHREADS, 2) gemm_kernel(GemmArgs p) {
 }
 
 }  // namespace
+// the grid of a persistent launch on a chip of ncu CUs (a pure function: the tile plan below prices grids with it)
+static int grid_for(int ntiles, int blocks_per_cu, int ncu) {
+    const int slots = blocks_per_cu * ncu;   // resident blocks chip-wide (LDS- and VGPR-limited)
+    if (ntiles <= slots) return ntiles;
+    const int rounds = (ntiles + slots - 1) / slots;          // balance: every block gets rounds or rounds-1 tiles
+    int g = (ntiles + rounds - 1) / rounds;
+    g = (g + 7) & ~7;                                         // multiple of 8 keeps a block's tiles on one XCD band
+    return g < slots ? g : slots;
+}
 int vcxgemm::persistent_grid(int ntiles, int blocks_per_cu) {
     static std::atomic<int> cached{0};       // every GPU of a node is the same part: one query per process
     int ncu = cached.load(std::memory_order_relaxed);
@@ -365,12 +374,104 @@ int vcxgemm::persistent_grid(int ntiles, int blocks_per_cu) {
             ncu = prop.multiProcessorCount;
         cached.store(ncu, std::memory_order_relaxed);
     }
-    const int slots = blocks_per_cu * ncu;   // resident blocks chip-wide (LDS- and VGPR-limited)
-    if (ntiles <= slots) return ntiles;
-    const int rounds = (ntiles + slots - 1) / slots;          // balance: every block gets rounds or rounds-1 tiles
-    int g = (ntiles + rounds - 1) / rounds;
-    g = (g + 7) & ~7;                                         // multiple of 8 keeps a block's tiles on one XCD band
-    return g < slots ? g : slots;
+    return grid_for(ntiles, blocks_per_cu, ncu);
+}
+
+// ---- tile plan of the DMA engine -------------------------------------------------------------------------------------------------
+// Which tile configuration(s) (gemm_dma.hip launch_dma) compute a problem.  Large tiles (256 rows, one block per CU) halve the LDS
+// traffic per MFMA, but a partial last round of them costs a whole tile time, so a problem is at most two launches on one stream:
+// whole rounds of large tiles, then the remaining rows on a smaller configuration.  The tile shape does not enter a row's
+// arithmetic (64-deep K-steps in order, the same MFMA), so every plan gives the same bits.
+struct TileSeg { int cfg, m_begin, rows, grid; };
+struct TilePlan { int n; TileSeg seg[2]; float cost; };
+// epilogue kind, as far as the choice of configurations goes: PLAIN = every non-GEGLU epilogue that the 64-row configurations have,
+// GEGLU = a linear GEGLU projection; the _ONLY128 kinds (fp32 output, LNFOLD_T; GEGLU of a convolution) have the 128-row tails only
+enum { EPI_PLAIN = 0, EPI_GEGLU = 1, EPI_PLAIN_ONLY128 = 2, EPI_GEGLU_ONLY128 = 3 };
+
+struct TileCost {
+    int tbm, tbn, bpc;
+    float k_alone, k_share;      // microseconds per 64-deep K-step of one block: alone on its CU / when the launch has more blocks than CUs
+    float e;                     // ... per tile besides its K-steps (pipeline fill, epilogue, stores)
+};
+// Measured on an MI355X (256 CUs).  k_alone and e: tools/gemm_tile_cost.py, every configuration forced (knob GEMM_CFG) on
+// linear problems of ncu, 2 ncu and 4 ncu tiles at K = 1152 and 2304 (profiles/r08a_tile_cost.txt).  k_share: that tool's two-blocks-per-CU
+// figure holds for ONE round only (0.90 / 1.10 / 0.59 / 0.48 / 0.64); over several rounds of a real layer every configuration runs at the
+// figures below - whole problems of the benchmark under each forced configuration, time / rounds / K-steps (tools/gemm_cfg_scan.py,
+// profiles/r08b_gemm_cfg_scan.txt; write-up profiles/r08_tile_plan.md section 2).  Re-measure when a kernel of the engine or the part changes.
+static const TileCost TILE_COST[7] = {
+    {128, 128, 2, 0.66f, 1.14f, 3.2f},
+    {128, 160, 2, 0.70f, 1.16f, 2.8f},
+    {256, 256, 1, 1.63f, 1.63f, 5.0f},      // (1.48 / 1.86 on the cache-resident problems of the tool; sustained over a layer's rounds:)
+    {256, 320, 1, 2.05f, 2.05f, 5.4f},
+    {64, 128, 2, 0.54f, 0.81f, 1.3f},       // 1x4 waves, 64 x 32 per wave
+    {64, 64, 2, 0.46f, 0.73f, 1.3f},        // 1x4 waves, 64 x 16 per wave
+    {64, 128, 2, 0.57f, 0.67f, 1.6f},       // 2x2 waves, 32 x 64 per wave (GEGLU)
+};
+constexpr float LAUNCH_COST = 4.0f;      // microseconds a launch costs beyond its tiles (2.7 ... 6.2 over the configurations)
+
+static TileSeg plan_seg(int cfg, int m_begin, int rows, int N, int ncu) {
+    const TileCost& t = TILE_COST[cfg];
+    const int tiles = ((rows + t.tbm - 1) / t.tbm) * ((N + t.tbn - 1) / t.tbn);
+    return TileSeg{cfg, m_begin, rows, grid_for(tiles, t.bpc, ncu)};
+}
+static float seg_cost(const TileSeg& g, int N, int K, int ncu) {
+    const TileCost& t = TILE_COST[g.cfg];
+    const int tiles = ((g.rows + t.tbm - 1) / t.tbm) * ((N + t.tbn - 1) / t.tbn);
+    const int per_block = (tiles + g.grid - 1) / g.grid;      // rounds: the tiles of the longest-running block
+    const bool share = g.grid > ncu;
+    return LAUNCH_COST + per_block * ((float)(K / BK) * (share ? t.k_share : t.k_alone) + t.e);
+}
+
+// A pure function of its arguments.  Candidates: the whole problem on small tiles; where large tiles apply (N and the tile count, as
+// before: from 1.5 rounds on), the whole problem on them, and `full` or `full - 1` whole rounds of them followed by the remaining rows
+// in each smaller configuration that has the epilogue.  Cheapest under seg_cost wins; earlier candidates win ties.
+static TilePlan plan_tiles(int M, int N, int K, int epi, int ncu) {
+    const bool geglu = epi == EPI_GEGLU || epi == EPI_GEGLU_ONLY128;
+    const int small = (!geglu && N % 160 == 0) ? 1 : 0;
+    const int big_bn = (N % 320 == 0 && !geglu) ? 320 : ((N % 256 == 0 || N >= 1024) ? 256 : 0);
+    TilePlan best;
+    auto consider = [&](int n, TileSeg a, TileSeg b, bool first) {
+        const float c = seg_cost(a, N, K, ncu) + (n == 2 ? seg_cost(b, N, K, ncu) : 0.f);
+        if (first || c < best.cost) best = TilePlan{n, {a, b}, c};
+    };
+    const TileSeg none{0, 0, 0, 0};
+    consider(1, plan_seg(small, 0, M, N, ncu), none, true);
+    if (!big_bn) return best;
+    const int large = big_bn == 320 ? 3 : 2;
+    const int tiles_m = (M + 255) / 256, tiles_n = (N + big_bn - 1) / big_bn;
+    const long long tiles = (long long)tiles_m * tiles_n;
+    if (tiles < 384) return best;
+    consider(1, plan_seg(large, 0, M, N, ncu), none, true);      // (large tiles beat small ones from here on: measured, the rule of rounds 1-6)
+    int tails[3], ntails = 0;
+    tails[ntails++] = small;
+    if (epi == EPI_PLAIN) { tails[ntails++] = 4; tails[ntails++] = 5; }
+    if (epi == EPI_GEGLU) tails[ntails++] = 6;
+    const long long full = tiles / ncu;
+    for (long long r = full; r >= 1 && r >= full - 1; --r) {
+        const int m1 = (int)(r * ncu / tiles_n) * 256;
+        if (m1 <= 0 || m1 >= M) continue;
+        for (int i = 0; i < ntails; ++i) consider(2, plan_seg(large, 0, m1, N, ncu), plan_seg(tails[i], m1, M - m1, N, ncu), false);
+    }
+    return best;
+}
+
+// GEMM_CFG >= 0 (A/B tools, tests): one configuration for the whole problem; under a forced large configuration the split rule of
+// rounds 1-6 (a remainder below 0.7 rounds goes to the 128-row tiles), which the batch-invariance tests mirror
+static TilePlan forced_plan(int M, int N, int cfg, bool geglu, int ncu) {
+    TilePlan p{1, {plan_seg(cfg, 0, M, N, ncu), TileSeg{0, 0, 0, 0}}, 0.f};
+    if (cfg == 2 || cfg == 3) {
+        const TileCost& t = TILE_COST[cfg];
+        const int tiles_n = (N + t.tbn - 1) / t.tbn;
+        const long long tiles = (long long)((M + 255) / 256) * tiles_n;
+        const long long full = tiles / ncu, rem = tiles % ncu;
+        const int m1 = (int)(full * ncu / tiles_n) * 256;
+        if (full >= 1 && rem > 0 && rem * 10 < (long long)ncu * 7 && m1 > 0 && m1 < M) {
+            p.n = 2;
+            p.seg[0] = plan_seg(cfg, 0, m1, N, ncu);
+            p.seg[1] = plan_seg((geglu || N % 160 != 0) ? 0 : 1, m1, M - m1, N, ncu);
+        }
+    }
+    return p;
 }
 namespace {
 
@@ -558,45 +659,35 @@ extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
     VCX_REQUIRE(!(flags & VCX_GEMM_ROWSTATS), "vcx_gemm_f16: ROWSTATS needs the weight-stationary kernel (linear, N = K = 320, M >= 8192, BIAS_N / RESIDUAL at most, knob GEMM_WS on); M=%d N=%d K=%d flags=0x%x",
                 d->M, d->N, d->K, flags);
     if (dma_ok) {
-        // tile choice: the large (256-row, 8-wave) tiles halve the LDS traffic per MFMA but need >= ~1.5 waves of 256 tiles
-        const int force = vcx_tune(VCX_TUNE_GEMM_CFG);      // -1 in production; tools/gemm_quick.py A/Bs tile configurations
-        int cfg = use160 ? 1 : 0;
-        const int big_bn = (d->N % 320 == 0 && !geglu) ? 320 : ((d->N % 256 == 0 || d->N >= 1024) ? 256 : 0);
-        if (big_bn) {
-            const long long tiles = (long long)((d->M + 255) / 256) * ((d->N + big_bn - 1) / big_bn);
-            if (tiles >= 384) cfg = big_bn == 320 ? 3 : 2;
+        // tile choice: plan_tiles above; a forced configuration (knob GEMM_CFG >= 0; tools/gemm_quick.py, tests) replaces the plan
+        const int force = vcx_tune(VCX_TUNE_GEMM_CFG);      // -1 in production
+        const int ncu = persistent_grid(1 << 30, 1);
+        const int epi = geglu ? (conv ? EPI_GEGLU_ONLY128 : EPI_GEGLU) : ((f32 || lnf == 2) ? EPI_PLAIN_ONLY128 : EPI_PLAIN);
+        TilePlan plan;
+        if (force >= 0 && !(geglu && (force == 1 || force == 3))) {
+            VCX_REQUIRE(force <= 6, "vcx_gemm_f16: unknown tile configuration %d (knob GEMM_CFG)", force);
+            plan = forced_plan(d->M, d->N, force, geglu, ncu);
+        } else if (force >= 0) {      // (a forced 160-column configuration has no GEGLU epilogue: the rule of rounds 1-6, as before)
+            int cfg = 0;
+            if ((d->N % 256 == 0 || d->N >= 1024) && (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) >= 384) cfg = 2;
+            plan = forced_plan(d->M, d->N, cfg, geglu, ncu);
+        } else {
+            plan = plan_tiles(d->M, d->N, d->K, epi, ncu);
         }
-        if (force >= 0 && !(geglu && (force == 1 || force == 3))) cfg = force;
-        const int tbm = cfg >= 2 ? 256 : 128, tbn = cfg == 0 ? 128 : cfg == 1 ? 160 : cfg == 2 ? 256 : 320;
-        a.tiles_m = (d->M + tbm - 1) / tbm;
-        a.tiles_n = (d->N + tbn - 1) / tbn;
-        auto big = [&](GemmArgs& g, int c) { return launch_dma(g, c, conv, geglu, f32, s); };
-        if (cfg >= 2) {
-            // Large tiles run one block per CU: a partial last round of 256-row tiles costs a full tile time.  When the
-            // remainder is small, finish the full rounds with large tiles and hand the tail rows to the small-tile config.
-            const int slots = persistent_grid(1 << 30, 1);
-            const long long tiles = (long long)a.tiles_m * a.tiles_n;
-            const long long full = tiles / slots, rem = tiles % slots;
-            if (full >= 1 && rem > 0 && rem * 10 < slots * 7) {
-                const int tm1 = (int)(full * slots / a.tiles_n);
-                const int m1 = tm1 * 256;
-                if (m1 > 0 && m1 < d->M) {
-                    GemmArgs b = a;
-                    b.M = m1;
-                    b.tiles_m = tm1;
-                    int rc = big(b, cfg);
-                    if (rc) return rc;
-                    GemmArgs c = a;
-                    const int scfg = (geglu || d->N % 160 != 0) ? 0 : 1;
-                    const int sbn = scfg ? 160 : 128;
-                    c.m_begin = m1;
-                    c.tiles_m = (d->M - m1 + 127) / 128;
-                    c.tiles_n = (d->N + sbn - 1) / sbn;
-                    return launch_dma(c, scfg, conv, geglu, f32, s);
-                }
-            }
+        const bool trace = getenv("VCX_GEMM_PLAN_TRACE") != nullptr;      // read per call: tools/gemm_cfg_scan.py and the tests switch it on around single calls
+        for (int i = 0; i < plan.n; ++i) {
+            const TileSeg& g = plan.seg[i];
+            const TileCost& t = TILE_COST[g.cfg];
+            if (trace) fprintf(stderr, "[vcx] gemm plan M=%d N=%d K=%d seg %d/%d: cfg %d rows %d+%d grid %d\n", d->M, d->N, d->K, i + 1, plan.n, g.cfg, g.m_begin, g.rows, g.grid);
+            GemmArgs c = a;
+            c.m_begin = g.m_begin;
+            c.M = i + 1 < plan.n ? g.m_begin + g.rows : d->M;      // rows >= M are dropped: the first segment ends where the second begins
+            c.tiles_m = (g.rows + t.tbm - 1) / t.tbm;
+            c.tiles_n = (d->N + t.tbn - 1) / t.tbn;
+            const int rc = launch_dma(c, g.cfg, conv, geglu, f32, s, g.grid);      // the grid the plan priced (and the trace prints) is the grid that runs
+            if (rc) return rc;
         }
-        return cfg >= 2 ? big(a, cfg) : launch_dma(a, cfg, conv, geglu, f32, s);
+        return VCX_OK;
     }
     VCX_REQUIRE(!(flags & VCX_GEMM_COLSTATS), "vcx_gemm_f16: COLSTATS needs the DMA kernel (K / cin %% 64 == 0, extents < 4 GiB); K=%d cin=%d", d->K, d->cin);
     VCX_REQUIRE(!lnf, "vcx_gemm_f16: LNFOLD needs the DMA kernel (K %% 64 == 0, N %% 8 == 0, extents < 4 GiB); K=%d N=%d", d->K, d->N);

@@ -113,7 +113,7 @@ __device__ __forceinline__ void tile_coords(int t, int ntiles, int tiles_n, int&
 }
 
 int persistent_grid(int ntiles, int blocks_per_cu = 2);
-int launch_dma(GemmArgs& a, int cfg, bool conv, bool geglu, bool f32, hipStream_t s);      // (a.k2 + a.k3 > 0: the K-tail instantiations)
+int launch_dma(GemmArgs& a, int cfg, bool conv, bool geglu, bool f32, hipStream_t s, int grid = 0);      // (a.k2 + a.k3 > 0: the K-tail instantiations; grid 0 = persistent_grid of the tiles)
 int launch_ws320_geglu(GemmArgs& a, hipStream_t s);  // ... GEGLU projection, K = 320, N % 256 == 0
 int launch_ws320_lnfold(GemmArgs& a, hipStream_t s); // ... LayerNorm-folded projection (VCX_GEMM_LNFOLD), K = 320, N % 64 == 0
 int launch_ws320_units(GemmArgs& a, hipStream_t s);  // ... with one weight / bias set per unit of rows (vcx_gemm_units_f16)

@@ -26,6 +26,9 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // Tile configuration: block tile TBM x TBN, NWM x NWN waves, each wave owns (TBM/NWM) x (TBN/NWN) outputs.
 //   small : 128 x {128,160}, 2x2 waves (64 x {64,80} per wave), 2 blocks/CU      - few tiles / small M
+//   tail  : 64 x {128,64}, 1x4 waves (64 x {32,16} per wave), and 64 x 128 on 2x2 waves (32 x 64 per wave: GEGLU), 2 blocks/CU
+//           - the rows left over by the last whole round of large tiles (see dispatch_tail below and plan_tiles in gemm.hip): a
+//           wave's K-step is 16 / 8 MFMAs instead of 40, so a tail that cannot fill the chip at least ends sooner
 //   large : 256 x {256,320}, 4x2 waves (64 x {128,160} per wave), 1 block/CU      - LDS bytes per MFMA drop from ~690 to
 //           ~450 (DMA writes 230 -> 115-128, fragment reads 461 -> 333-384): the small tile is LDS-bandwidth bound
 //           (profiles/r01_gemm_experiments.md: removing the DMA gives +25 %, removing barriers or DMA waits nothing).
@@ -318,47 +321,96 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
 }
 
 template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false>
-int launch(const GemmArgs& a, hipStream_t s) {
+int launch(const GemmArgs& a, hipStream_t s, int grid) {
     static VcxLdsAttr lds;
     auto kern = gemm_dma_kernel<Cfg, CONV, GEGLU, OUT_F32, LNF, TAIL>;
     constexpr size_t smem = LNF ? Cfg::SMEM_LNF : Cfg::SMEM;
     if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)smem, "vcx_gemm_f16(dma)")) return VCX_ELAUNCH;
     const int blocks_per_cu = Cfg::SMEM > 80 * 1024 ? 1 : 2;
-    const int nb = persistent_grid(a.tiles_m * a.tiles_n, blocks_per_cu);
+    const int nb = grid > 0 ? grid : persistent_grid(a.tiles_m * a.tiles_n, blocks_per_cu);      // the tile plan's grid (gemm.hip), the one it priced
     hipLaunchKernelGGL(kern, dim3(nb), dim3(Cfg::THREADS), smem, s, a, a.a_bytes, a.w_bytes);
     return vcx_check_launch("vcx_gemm_f16(dma)");
 }
 
 template <class Cfg>
-int dispatch(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_t s) {
+int dispatch(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_t s, int grid) {
     if (a.k2 + a.k3 > 0)       // K tail: convolutions with fp16 output, plain or column-moment epilogue (checked by vcx_gemm_f16)
-        return (a.flags & VCX_GEMM_COLSTATS) ? launch<Cfg, true, false, false, 3, true>(a, s) : launch<Cfg, true, false, false, 0, true>(a, s);
+        return (a.flags & VCX_GEMM_COLSTATS) ? launch<Cfg, true, false, false, 3, true>(a, s, grid) : launch<Cfg, true, false, false, 0, true>(a, s, grid);
     if (a.flags & (VCX_GEMM_LNFOLD | VCX_GEMM_LNFOLD_T)) {      // linear, fp16 output (checked by vcx_gemm_f16)
-        if (a.flags & VCX_GEMM_LNFOLD_T) return launch<Cfg, false, false, false, 2>(a, s);
-        if (!geglu) return launch<Cfg, false, false, false, 1>(a, s);
-        if constexpr (Cfg::NF % 4 == 0) return launch<Cfg, false, true, false, 1>(a, s);
+        if (a.flags & VCX_GEMM_LNFOLD_T) return launch<Cfg, false, false, false, 2>(a, s, grid);
+        if (!geglu) return launch<Cfg, false, false, false, 1>(a, s, grid);
+        if constexpr (Cfg::NF % 4 == 0) return launch<Cfg, false, true, false, 1>(a, s, grid);
         vcx_set_error("vcx_gemm_f16(dma): GEGLU needs whole 64-column packed blocks per wave");
         return VCX_EINVAL;
     }
     if (a.flags & VCX_GEMM_COLSTATS)      // fp16 output, no GEGLU / LNFOLD (checked by vcx_gemm_f16)
-        return conv ? launch<Cfg, true, false, false, 3>(a, s) : launch<Cfg, false, false, false, 3>(a, s);
+        return conv ? launch<Cfg, true, false, false, 3>(a, s, grid) : launch<Cfg, false, false, false, 3>(a, s, grid);
     if (geglu) {
-        if constexpr (Cfg::NF % 4 == 0) return conv ? launch<Cfg, true, true, false>(a, s) : launch<Cfg, false, true, false>(a, s);
+        if constexpr (Cfg::NF % 4 == 0) return conv ? launch<Cfg, true, true, false>(a, s, grid) : launch<Cfg, false, true, false>(a, s, grid);
         vcx_set_error("vcx_gemm_f16(dma): GEGLU needs whole 64-column packed blocks per wave");
         return VCX_EINVAL;
     }
-    if (f32) return conv ? launch<Cfg, true, false, true>(a, s) : launch<Cfg, false, false, true>(a, s);
-    return conv ? launch<Cfg, true, false, false>(a, s) : launch<Cfg, false, false, false>(a, s);
+    if (f32) return conv ? launch<Cfg, true, false, true>(a, s, grid) : launch<Cfg, false, false, true>(a, s, grid);
+    return conv ? launch<Cfg, true, false, false>(a, s, grid) : launch<Cfg, false, false, false>(a, s, grid);
+}
+
+// Tail configurations (indices >= 4): 64-row tiles for the rows that the last whole round of large tiles leaves over (gemm.hip
+// plan_tiles).  Only the epilogues that reach a tail in production are instantiated: plain / residual, COLSTATS, K tail, LNFOLD and
+// GEGLU.  COLSTATS writes one moment strip per 64 rows of a WAVE, so it exists where a wave owns 64 rows (MF == 4).
+// The launch asks for at least TAIL_LDS bytes of LDS: at most two blocks then share a CU, as with the 128-row tiles - the
+// occupancy that the grid (persistent_grid, two blocks per CU) and the plan's cost table are written for.
+constexpr size_t TAIL_LDS = 54 * 1024;
+constexpr size_t CU_LDS = 160 * 1024;      // LDS of a gfx950 CU: two 54 KiB blocks fit, a third does not
+static_assert(2 * TAIL_LDS <= CU_LDS && 3 * TAIL_LDS > CU_LDS, "TAIL_LDS must cap the tail kernels at two blocks per CU");
+
+template <class Cfg, bool CONV, bool GEGLU, int LNF = 0, bool TAIL = false>
+int launch_tail(const GemmArgs& a, hipStream_t s, int grid) {
+    static VcxLdsAttr lds;
+    auto kern = gemm_dma_kernel<Cfg, CONV, GEGLU, false, LNF, TAIL>;
+    constexpr size_t need = LNF ? Cfg::SMEM_LNF : Cfg::SMEM;
+    constexpr size_t smem = need > TAIL_LDS ? need : TAIL_LDS;
+    if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)smem, "vcx_gemm_f16(dma tail)")) return VCX_ELAUNCH;
+    const int nb = grid > 0 ? grid : persistent_grid(a.tiles_m * a.tiles_n, 2);
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(Cfg::THREADS), smem, s, a, a.a_bytes, a.w_bytes);
+    return vcx_check_launch("vcx_gemm_f16(dma tail)");
+}
+
+template <class Cfg>
+int dispatch_tail(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_t s, int grid) {
+    const bool cs = a.flags & VCX_GEMM_COLSTATS;
+    if (f32 || (a.flags & VCX_GEMM_LNFOLD_T)) {
+        vcx_set_error("vcx_gemm_f16(dma): the 64-row tile configurations have no fp32-output / LNFOLD_T epilogue");
+        return VCX_EINVAL;
+    }
+    if constexpr (Cfg::NF % 4 == 0) {       // the GEGLU configuration
+        if (geglu && !conv && a.k2 + a.k3 == 0 && !cs)
+            return (a.flags & VCX_GEMM_LNFOLD) ? launch_tail<Cfg, false, true, 1>(a, s, grid) : launch_tail<Cfg, false, true>(a, s, grid);
+        vcx_set_error("vcx_gemm_f16(dma): this 64-row tile configuration is for GEGLU projections (linear) only");
+        return VCX_EINVAL;
+    } else {
+        static_assert(Cfg::MF == 4, "COLSTATS: one moment strip per 64 rows of a wave");
+        if (geglu) {
+            vcx_set_error("vcx_gemm_f16(dma): GEGLU needs whole 64-column packed blocks per wave");
+            return VCX_EINVAL;
+        }
+        if (a.k2 + a.k3 > 0) return cs ? launch_tail<Cfg, true, false, 3, true>(a, s, grid) : launch_tail<Cfg, true, false, 0, true>(a, s, grid);
+        if (a.flags & VCX_GEMM_LNFOLD) return launch_tail<Cfg, false, false, 1>(a, s, grid);
+        if (cs) return conv ? launch_tail<Cfg, true, false, 3>(a, s, grid) : launch_tail<Cfg, false, false, 3>(a, s, grid);
+        return conv ? launch_tail<Cfg, true, false>(a, s, grid) : launch_tail<Cfg, false, false>(a, s, grid);
+    }
 }
 
 }  // namespace
 
-int vcxgemm::launch_dma(GemmArgs& a, int cfg, bool conv, bool geglu, bool f32, hipStream_t s) {
+int vcxgemm::launch_dma(GemmArgs& a, int cfg, bool conv, bool geglu, bool f32, hipStream_t s, int grid) {
     switch (cfg) {
-        case 0: return dispatch<TileCfg<128, 128, 2, 2>>(a, conv, geglu, f32, s);
-        case 1: return dispatch<TileCfg<128, 160, 2, 2>>(a, conv, geglu, f32, s);
-        case 2: return dispatch<TileCfg<256, 256, 4, 2>>(a, conv, geglu, f32, s);
-        case 3: return dispatch<TileCfg<256, 320, 4, 2>>(a, conv, geglu, f32, s);
+        case 0: return dispatch<TileCfg<128, 128, 2, 2>>(a, conv, geglu, f32, s, grid);
+        case 1: return dispatch<TileCfg<128, 160, 2, 2>>(a, conv, geglu, f32, s, grid);
+        case 2: return dispatch<TileCfg<256, 256, 4, 2>>(a, conv, geglu, f32, s, grid);
+        case 3: return dispatch<TileCfg<256, 320, 4, 2>>(a, conv, geglu, f32, s, grid);
+        case 4: return dispatch_tail<TileCfg<64, 128, 1, 4>>(a, conv, geglu, f32, s, grid);      // 64 x 32 per wave
+        case 5: return dispatch_tail<TileCfg<64, 64, 1, 4>>(a, conv, geglu, f32, s, grid);       // 64 x 16 per wave
+        case 6: return dispatch_tail<TileCfg<64, 128, 2, 2>>(a, conv, geglu, f32, s, grid);      // 32 x 64 per wave: GEGLU
     }
     vcx_set_error("vcx_gemm_f16(dma): unknown tile configuration %d", cfg);
     return VCX_EINVAL;

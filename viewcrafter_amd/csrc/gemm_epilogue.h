@@ -89,7 +89,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f4 (&acc)[Cfg::
         const unsigned odd = lg & 1, half = lg >> 1;
 #pragma unroll
         for (int b = 0; b < MFRAG; ++b) {
-            u2v packed[NOUT];
+            u2v packed[NOUT ? NOUT : 1];      // (NF = 1 never takes this branch, but it is compiled)
             [[maybe_unused]] float rb = 0.f, qb = 0.f;
             if (LNF) {
                 rb = p.alpha * ln_r1[b];
