@@ -151,9 +151,18 @@ int vcx_gemm_f16(const vcx_gemm_desc* desc_host, void* stream);
 /* The same linear layer with ONE weight / bias set per `unit_rows` consecutive rows: rows [u unit_rows, (u + 1) unit_rows) use
  * W + u w_unit_stride and bias + u bias_unit_stride (element strides) - the (Wn, bn) sets of vcx_groupnorm_fold_linear_f16, one per
  * frame (SpatialTransformer.norm -> proj_in, attention.py:265-269,299) or per video (TemporalTransformer, attention.py:331-336,369-372).
- * Linear mode, VCX_GEMM_BIAS_N at most, M a whole number of units.  N = K = 320 with unit_rows % 32 == 0, >= 1024 and M >= 8192 runs as
- * ONE launch of the weight-stationary kernel (a block keeps its unit's weights in registers); every other shape unit by unit through
- * vcx_gemm_f16.  VCX_GEMM_ROWSTATS: in the one-launch form, or with one unit (vcx_gemm_f16's weight-stationary kernel, the same bits). */
+ * Linear mode, VCX_GEMM_BIAS_N at most, M a whole number of units.  Routes, the first that applies:
+ *  - N = K = 320 with unit_rows % 32 == 0, >= 1024 and M >= 8192: ONE launch of the weight-stationary kernel (a block keeps its unit's
+ *    weights in registers);
+ *  - more than one unit, K % 64 == 0, N % 8 == 0, A and C of the whole call addressable with 32-bit byte offsets (below 0xFFFF0000, the
+ *    output up to 256 rows past its end), at most 65535 units, knob GEMM_DMA on: the tiled engine's per-unit form - ONE tile plan over
+ *    units x ceil(unit_rows / tile rows) row tiles (no tile straddles two units), at most two launches.  Not where vcx_gemm_f16 would run
+ *    each unit on its weight-stationary kernel (K = 320, N = 320 j <= 1280, unit_rows >= 8192), nor under a forced GEMM_CFG 6;
+ *  - every other shape unit by unit through vcx_gemm_f16.  VCX_GEMM_UNITS_LOOP=1 in the environment (read per call) sends the second
+ *    route here too (tests, A/B runs).
+ * The second and third route give the same bits.  A forced GEMM_CFG forces the per-unit form's tile configuration too; under
+ * VCX_GEMM_PLAN_TRACE it prints its segments with ` units <U> unit_rows <R>` appended (U = the units of the segment).
+ * VCX_GEMM_ROWSTATS: in the weight-stationary one-launch form, or with one unit (vcx_gemm_f16's weight-stationary kernel, the same bits). */
 int vcx_gemm_units_f16(const vcx_gemm_desc* desc_host, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------

@@ -409,14 +409,20 @@ static const TileCost TILE_COST[7] = {
 };
 constexpr float LAUNCH_COST = 4.0f;      // microseconds a launch costs beyond its tiles (2.7 ... 6.2 over the configurations)
 
-static TileSeg plan_seg(int cfg, int m_begin, int rows, int N, int ncu) {
+// tiles of `rows` rows under configuration cfg.  unit_rows > 0 (vcx_gemm_units_f16, rows a whole number of units): row tiles are
+// counted per unit - no tile straddles two units, so a ragged unit costs a whole tile
+static int seg_tiles(int cfg, int rows, int N, int unit_rows) {
     const TileCost& t = TILE_COST[cfg];
-    const int tiles = ((rows + t.tbm - 1) / t.tbm) * ((N + t.tbn - 1) / t.tbn);
-    return TileSeg{cfg, m_begin, rows, grid_for(tiles, t.bpc, ncu)};
+    const int tiles_n = (N + t.tbn - 1) / t.tbn;
+    if (unit_rows > 0) return (rows / unit_rows) * ((unit_rows + t.tbm - 1) / t.tbm) * tiles_n;
+    return ((rows + t.tbm - 1) / t.tbm) * tiles_n;
 }
-static float seg_cost(const TileSeg& g, int N, int K, int ncu) {
+static TileSeg plan_seg(int cfg, int m_begin, int rows, int N, int ncu, int unit_rows = 0) {
+    return TileSeg{cfg, m_begin, rows, grid_for(seg_tiles(cfg, rows, N, unit_rows), TILE_COST[cfg].bpc, ncu)};
+}
+static float seg_cost(const TileSeg& g, int N, int K, int ncu, int unit_rows = 0) {
     const TileCost& t = TILE_COST[g.cfg];
-    const int tiles = ((g.rows + t.tbm - 1) / t.tbm) * ((N + t.tbn - 1) / t.tbn);
+    const int tiles = seg_tiles(g.cfg, g.rows, N, unit_rows);
     const int per_block = (tiles + g.grid - 1) / g.grid;      // rounds: the tiles of the longest-running block
     const bool share = g.grid > ncu;
     return LAUNCH_COST + per_block * ((float)(K / BK) * (share ? t.k_share : t.k_alone) + t.e);
@@ -425,32 +431,35 @@ static float seg_cost(const TileSeg& g, int N, int K, int ncu) {
 // A pure function of its arguments.  Candidates: the whole problem on small tiles; where large tiles apply (N and the tile count, as
 // before: from 1.5 rounds on), the whole problem on them, and `full` or `full - 1` whole rounds of them followed by the remaining rows
 // in each smaller configuration that has the epilogue.  Cheapest under seg_cost wins; earlier candidates win ties.
-static TilePlan plan_tiles(int M, int N, int K, int epi, int ncu) {
+// unit_rows > 0: the per-unit form (M a whole number of units).  Tiles are units x tiles per unit, and a plan of two launches changes
+// configuration at a unit boundary: the large tiles take the units that whole rounds of them hold.
+static TilePlan plan_tiles(int M, int N, int K, int epi, int ncu, int unit_rows = 0) {
     const bool geglu = epi == EPI_GEGLU || epi == EPI_GEGLU_ONLY128;
     const int small = (!geglu && N % 160 == 0) ? 1 : 0;
     const int big_bn = (N % 320 == 0 && !geglu) ? 320 : ((N % 256 == 0 || N >= 1024) ? 256 : 0);
     TilePlan best;
     auto consider = [&](int n, TileSeg a, TileSeg b, bool first) {
-        const float c = seg_cost(a, N, K, ncu) + (n == 2 ? seg_cost(b, N, K, ncu) : 0.f);
+        const float c = seg_cost(a, N, K, ncu, unit_rows) + (n == 2 ? seg_cost(b, N, K, ncu, unit_rows) : 0.f);
         if (first || c < best.cost) best = TilePlan{n, {a, b}, c};
     };
     const TileSeg none{0, 0, 0, 0};
-    consider(1, plan_seg(small, 0, M, N, ncu), none, true);
+    consider(1, plan_seg(small, 0, M, N, ncu, unit_rows), none, true);
     if (!big_bn) return best;
     const int large = big_bn == 320 ? 3 : 2;
-    const int tiles_m = (M + 255) / 256, tiles_n = (N + big_bn - 1) / big_bn;
+    const int tpu = unit_rows > 0 ? (unit_rows + 255) / 256 : 1, step_rows = unit_rows > 0 ? unit_rows : 256;      // row tiles / rows between two places where a plan may split
+    const int tiles_m = unit_rows > 0 ? M / unit_rows * tpu : (M + 255) / 256, tiles_n = (N + big_bn - 1) / big_bn;
     const long long tiles = (long long)tiles_m * tiles_n;
     if (tiles < 384) return best;
-    consider(1, plan_seg(large, 0, M, N, ncu), none, true);      // (large tiles beat small ones from here on: measured, the rule of rounds 1-6)
+    consider(1, plan_seg(large, 0, M, N, ncu, unit_rows), none, true);      // (large tiles beat small ones from here on: measured, the rule of rounds 1-6)
     int tails[3], ntails = 0;
     tails[ntails++] = small;
     if (epi == EPI_PLAIN) { tails[ntails++] = 4; tails[ntails++] = 5; }
     if (epi == EPI_GEGLU) tails[ntails++] = 6;
     const long long full = tiles / ncu;
     for (long long r = full; r >= 1 && r >= full - 1; --r) {
-        const int m1 = (int)(r * ncu / tiles_n) * 256;
+        const int m1 = (int)(r * ncu / tiles_n / tpu) * step_rows;
         if (m1 <= 0 || m1 >= M) continue;
-        for (int i = 0; i < ntails; ++i) consider(2, plan_seg(large, 0, m1, N, ncu), plan_seg(tails[i], m1, M - m1, N, ncu), false);
+        for (int i = 0; i < ntails; ++i) consider(2, plan_seg(large, 0, m1, N, ncu, unit_rows), plan_seg(tails[i], m1, M - m1, N, ncu, unit_rows), false);
     }
     return best;
 }
@@ -694,10 +703,18 @@ extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
     return use160 ? dispatch<160>(a, conv, geglu, f32, s) : dispatch<128>(a, conv, geglu, f32, s);
 }
 
-// One weight / bias set per unit of rows (include/vcx.h): the weight-stationary kernel in ONE launch where it applies (N = K = 320, the
-// level-0 projections: a block keeps its unit's weights in registers anyway), otherwise unit by unit through vcx_gemm_f16.  ONE unit (a single
-// video, B = 1) goes to vcx_gemm_f16 with ROWSTATS too: the same pipelined weight-stationary kernel and epilogue, so its rows and statistics
-// are the bits of the same video inside a batch (B = 2); that kernel's own grid measured faster than the one-launch form's for one unit.
+// One weight / bias set per unit of rows (include/vcx.h).  Three routes, the first that applies:
+//  1. N = K = 320 (the level-0 projections): ONE launch of the weight-stationary kernel - a block keeps its unit's weights in registers anyway.
+//  2. the tiled engine's per-unit form (gemm_dma.hip, UNITS), ONE plan over units x tiles-per-unit tiles and at most two launches:
+//     units > 1, K % 64 == 0, N % 8 == 0, the 32-bit extents of the whole call (`dma_ok`'s rule, output offsets up to 256 rows past the
+//     end), units <= 65535, knob GEMM_DMA on.  The same bits as route 3 - the tile shape does not enter a row's arithmetic - so the
+//     choice between the two is a matter of cost alone.  Left on route 3: units that vcx_gemm_f16 would give to its weight-stationary
+//     kernel (K = 320, N = 320 ... 1280, unit_rows >= 8192), so that the bits stay those of the loop whatever that kernel does; a forced
+//     GEMM_CFG 6 (the GEGLU configuration); VCX_GEMM_UNITS_LOOP=1 (read per call: tests, A/B runs).
+//  3. unit by unit through vcx_gemm_f16.
+// ONE unit (a single video, B = 1) goes to vcx_gemm_f16 with ROWSTATS too: the same pipelined weight-stationary kernel and epilogue, so its
+// rows and statistics are the bits of the same video inside a batch (B = 2); that kernel's own grid measured faster than the one-launch
+// form's for one unit.
 extern "C" int vcx_gemm_units_f16(const vcx_gemm_desc* d, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, void* stream) {
     VCX_REQUIRE(d != nullptr && d->struct_size == sizeof(vcx_gemm_desc), "vcx_gemm_units_f16: null descriptor or wrong struct_size");
     VCX_REQUIRE(d->A && d->W && d->C && d->M > 0 && d->N > 0 && d->K > 0, "vcx_gemm_units_f16: null A/W/C or empty problem");
@@ -728,6 +745,43 @@ extern "C" int vcx_gemm_units_f16(const vcx_gemm_desc* d, int unit_rows, int64_t
     }
     VCX_REQUIRE(units == 1 || !(d->flags & VCX_GEMM_ROWSTATS), "vcx_gemm_units_f16: ROWSTATS needs the one-launch weight-stationary form (N = K = 320, unit_rows %% 32 == 0, >= 1024, M >= 8192); M=%d N=%d K=%d unit_rows=%d",
                 d->M, d->N, d->K, unit_rows);
+    const int force = vcx_tune(VCX_TUNE_GEMM_CFG);
+    const char* loop_env = getenv("VCX_GEMM_UNITS_LOOP");
+    const unsigned long long w_ext = 2ull * ((unsigned long long)(d->N - 1) * d->ldw + d->K);      // of ONE unit: a tile's descriptor starts at its unit's weights
+    const bool ws_per_unit = d->K == 320 && d->N % 320 == 0 && d->N <= 1280 && unit_rows >= 8192 && vcx_tune(VCX_TUNE_GEMM_WS) != 0 && force < 0;
+    if (units > 1 && units <= 65535 && d->K % 64 == 0 && d->N % 8 == 0 && a_ext < lim && w_ext < lim && 2ull * (unsigned long long)(d->M + 256) * d->ldc < lim &&
+        vcx_tune(VCX_TUNE_GEMM_DMA) != 0 && force <= 5 && !ws_per_unit && !(loop_env && loop_env[0] && loop_env[0] != '0')) {
+        GemmArgs a{};
+        a.A = (const half_t*)d->A; a.W = (const half_t*)d->W; a.C = d->C; a.bias = d->bias;
+        a.lda = d->lda; a.M = d->M; a.N = d->N; a.K = d->K; a.ldw = d->ldw; a.ldc = d->ldc; a.ldr = 0;
+        a.rowadd_div = 1; a.rowadd_ld = d->N; a.flags = d->flags; a.alpha = d->alpha; a.m_begin = 0;
+        a.ldcs = d->N;
+        a.a_bytes = (unsigned)a_ext; a.c_bytes = (unsigned)c_ext; a.w_bytes = (unsigned)w_ext; a.r_bytes = 0;
+        a.unit_rows = unit_rows; a.units = units; a.w_unit_stride = w_unit_stride; a.bias_unit_stride = bias_unit_stride;
+        VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * d->M * (double)d->N * d->K, 2.0 * ((double)d->M * d->K + (double)units * d->N * d->K + (double)d->M * d->N));
+        const int ncu = persistent_grid(1 << 30, 1);
+        TilePlan plan;
+        if (force >= 0) plan = TilePlan{1, {plan_seg(force, 0, d->M, d->N, ncu, unit_rows), TileSeg{0, 0, 0, 0}}, 0.f};      // a forced configuration: the whole call on it
+        else plan = plan_tiles(d->M, d->N, d->K, EPI_PLAIN, ncu, unit_rows);
+        const bool trace = getenv("VCX_GEMM_PLAN_TRACE") != nullptr;
+        for (int i = 0; i < plan.n; ++i) {
+            const TileSeg& g = plan.seg[i];
+            const TileCost& t = TILE_COST[g.cfg];
+            const int u0 = g.m_begin / unit_rows, nu = g.rows / unit_rows;      // segments begin and end at unit boundaries
+            if (trace) fprintf(stderr, "[vcx] gemm plan M=%d N=%d K=%d seg %d/%d: cfg %d rows %d+%d grid %d units %d unit_rows %d\n", d->M, d->N, d->K, i + 1, plan.n, g.cfg, g.m_begin, g.rows, g.grid, nu, unit_rows);
+            GemmArgs c = a;
+            c.m_begin = g.m_begin;
+            c.M = g.m_begin + g.rows;
+            c.units = nu;
+            c.W = a.W + (int64_t)u0 * w_unit_stride;
+            if (a.bias) c.bias = a.bias + (int64_t)u0 * bias_unit_stride;
+            c.tiles_m = nu * ((unit_rows + t.tbm - 1) / t.tbm);
+            c.tiles_n = (d->N + t.tbn - 1) / t.tbn;
+            const int rc = launch_dma(c, g.cfg, false, false, false, s, g.grid);
+            if (rc) return rc;
+        }
+        return VCX_OK;
+    }
     for (int u = 0; u < units; ++u) {
         vcx_gemm_desc du = *d;
         du.A = (const half_t*)d->A + (int64_t)u * unit_rows * d->lda;

@@ -54,7 +54,13 @@ struct TileCfg {
 // TAIL (round 6, convolutions only): the last (p.k2 + p.k3) / 64 K-steps of a tile read, for output row m, row m of p.A2 and then of p.A3
 // - linear sources - instead of an input pixel: the 1x1 skip convolution of a ResBlock rides in the K loop of its second 3x3
 // convolution (include/vcx.h tail_a0 / tail_a1).  Own instantiations: the kernels without a tail keep their listing.
-template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false>
+// UNITS (round 9, linear mode, fp16 output, bias epilogue only; vcx_gemm_units_f16): one weight / bias set per p.unit_rows consecutive
+// rows.  Row tiles are counted per unit - p.tiles_m = units x ceil(unit_rows / TBM), tile_m = unit x tiles-per-unit + tile inside the
+// unit - so no tile straddles two units and the tiles of a unit are neighbours in the XCD-aware walk (its weight set stays in one L2).
+// A tile's unit moves the base of the W descriptor (scalar arithmetic in init_load, ahead of the tile's first DMA) and of the bias, and
+// bounds the output descriptor at the unit's end: the ragged last tile of a unit READS rows of the next unit and stores none of them.
+// Own instantiations, like TAIL.
+template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false, bool UNITS = false>
 __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, unsigned a_bytes, unsigned w_bytes) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (the body uses device-only types)
     constexpr int TBM = Cfg::TBM, BN = Cfg::TBN;
@@ -70,6 +76,13 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t srd_a3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(TAIL && p.A3 ? p.A3 : p.A), 0, TAIL ? (int)p.a3_bytes : 0, 0x00020000);
     [[maybe_unused]] const int nk_main = (p.K - (TAIL ? p.k2 + p.k3 : 0)) / BK, nk_a2 = TAIL ? p.k2 / BK : 0;      // K-steps of the gather / of the first linear source
     [[maybe_unused]] int lrow0 = 0;                            // first output row of the tile being loaded
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t srd_wu = srd_w;   // UNITS: the weight set of the tile being loaded
+    [[maybe_unused]] const int tpu = UNITS ? (p.unit_rows + TBM - 1) / TBM : 1;      // UNITS: row tiles per unit
+    // UNITS: unit (relative to this launch's first one) and first row of row tile tm
+    [[maybe_unused]] auto unit_of = [&](int tm, int& u, int& row0) {
+        u = tm / tpu;
+        row0 = p.m_begin + u * p.unit_rows + (tm - u * tpu) * TBM;
+    };
 
     const int ntiles = p.tiles_m * p.tiles_n;
     const int G = gridDim.x;
@@ -90,10 +103,15 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
         int tile_m, tile_n;
         tile_coords(t, ntiles, p.tiles_n, tile_m, tile_n);
         if (TAIL) lrow0 = p.m_begin + tile_m * TBM;
+        if (UNITS) {
+            int lu;
+            unit_of(tile_m, lu, lrow0);
+            srd_wu = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.W + (int64_t)lu * p.w_unit_stride), 0, (int)w_bytes, 0x00020000);
+        }
 #pragma unroll
         for (int i = 0; i < XROWS; ++i) {
             const int r = r0 + RSTEP * i;
-            const int m = p.m_begin + tile_m * TBM + r;
+            const int m = UNITS ? lrow0 + r : p.m_begin + tile_m * TBM + r;
             const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;   // source chunk that lands at position `chunk`
             if (CONV) {
                 const int hw = p.out_h * p.out_w;
@@ -201,7 +219,7 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
             const unsigned soffw = (unsigned)kt * (BK * 2);
 #pragma unroll
             for (int i = 0; i < WROWS; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_w, (lds_ptr_t)(dw + RSTEP * i * BK), 16, woff[i], soffw, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(UNITS ? srd_wu : srd_w, (lds_ptr_t)(dw + RSTEP * i * BK), 16, woff[i], soffw, 0, 0);
         }
     };
 
@@ -297,6 +315,18 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
         }
         if (ckt == nk - 1) {
             float* sB = reinterpret_cast<float*>(smem_raw + Cfg::STAGES) + wave * WN;   // the wave's private strip of column addends
+            if constexpr (UNITS) {
+                // the tile as a one-tile problem of its unit: rows from the tile's first one, the unit's bias, the output bounded at the
+                // unit's last row (rows beyond it fall outside the descriptor, as rows >= M do for a plain launch)
+                int cu, crow0;
+                unit_of(tile_m, cu, crow0);
+                GemmArgs q = p;
+                q.m_begin = crow0;
+                q.M = p.m_begin + (cu + 1) * p.unit_rows;
+                q.bias = p.bias + (int64_t)cu * p.bias_unit_stride;
+                q.c_bytes = (unsigned)(2ull * ((unsigned long long)(q.M - 1) * (unsigned)p.ldc + (unsigned)p.N));
+                gemm_epilogue<Cfg, false, false, 0>(q, acc, 0, tile_n, wm, wn, lane, sB);
+            } else
             gemm_epilogue<Cfg, GEGLU, OUT_F32, LNF>(p, acc, tile_m, tile_n, wm, wn, lane, sB,
                                                     reinterpret_cast<float*>(smem_raw + Cfg::STAGES + Cfg::STRIP) + wave * WN, ln_r0, ln_r1);
 #pragma unroll
@@ -320,10 +350,10 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
 #endif
 }
 
-template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false>
+template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false, bool UNITS = false>
 int launch(const GemmArgs& a, hipStream_t s, int grid) {
     static VcxLdsAttr lds;
-    auto kern = gemm_dma_kernel<Cfg, CONV, GEGLU, OUT_F32, LNF, TAIL>;
+    auto kern = gemm_dma_kernel<Cfg, CONV, GEGLU, OUT_F32, LNF, TAIL, UNITS>;
     constexpr size_t smem = LNF ? Cfg::SMEM_LNF : Cfg::SMEM;
     if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)smem, "vcx_gemm_f16(dma)")) return VCX_ELAUNCH;
     const int blocks_per_cu = Cfg::SMEM > 80 * 1024 ? 1 : 2;
@@ -334,6 +364,8 @@ int launch(const GemmArgs& a, hipStream_t s, int grid) {
 
 template <class Cfg>
 int dispatch(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_t s, int grid) {
+    if (a.unit_rows > 0)       // one weight / bias set per unit of rows: linear, fp16 output, BIAS_N at most (checked by vcx_gemm_units_f16)
+        return launch<Cfg, false, false, false, 0, false, true>(a, s, grid);
     if (a.k2 + a.k3 > 0)       // K tail: convolutions with fp16 output, plain or column-moment epilogue (checked by vcx_gemm_f16)
         return (a.flags & VCX_GEMM_COLSTATS) ? launch<Cfg, true, false, false, 3, true>(a, s, grid) : launch<Cfg, true, false, false, 0, true>(a, s, grid);
     if (a.flags & (VCX_GEMM_LNFOLD | VCX_GEMM_LNFOLD_T)) {      // linear, fp16 output (checked by vcx_gemm_f16)
@@ -363,10 +395,10 @@ constexpr size_t TAIL_LDS = 54 * 1024;
 constexpr size_t CU_LDS = 160 * 1024;      // LDS of a gfx950 CU: two 54 KiB blocks fit, a third does not
 static_assert(2 * TAIL_LDS <= CU_LDS && 3 * TAIL_LDS > CU_LDS, "TAIL_LDS must cap the tail kernels at two blocks per CU");
 
-template <class Cfg, bool CONV, bool GEGLU, int LNF = 0, bool TAIL = false>
+template <class Cfg, bool CONV, bool GEGLU, int LNF = 0, bool TAIL = false, bool UNITS = false>
 int launch_tail(const GemmArgs& a, hipStream_t s, int grid) {
     static VcxLdsAttr lds;
-    auto kern = gemm_dma_kernel<Cfg, CONV, GEGLU, false, LNF, TAIL>;
+    auto kern = gemm_dma_kernel<Cfg, CONV, GEGLU, false, LNF, TAIL, UNITS>;
     constexpr size_t need = LNF ? Cfg::SMEM_LNF : Cfg::SMEM;
     constexpr size_t smem = need > TAIL_LDS ? need : TAIL_LDS;
     if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)smem, "vcx_gemm_f16(dma tail)")) return VCX_ELAUNCH;
@@ -383,6 +415,10 @@ int dispatch_tail(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_
         return VCX_EINVAL;
     }
     if constexpr (Cfg::NF % 4 == 0) {       // the GEGLU configuration
+        if (a.unit_rows > 0) {
+            vcx_set_error("vcx_gemm_f16(dma): this 64-row tile configuration has no per-unit weight form");
+            return VCX_EINVAL;
+        }
         if (geglu && !conv && a.k2 + a.k3 == 0 && !cs)
             return (a.flags & VCX_GEMM_LNFOLD) ? launch_tail<Cfg, false, true, 1>(a, s, grid) : launch_tail<Cfg, false, true>(a, s, grid);
         vcx_set_error("vcx_gemm_f16(dma): this 64-row tile configuration is for GEGLU projections (linear) only");
@@ -393,6 +429,7 @@ int dispatch_tail(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_
             vcx_set_error("vcx_gemm_f16(dma): GEGLU needs whole 64-column packed blocks per wave");
             return VCX_EINVAL;
         }
+        if (a.unit_rows > 0) return launch_tail<Cfg, false, false, 0, false, true>(a, s, grid);
         if (a.k2 + a.k3 > 0) return cs ? launch_tail<Cfg, true, false, 3, true>(a, s, grid) : launch_tail<Cfg, true, false, 0, true>(a, s, grid);
         if (a.flags & VCX_GEMM_LNFOLD) return launch_tail<Cfg, false, false, 1>(a, s, grid);
         if (cs) return conv ? launch_tail<Cfg, true, false, 3>(a, s, grid) : launch_tail<Cfg, false, false, 3>(a, s, grid);

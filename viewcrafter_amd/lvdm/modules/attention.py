@@ -46,20 +46,29 @@ FOLD_LAYERNORM_FF_MIN_DIM = int(os.environ.get("VCX_LN_FOLD_FF_MIN_DIM", "640"))
 # TemporalTransformer.norm -> proj_in (reference attention.py:331-336,369-372) and SpatialTransformer.norm -> proj_in (:265-269,299):
 # a GroupNorm without SiLU in front of a linear layer is an affine map per (statistics unit, channel), so it runs as per-unit scaled
 # weights and bias of the projection (vcx_groupnorm_fold_linear_f16 + vcx_gemm_units_f16 on the UN-normalised rows) and the normalised
-# copy of the tensor is neither written nor re-read.  Temporal norms (unit = video): wherever a video's tensor is at least
-# GN_FOLD_MIN_BYTES (below that the apply pass is cheaper than a launch per video).  Spatial norms (unit = frame, 50 of them): only
-# where all frames go through ONE launch - the weight-stationary kernel at C = 320, level 0 of the UNet, whose blocks keep a weight
-# set in registers anyway.  VCX_GN_FOLD=0: the separate apply pass everywhere (A/B runs, tools/step_ab.py).
+# copy of the tensor is neither written nor re-read.  All units of a call run under ONE tile plan wherever ops.units_one_launch_ok holds: the
+# weight-stationary kernel at C = 320, the tiled engine's per-unit form at the other widths (at most two launches, tiles counted per unit;
+# the same bits as the unit-by-unit loop it replaced).  Temporal norms (unit = video): wherever a video's tensor is at least
+# GN_FOLD_MIN_BYTES - a per-video size floor from the time when every video was a launch of its own, kept so that the default host graph
+# and its rounding stay what they were.  Spatial norms (unit = frame, 50 of them): by default only at C = 320, level 0 of the UNet (the
+# weight-stationary kernel, whose blocks keep a weight set in registers anyway).  VCX_GN_FOLD_SPATIAL=2 (opt-in) folds them at every width
+# where the frames of a video go through the per-unit form; the fold agrees with norm-then-linear to fp16 rounding, not bit for bit,
+# which is why the default stays.  VCX_GN_FOLD=0: the separate apply pass everywhere (A/B runs, tools/step_ab.py).
 GN_FOLD = os.environ.get("VCX_GN_FOLD", "1") != "0"
 GN_FOLD_MIN_BYTES = int(os.environ.get("VCX_GN_FOLD_MIN_BYTES", str(16 << 20)))
-GN_FOLD_SPATIAL = os.environ.get("VCX_GN_FOLD_SPATIAL", "1") != "0"
+GN_FOLD_SPATIAL = {"0": 0, "2": 2}.get(os.environ.get("VCX_GN_FOLD_SPATIAL", "1"), 1)      # 0: never, 1: C = 320 only, 2: every width with a one-plan route
 
 
 def spatial_fold_ok(n, pixels, C, D):
     """Does vcx_gemm_units_f16 take the frames of a video, n frames of `pixels` rows, in ONE weight-stationary launch (csrc/gemm.hip)?
     Decided per VIDEO (n = frames per video, not frames per call): a frame's bits must not depend on how many videos share the call
     (B = 2 against two B = 1, the shared CFG prefix against the replicated batch), so the size thresholds look at one video and the
-    kernel's own M >= 8192 follows from them for every batch.  The caller checks the 4 GiB extents of the whole call (fold_extent_ok)."""
+    kernel's own M >= 8192 follows from them for every batch.  The caller checks the 4 GiB extents of the whole call (fold_extent_ok).
+    GN_FOLD_SPATIAL == 2 (opt-in): also where the tiled engine's per-unit form takes the frames of a video (ops.units_route "grouped");
+    that form and the unit-by-unit loop give the same bits, so there too a frame does not depend on the batch."""
+    if (GN_FOLD and GN_FOLD_SPATIAL == 2 and n > 1 and pixels % 8 == 0 and 2 * n * pixels * C >= GN_FOLD_MIN_BYTES and fold_extent_ok(n * pixels, max(C, D))
+            and ops.units_route(n * pixels, D, C, pixels) == "grouped"):
+        return True
     return (GN_FOLD and GN_FOLD_SPATIAL and C == 320 and D == 320 and pixels % 32 == 0 and pixels >= 1024 and n * pixels >= 8192
             and 2 * n * pixels * C >= GN_FOLD_MIN_BYTES and fold_extent_ok(n * pixels, C) and ops.tune_get("GEMM_DMA") != 0
             and ops.tune_get("GEMM_WS") != 0 and ops.tune_get("GEMM_CFG") < 0)      # (a forced tile configuration means the tiled engine: ADVICE r5)
@@ -406,7 +415,7 @@ class SpatialTransformer(PackedModule):
         # colstats: column moments of x from the convolution that produced it (ResBlock): the norm then needs no statistics pass
         stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, N_img, C)
         D_in = pk["win"].shape[0]
-        fold = N_img % 8 == 0 and spatial_fold_ok(frames_per_video, N_img, C, D_in) and fold_extent_ok(n * N_img, C)     # the norm as per-frame weights / bias of proj_in
+        fold = N_img % 8 == 0 and spatial_fold_ok(frames_per_video, N_img, C, D_in) and fold_extent_ok(n * N_img, max(C, D_in))     # the norm as per-frame weights / bias of proj_in
         a = None if fold else ops.group_norm(x.view(n, N_img, C), pk["gn_w"], pk["gn_b"], self.norm.eps, False, stats=stats)
         # The attention kernels address a frame's keys / values at 16-byte granularity: h*w must be a multiple of 8.  It is at every
         # level of 576x1024 and 320x512; for other --height / --width (e.g. 384x640: 6x10 = 60 tokens at the deepest level) each

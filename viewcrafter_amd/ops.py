@@ -165,8 +165,10 @@ def rowstats_buffer(M, device):
 
 def gemm_units(a, wn, bn, *, unit_rows, out=None, rowstats=None, rowstats_eps=1e-5):
     """out[M, N] = a[M, K] Wn[u]^T + bn[u] for the rows of unit u = m // unit_rows: wn [units, N, K] fp16, bn [units, N] fp32 (the
-    sets of group_norm_fold_linear).  One launch of the weight-stationary kernel where it applies, else unit by unit (include/vcx.h).
-    `rowstats`: as in gemm (the one-launch form, or a single unit; see rowstats_ok)."""
+    sets of group_norm_fold_linear).  One launch of the weight-stationary kernel at N = K = 320, one plan of the tiled engine (at most two
+    launches, tiles counted per unit) wherever its DMA kernel takes the shape, else unit by unit - units_route below, include/vcx.h.
+    The tiled form and the unit-by-unit loop give the same bits.  `rowstats`: as in gemm (the weight-stationary one-launch form, or a
+    single unit; see rowstats_ok)."""
     M, K = a.shape
     units, N, K2 = wn.shape
     _dev16(a, wn, out)
@@ -187,6 +189,35 @@ def gemm_units(a, wn, bn, *, unit_rows, out=None, rowstats=None, rowstats_eps=1e
         d.flags |= GEMM_ROWSTATS
     check(lib().vcx_gemm_units_f16(ctypes.byref(d), int(unit_rows), N * K, N, _stream()), "vcx_gemm_units_f16")
     return out
+
+
+def units_route(M, N, K, unit_rows, *, lda=None, ldc=None):
+    """The route vcx_gemm_units_f16 takes for M rows in units of unit_rows: a mirror of its dispatcher in csrc/gemm.hip.
+    "single" (one unit: vcx_gemm_f16), "ws320" (one launch of the weight-stationary kernel, N = K = 320), "grouped" (the tiled engine's
+    per-unit form: one plan for all units) or "loop" (vcx_gemm_f16 unit by unit).  Knobs and VCX_GEMM_UNITS_LOOP are read per call, as
+    the dispatcher reads them."""
+    lim = 0xFFFF0000
+    lda, ldc = K if lda is None else lda, N if ldc is None else ldc
+    if unit_rows <= 0 or M <= 0 or M % unit_rows != 0:
+        raise VcxError(f"units_route: M ({M}) must be a whole number of units of {unit_rows} rows")
+    units = M // unit_rows
+    if units == 1:
+        return "single"
+    dma, ws, force = tune_get("GEMM_DMA") != 0, tune_get("GEMM_WS") != 0, tune_get("GEMM_CFG")
+    extents = 2 * ((M - 1) * lda + K) < lim and 2 * (M + 256) * ldc < lim
+    if (K == 320 and N == 320 and unit_rows % 32 == 0 and unit_rows >= 1024 and M >= 8192 and extents and units <= 65535 and dma and ws and force < 0):
+        return "ws320"
+    ws_per_unit = K == 320 and N % 320 == 0 and N <= 1280 and unit_rows >= 8192 and ws and force < 0      # vcx_gemm_f16 would take each unit weight-stationary
+    if (units <= 65535 and K % 64 == 0 and N % 8 == 0 and extents and 2 * ((N - 1) * K + K) < lim and dma and force <= 5 and not ws_per_unit
+            and os.environ.get("VCX_GEMM_UNITS_LOOP", "0")[:1] in ("", "0")):
+        return "grouped"
+    return "loop"
+
+
+def units_one_launch_ok(M, N, K, unit_rows, *, lda=None, ldc=None):
+    """Does vcx_gemm_units_f16 run all units of the call under ONE tile plan (the weight-stationary launch or the tiled engine's per-unit
+    form) instead of once per unit?  (units_route; like lnfold_ok, callers use it to decide a fold whose cost is a launch per unit.)"""
+    return units_route(M, N, K, unit_rows, lda=lda, ldc=ldc) in ("ws320", "grouped")
 
 
 def lnfold_ok(rows, n_out, K, *, lda=None, ldc=None, transposed=False):
