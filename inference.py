@@ -2,7 +2,8 @@
 
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 inference.py ...` starts one process
 per GPU (RCCL over xGMI); independent trajectories (`--renderings a.pt,b.pt,...`, the clips of `--mode sparse_view_interp`)
-are sharded over the ranks with no collective inside the DDIM loop (viewcrafter_amd/parallel.py).
+are sharded over the ranks with no collective inside the DDIM loop (viewcrafter_amd/parallel.py).  VCX_GUIDANCE_PARALLEL=1 (opt-in)
+puts ONE video on the 2 (CFG) or 3 (multi-condition guidance) GPUs of a group instead: one guidance evaluation per GPU and step.
 """
 import os
 from datetime import datetime
@@ -15,7 +16,7 @@ def main(argv=None):
     from viewcrafter_amd import parallel
     rank, world = parallel.init_distributed()
     if world > 1 and str(opts.device).startswith("cuda"):
-        opts.device = f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}"
+        opts.device = f"cuda:{parallel.local_device_index()}"          # LOCAL_RANK (wrapped round the devices in the VCX_SHARE_GPU test mode)
     from viewcrafter import ViewCrafter
     if opts.exp_name is None:
         stamp = datetime.now().strftime("%Y%m%d_%H%M")

@@ -36,7 +36,9 @@ class ViewCrafter:
         rank, world = parallel.rank_world()
         # sparse-view mode under a torchrun launch: DUSt3R and the point render run on rank 0 ONLY (they are the reference's, and
         # identical on every rank); the clips they produce are broadcast and sharded (nvs_sparse_view_interp below)
-        geometry_here = not (world > 1 and rank != 0 and getattr(opts, "mode", None) == "sparse_view_interp")
+        # ... and in EVERY mode of a guidance-parallel launch (VCX_GUIDANCE_PARALLEL=1): all ranks of a group must denoise the same clip
+        recorded = getattr(opts, "mode", None) == "sparse_view_interp" or parallel.guidance_parallel_from_env()
+        geometry_here = not (world > 1 and rank != 0 and recorded)
         if getattr(opts, "renderings", None) is None and not gradio and geometry_here:
             self._attach_reference_geometry()
 
@@ -79,8 +81,32 @@ class ViewCrafter:
                 self.diffusion, prompts, videos, self.noise_shape, self.opts.n_samples, self.opts.ddim_steps,
                 self.opts.ddim_eta, self.opts.unconditional_guidance_scale, self.opts.cfg_img, self.opts.frame_stride,
                 self.opts.text_input, self.opts.multiple_cond_cfg, self.opts.timestep_spacing, self.opts.guidance_rescale,
-                condition_index)
+                condition_index, **self._split_kw())
         return torch.clamp(batch_samples[0][0].permute(1, 2, 3, 0), -1., 1.)
+
+    def _split_kw(self):
+        """guidance_group=... while run_diffusion_many runs a guidance-parallel launch, nothing otherwise."""
+        group = self.__dict__.get("_split")
+        return {} if group is None else {"guidance_group": group}
+
+    def _guidance_group(self):
+        """None with VCX_GUIDANCE_PARALLEL off (the default).  On: the parallel.GuidanceGroup of this rank, built once per launch (every
+        rank creates every process group); rank 0 prints the layout and names the ranks that stay idle."""
+        if not parallel.guidance_parallel_from_env():
+            return None
+        if self.__dict__.get("_guidance") is None:
+            rank, world = parallel.rank_world()
+            o = self.opts
+            copies = clip_batch.guidance_copies(o.unconditional_guidance_scale, o.multiple_cond_cfg, o.cfg_img)
+            line = parallel.describe_layout(world, copies)          # refuses a launch that cannot be split
+            if rank == 0:
+                print(line, flush=True)
+                idle = parallel.guidance_layout(world, copies)[3]
+                if idle:
+                    print(f"[guidance-parallel] WARNING: ranks {idle} are idle ({world} ranks do not divide into groups of {copies}): "
+                          "they own no clip and only join the start-up broadcast and the final barrier", flush=True)
+            self.__dict__["_guidance"] = parallel.build_guidance_group(copies)
+        return self.__dict__["_guidance"]
 
     def _synthesis_args(self):
         o = self.opts
@@ -93,7 +119,7 @@ class ViewCrafter:
         videos = [(r * 2. - 1.).permute(3, 0, 1, 2).unsqueeze(0).to(self.device) for r in clips]
         with torch.no_grad():
             outs = image_guided_synthesis_clips(self.diffusion, [self.opts.prompt], videos, self.noise_shape, *self._synthesis_args(),
-                                                condition_index=[0], streams=streams)
+                                                condition_index=[0], streams=streams, **self._split_kw())
         return [torch.clamp(o[0][0].permute(1, 2, 3, 0), -1., 1.) for o in outs]
 
     def run_diffusion_many(self, clips):
@@ -109,11 +135,33 @@ class ViewCrafter:
         per UNet forward with CFG), every clip drawing from its own generator state - the videos are bit-identical to the plain loop's.
         k is capped where a forward would reach the GEMM engine's 4 GiB extents (clip_batch.max_clips_per_forward: k <= 3 with CFG at
         576 x 1024 x 25, k <= 2 with multi-condition guidance).  Measured sign: README.md (multi-clip paragraph).  Not combined with
-        VCX_CLIPS_PER_GPU > 1 (refused)."""
-        _, world = parallel.rank_world()
+        VCX_CLIPS_PER_GPU > 1 (refused).
+
+        VCX_GUIDANCE_PARALLEL=1 (opt-in): ONE clip on several GPUs.  Consecutive ranks form groups of 2 (CFG) or 3 (multi-condition
+        guidance) ranks; the clips are sharded over the G GROUPS (group g: clips g, g + G, ...), every rank of a group runs the clip's
+        whole preamble itself and, in the DDIM loop, the ONE guidance evaluation of its position, exchanged with one all_gather per
+        step (parallel.GuidanceGroup).  Clip i is seeded as a launch of W = G ranks seeds it - with one group clip 0 continues the
+        current state - and every rank of a group alike, so the videos are bit-identical to that launch's.  VCX_CLIP_BATCH=k beside it:
+        each rank runs a B = k forward of its one conditioning (the extent cap counts one video per clip).  VCX_CLIPS_PER_GPU > 1 is
+        refused."""
+        split = self._guidance_group()
+        if split is None:
+            return self._run_many(clips, parallel.rank_world()[1], None)
+        self.__dict__["_split"] = split
+        try:
+            outs = self._run_many(clips, split.n_groups, split)
+        finally:
+            self.__dict__["_split"] = None
+        if split.position is not None:       # every working rank says what IT executed: one forward of its conditioning per step
+            print(split.report(parallel.rank_world()[0]), flush=True)
+        return outs
+
+    def _run_many(self, clips, world, split):
+        """run_diffusion_many over `world` owners of clips: the ranks, or the guidance groups (`split`)."""
         k = clip_batch.clip_batch_from_env()
         if k > 1:      # capped per workload, never split inside a forward
-            copies = clip_batch.guidance_copies(self.opts.unconditional_guidance_scale, self.opts.multiple_cond_cfg, self.opts.cfg_img)
+            copies = 1 if split is not None else clip_batch.guidance_copies(self.opts.unconditional_guidance_scale,
+                                                                            self.opts.multiple_cond_cfg, self.opts.cfg_img)
             k = min(k, clip_batch.max_clips_per_forward(self.diffusion.model.diffusion_model, self.noise_shape, copies))
         if k > 1:
             def group(items, indices):
@@ -121,7 +169,7 @@ class ViewCrafter:
                 outs = self.run_diffusion_clips(items, streams)
                 streams.finish()
                 return outs
-            return parallel.run_sharded_batched(group, list(clips), k, gather=True)
+            return parallel.run_sharded_batched(group, list(clips), k, gather=True, group=split)
 
         def one(clip, index):
             if world > 1 or index > 0:
@@ -135,7 +183,8 @@ class ViewCrafter:
             lanes = max(1, int(os.environ.get("VCX_CLIPS_PER_GPU", "1")))
         except ValueError:
             lanes = 1
-        return parallel.run_sharded(one, list(clips), gather=True, lanes=lanes, model=self.diffusion)
+        return parallel.run_sharded(one, list(clips), gather=True, lanes=1 if split is not None else lanes, model=self.diffusion,
+                                    group=split)
 
     def nvs_from_renderings(self, path):
         """Diffusion leg only: `path` holds point-cloud renders [T, H, W, 3] in [0, 1] (.pt or .npy) - or several
@@ -195,7 +244,49 @@ class ViewCrafter:
         raise AttributeError(f"{type(self).__name__!s} has no attribute {name!r}"
                              + ("" if ref is not None else " (no reference checkout attached: geometry stages unavailable)"))
 
+    def _record_on_rank0(self, method, *args):
+        """The reference's `method` in recording mode on RANK 0 ONLY (its run_diffusion only collects the clips and returns zeros);
+        returns the clips on every rank.  A failure on rank 0 is raised on every rank together."""
+        rank, _ = parallel.rank_world()
+        clips, error = None, None
+        if rank == 0:
+            clips = []
+            self._ref._record = clips
+            try:
+                getattr(self._ref, method)(*args)
+            except Exception as e:          # reported to every rank by the broadcast below: all fail together, nobody hangs
+                error = f"{type(e).__name__}: {e}"
+            finally:
+                self._ref._record = None
+        clips = parallel.broadcast_tensor_list(clips, src=0, error=error)
+        if parallel.guidance_parallel_from_env():
+            # the geometry pass may have drawn random numbers on rank 0 alone; with one group clip 0 continues the current generator
+            # state (as the one-process run does), and the ranks of a group must draw the same noise
+            parallel.broadcast_rng_state(src=0)
+        return clips
+
+    def _single_view_split(self, method, stem, *args):
+        """A single-view mode of a guidance-parallel launch: geometry on rank 0 (the reference's DUSt3R and render need not give the same
+        bits on two ranks), the clip broadcast, the video denoised by the group; rank 0 writes <stem>.pt / .mp4 over the placeholder
+        video the recording pass left."""
+        from viewcrafter_amd.utils.video_io import save_video
+        self._guidance_group()          # a launch that cannot be split (one process, too few ranks) is refused BEFORE the geometry runs
+        clips = self._record_on_rank0(method, *args)
+        if len(clips) != 1:
+            raise RuntimeError(f"{method} denoises one clip, the reference's method asked for {len(clips)}")
+        outs = self.run_diffusion_many(clips)
+        if parallel.rank_world()[0] != 0:
+            return None
+        torch.save(outs[0].cpu(), os.path.join(self.opts.save_dir, f"{stem}.pt"))
+        video = os.path.join(self.opts.save_dir, f"{stem}.mp4")
+        written = save_video((outs[0] + 1.0) / 2.0, video, fps=8, value_range=(0.0, 1.0))
+        if written != video and os.path.exists(video):
+            os.remove(video)            # the writer fell back to another container: the placeholder must not stay beside the result
+        return outs[0]
+
     def nvs_single_view(self, gradio=False):
+        if parallel.guidance_parallel_from_env():
+            return self._single_view_split("nvs_single_view", "diffusion0", gradio)
         return self._ref.nvs_single_view(gradio)
 
     def nvs_sparse_view_interp(self):
@@ -210,17 +301,7 @@ class ViewCrafter:
         if world == 1:
             return self._ref.nvs_sparse_view_interp()
         from viewcrafter_amd.utils.video_io import save_video
-        clips, error = None, None
-        if rank == 0:       # geometry once: the reference's method in recording mode (run_diffusion only collects its clips)
-            clips = []
-            self._ref._record = clips
-            try:
-                self._ref.nvs_sparse_view_interp()
-            except Exception as e:          # reported to every rank by the broadcast below: all fail together, nobody hangs
-                error = f"{type(e).__name__}: {e}"
-            finally:
-                self._ref._record = None
-        clips = parallel.broadcast_tensor_list(clips, src=0, error=error)
+        clips = self._record_on_rank0("nvs_sparse_view_interp")     # geometry once: run_diffusion only collects its clips
         outs = self.run_diffusion_many(clips)
         if rank != 0:
             return None
@@ -229,6 +310,8 @@ class ViewCrafter:
         return result
 
     def nvs_single_view_eval(self):
+        if parallel.guidance_parallel_from_env():
+            return self._single_view_split("nvs_single_view_eval", "diffusion_ref0")
         return self._ref.nvs_single_view_eval()
 
     def run_gradio(self, *args, **kwargs):

@@ -29,6 +29,9 @@ class DDIMSampler(object):
         # ahead of the first cross-attention are computed once (UNetModel._forward, cfg_repeat) - bit-identical results: every route decision
         # of the host graph is made per video (tests/test_batch_invariance_gpu.py checks both routes against each other at full width)
         self.share_cfg_prefix = True
+        # one video on several GPUs (VCX_GUIDANCE_PARALLEL, viewcrafter_amd/parallel.py): a parallel.GuidanceGroup - this rank then
+        # evaluates ONLY the conditioning of its position and receives the others' outputs (_split_outputs); None = everything here
+        self.guidance_group = None
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor):
@@ -112,6 +115,7 @@ class DDIMSampler(object):
             subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
             timesteps = self.ddim_timesteps[:subset_end]
         intermediates = {"x_inter": [img], "pred_x0": [img]}
+        start_sum = None if self.guidance_group is None else self.guidance_group.checksum(img)      # compared with the final latent's
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
         clean_cond = kwargs.pop("clean_cond", False)
@@ -131,11 +135,30 @@ class DDIMSampler(object):
                 callback(i)
             if img_callback:
                 img_callback(pred_x0, i)
+            if self.guidance_group is not None and hasattr(self.guidance_group, "stats"):
+                self.guidance_group.stats["steps"] += 1
             step_yield()           # two clips per GPU (viewcrafter_amd/interleave.py): the other clip's step is queued next; a no-op otherwise
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates["x_inter"].append(img)
                 intermediates["pred_x0"].append(pred_x0)
+        if self.guidance_group is not None:      # x was never sent inside the group: check once per video that it did stay bit-equal
+            self.guidance_group.check_equal(img, also={"x_T": start_sum})
         return img, intermediates
+
+    # ------------------------------------------------------------------ guidance evaluations split over the ranks of a group
+    def _split_outputs(self, x, t, conds, kwargs):
+        """One forward of batch b under conds[position] - no cfg_repeat, no stacking, whatever the conditionings' types - then one
+        all_gather: every rank of the group returns the same len(conds) outputs, in the order of `conds`.  The exchange is outside the
+        forward, so a captured forward (use_hip_graph) replays as it is."""
+        group = self.guidance_group
+        if group.size != len(conds):
+            raise ValueError(f"the guidance group has {group.size} ranks, a step has {len(conds)} denoiser evaluations")
+        stats = getattr(group, "stats", None)
+        if stats is not None:
+            stats["forwards"] += 1
+            stats["batch"] = x.shape[0]
+        # the outputs are views of the group's ONE reused buffer: valid until the next exchange (the step kernel reads them now)
+        return group.exchange(self.model.apply_model(x, t, conds[group.position], **kwargs))
 
     # ------------------------------------------------------------------ CFG batching
     @staticmethod
@@ -188,6 +211,9 @@ class DDIMSampler(object):
         cfg_img)."""
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
             return self.model.apply_model(x, t, c, **kwargs), None, None, 0.0
+        if self.guidance_group is not None:
+            v_c, v_u = self._split_outputs(x, t, (c, unconditional_conditioning), kwargs)
+            return v_c, v_u, None, 0.0
         if self._batchable(c, unconditional_conditioning):
             v_c, v_u = self._apply_batched(x, t, (c, unconditional_conditioning), kwargs)
         elif isinstance(c, (torch.Tensor, dict)):

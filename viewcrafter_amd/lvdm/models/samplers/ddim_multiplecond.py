@@ -42,7 +42,9 @@ class DDIMSampler(_DDIMSampler):
         uc_img = kwargs["unconditional_conditioning_img_nonetext"]
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
             return self.model.apply_model(x, t, c, **kwargs), None, None, 0.0
-        if self._batchable(c, unconditional_conditioning, uc_img):
+        if self.guidance_group is not None:
+            v_c, v_u, v_i = self._split_outputs(x, t, (c, unconditional_conditioning, uc_img), kwargs)
+        elif self._batchable(c, unconditional_conditioning, uc_img):
             v_c, v_u, v_i = self._apply_batched(x, t, (c, unconditional_conditioning, uc_img), kwargs)
         else:
             v_c = self.model.apply_model(x, t, c, **kwargs)

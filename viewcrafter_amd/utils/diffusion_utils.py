@@ -125,20 +125,25 @@ def _conditioning(model, prompts, videos, batch_size, unconditional_guidance_sca
     return cond, uc, uc_2
 
 
-def _sampler(model, multiple_cond_cfg):
+def _sampler(model, multiple_cond_cfg, guidance_group=None):
     from ..lvdm.models.samplers.ddim import DDIMSampler
     if multiple_cond_cfg:
         from ..lvdm.models.samplers.ddim_multiplecond import DDIMSampler as DDIMSamplerMulti
-        return DDIMSamplerMulti(model)
-    return DDIMSampler(model)
+        sampler = DDIMSamplerMulti(model)
+    else:
+        sampler = DDIMSampler(model)
+    sampler.guidance_group = guidance_group
+    return sampler
 
 
 def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, timestep_spacing="uniform", guidance_rescale=0.0,
-                           condition_index=None, **kwargs):
-    """Reference diffusion_utils.py:117-201.  videos [B, 3, T, H, W] in [-1, 1]; returns [B, n_samples, 3, T, H, W]."""
-    ddim_sampler = _sampler(model, multiple_cond_cfg)
+                           condition_index=None, guidance_group=None, **kwargs):
+    """Reference diffusion_utils.py:117-201.  videos [B, 3, T, H, W] in [-1, 1]; returns [B, n_samples, 3, T, H, W].
+    `guidance_group` (not in the reference; default None = unchanged): a parallel.GuidanceGroup - this rank runs the whole preamble
+    itself and, in the loop, only the guidance evaluation of its position (VCX_GUIDANCE_PARALLEL)."""
+    ddim_sampler = _sampler(model, multiple_cond_cfg, guidance_group)
     batch_size = noise_shape[0]
     fs = torch.tensor([fs] * batch_size, dtype=torch.long, device=model.device)
     cond, uc, uc_2 = _conditioning(model, prompts, videos, batch_size, unconditional_guidance_scale, cfg_img, text_input,
@@ -166,13 +171,14 @@ def _stack(conds):
 def image_guided_synthesis_clips(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
                                  unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                                  multiple_cond_cfg=False, timestep_spacing="uniform", guidance_rescale=0.0,
-                                 condition_index=None, streams=None, **kwargs):
+                                 condition_index=None, streams=None, guidance_group=None, **kwargs):
     """k independent clips in ONE DDIM loop (VCX_CLIP_BATCH, viewcrafter_amd/clip_batch.py).  `videos`: a list of k tensors
     [b, 3, T, H, W] (b = noise_shape[0]); `prompts`: one prompt list for every clip or a list of k such lists; `streams`: a
     clip_batch.ClipStreams of k clips, whose contexts every random draw of clip i is made in.  Each clip's cond / uncond is built on its
     own, the conditionings are stacked on the batch axis, one sampler runs over B = k b (k b x 2 videos per forward with CFG, x 3 with
     multi-condition guidance) and each clip's latent is decoded on its own.  Returns a list of k tensors [b, n_samples, 3, T, H, W],
-    each bit-identical to image_guided_synthesis of that clip after its clip's seed."""
+    each bit-identical to image_guided_synthesis of that clip after its clip's seed.  `guidance_group`: as in image_guided_synthesis
+    (each rank of the group then runs a B = k b forward of its one conditioning)."""
     k = len(videos)
     if streams is None or len(streams) != k:
         raise ValueError(f"image_guided_synthesis_clips needs a ClipStreams of {k} clips")
@@ -186,7 +192,7 @@ def image_guided_synthesis_clips(model, prompts, videos, noise_shape, n_samples=
     for v in videos:
         if v.shape[0] != b:
             raise ValueError(f"every clip needs batch {b} (noise_shape[0]), got {tuple(v.shape)}")
-    ddim_sampler = _sampler(model, multiple_cond_cfg)
+    ddim_sampler = _sampler(model, multiple_cond_cfg, guidance_group)
     parts = []
     for i in range(k):
         with streams.clip(i):
