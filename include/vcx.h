@@ -223,6 +223,11 @@ int vcx_layernorm_f16(const void* x, void* y, const float* gamma, const float* b
  *   V^T rows : vt + (h*64)*ldvt + (g / kv_div)*kv_rows       64 rows (d) x nk cols (keys)
  *   O rows   : o  + (g*nq)*ldo + h*64
  * kv_rows is the row count between consecutive K/V groups (>= nk, multiple of 8).
+ * Padding (this entry point, the dual form and vcx_attn_flash_d512_f16 alike; tests/test_exact_gpu.py poisons it): K rows [nk, kv_rows)
+ * and V^T columns from the next multiple of 8 above nk up to kv_rows are never used, whatever they hold - NaN and Inf included.  The V^T
+ * columns [nk, (nk + 7) & ~7) are fetched with their 16-byte piece and meet a probability of exactly 0 on the matrix pipe: they must
+ * be FINITE (0 x NaN / Inf is NaN); any finite value gives the same bits.  The model code projects V^T from zero-padded token rows, so
+ * those columns hold the projection of a zero row; a caller that fills V^T itself must not leave them uninitialised.
  * flags: VCX_ATTN_ACCUMULATE adds into O (second softmax of the text (+) image
  * cross-attention, attention.py:129-142); VCX_ATTN_LOG2_LOGITS says the caller folded
  * scale * log2(e) into Q and/or K (e.g. as the alpha of the projection GEMM), so that
@@ -254,7 +259,8 @@ int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const void* vt1, 
 /* Flash attention with ONE head of dim 512, no mask: O = softmax(scale * Q K^T) V - the AttnBlock of the VAE
  * (lvdm/modules/networks/ae_modules.py:26-78 at 9216 tokens per 576x1024 frame); the score matrix is never materialised.
  * Group g (a frame): Q rows q + (g*nq)*ldq (512 columns), K rows k + (g*kv_rows)*ldk (nk valid), V^T rows vt + d*ldvt + g*kv_rows
- * (512 rows d x nk columns), O rows o + (g*nq)*ldo.  kv_rows >= nk, multiple of 8 (rows [nk, kv_rows) must be readable). */
+ * (512 rows d x nk columns), O rows o + (g*nq)*ldo.  kv_rows >= nk, multiple of 8 (rows [nk, kv_rows) must be readable; padding values: as for
+ * vcx_attn_flash_d64_f16 - only the V^T columns [nk, (nk + 7) & ~7) are used, and they must be finite). */
 int vcx_attn_flash_d512_f16(const void* q, const void* k, const void* vt, void* o, int n_groups, int nq, int nk, int kv_rows,
                             int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, float scale, void* stream);
 

@@ -21,19 +21,23 @@ def rel_l2(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-def check(out, ref, tol=2e-3, name=""):
+def check(out, ref, tol=2e-3, name="", maxabs=1e-2):
+    """rel-L2 <= tol and, element by element, |out - ref| <= maxabs * max|ref| (the module docstring's bound; a per-case `maxabs` other
+    than 1e-2 needs a derivation from the kernel's rounding points where it is passed)."""
     assert torch.isfinite(out.float()).all(), f"{name}: non-finite output"
     e = rel_l2(out, ref)
     mx = float((out.float().cpu() - ref.float().cpu()).abs().max())
-    assert e <= tol, f"{name}: rel-L2 {e:.3e} > {tol:.1e} (max abs {mx:.3e}, ref max {float(ref.abs().max()):.3e})"
+    mref = float(ref.abs().max())
+    assert e <= tol, f"{name}: rel-L2 {e:.3e} > {tol:.1e} (max abs {mx:.3e}, ref max {mref:.3e})"
+    assert mx <= maxabs * mref, f"{name}: max abs {mx:.3e} > {maxabs:.1e} * max|ref| = {maxabs * mref:.3e} (rel-L2 {e:.3e})"
 
 
-def check_rows(out, ref_rows, tol=2e-3, name="", chunk=65536):
+def check_rows(out, ref_rows, tol=2e-3, name="", chunk=65536, maxabs=1e-2):
     """check() against an fp32 / fp64 reference that is formed `chunk` rows at a time on the GPU (ref_rows(r0, r1) -> rows r0 .. r1 - 1): the
     benchmark's 460800-row problems are checked against fp32 like the small ones, without a 4.7 GB reference tensor (review r5 item 7)."""
     assert torch.isfinite(out.float()).all(), f"{name}: non-finite output"
     num = den = 0.0
-    mx = 0.0
+    mx = mref = 0.0
     for r0 in range(0, out.shape[0], chunk):
         r1 = min(r0 + chunk, out.shape[0])
         ref = ref_rows(r0, r1).double()
@@ -41,8 +45,10 @@ def check_rows(out, ref_rows, tol=2e-3, name="", chunk=65536):
         num += float((d * d).sum())
         den += float((ref * ref).sum())
         mx = max(mx, float(d.abs().max()))
+        mref = max(mref, float(ref.abs().max()))
     e = math.sqrt(num / (den + 1e-300))
     assert e <= tol, f"{name}: rel-L2 {e:.3e} > {tol:.1e} (max abs {mx:.3e}) over {out.shape[0]} rows"
+    assert mx <= maxabs * mref, f"{name}: max abs {mx:.3e} > {maxabs:.1e} * max|ref| = {maxabs * mref:.3e} over {out.shape[0]} rows (rel-L2 {e:.3e})"
     return e
 
 

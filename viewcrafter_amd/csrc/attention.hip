@@ -1147,7 +1147,7 @@ __global__ void __launch_bounds__(512) tattn_d64_kernel(TAttnArgs p) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) pf[s][j] = (half_t)(sacc[8 * s + j] * inv);   // normalised P, fp16 like the reference's einsum input
+        for (int j = 0; j < 8; ++j) pf[s][j] = (half_t)sacc[8 * s + j];   // UNnormalised P (the row maximum is exactly 1): 1 / l multiplies the fp32 result, like the flash kernels - equal logits give the exact mean, not sum x fp16(1 / T)
     if (REL) {
         // the probabilities of this lane's query by clipped distance: unique inside (-R, R), summed beyond (this lane's 16 keys, then the
         // other half of the row in lane ^ 32); masked / padded keys have probability 0
@@ -1156,7 +1156,7 @@ __global__ void __launch_bounds__(512) tattn_d64_kernel(TAttnArgs p) {
         for (int r = 0; r < 16; ++r) {
             const int key = (r & 3) + 8 * (r >> 2) + 4 * hi;
             const int d = key - lq;
-            const float pv = (float)pf[r >> 3][r & 7];
+            const float pv = (float)pf[r >> 3][r & 7] * inv;
             if (key < p.T) {
                 if (d <= -p.R) lo += pv;
                 else if (d >= p.R) up += pv;
@@ -1184,6 +1184,8 @@ __global__ void __launch_bounds__(512) tattn_d64_kernel(TAttnArgs p) {
             for (int j = 0; j < 8; ++j) vf[j] = sv[(16 * s + (j & 3) + 8 * (j >> 2) + 4 * hi) * VLD + d];
             oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[s], s == 0 ? zero16 : oacc[db], 0, 0, 0);
         }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oacc[db][i] *= inv;
     }
     // Output row (frame lq) of this (pixel, head): column group k = 4 db + gq holds columns 8k + 4 hi .. + 3 in this lane, i.e. a
     // row is split 8 bytes / 8 bytes between lanes l and l + 32.  v_permlane32_swap on the packed words of groups k (vdst) and
@@ -1275,6 +1277,7 @@ __global__ void __launch_bounds__(512) tattn64_d64_kernel(TAttnArgs p) {
             for (int s = 0; s < 4; ++s) sacc[kt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[kt][s], qf[qt][s], sacc[kt][qt], 0, 0, 0);
         }
     h8 pf[2][2][2];                                                   // [key tile][query tile][k-step of 16 keys]
+    float inv[2];                                                     // 1 / row sum per query tile: multiplies the fp32 result
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
         const int q = 32 * qt + lq;
@@ -1298,13 +1301,13 @@ __global__ void __launch_bounds__(512) tattn64_d64_kernel(TAttnArgs p) {
                 l += e;
             }
         l += __shfl_xor(l, 32);
-        const float inv = 1.0f / l;
+        inv[qt] = 1.0f / l;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) pf[kt][qt][s][j] = (half_t)(sacc[kt][qt][8 * s + j] * inv);
+                for (int j = 0; j < 8; ++j) pf[kt][qt][s][j] = (half_t)sacc[kt][qt][8 * s + j];      // unnormalised, as in tattn_d64_kernel
     }
     // O^T[d, q] = sum_key V^T[d, key] P^T[key, q]: a V^T fragment (d half db, key tile kt, k-step s) serves both query tiles
     f16v oacc[2][2];                                                  // [d half][query tile]
@@ -1323,6 +1326,8 @@ __global__ void __launch_bounds__(512) tattn64_d64_kernel(TAttnArgs p) {
                 oacc[db][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kt][0][s], oacc[db][0], 0, 0, 0);
                 oacc[db][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kt][1][s], oacc[db][1], 0, 0, 0);
             }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { oacc[db][0][i] *= inv[0]; oacc[db][1][i] *= inv[1]; }
     }
     typedef unsigned u2v __attribute__((ext_vector_type(2)));
     typedef unsigned u4v __attribute__((ext_vector_type(4)));

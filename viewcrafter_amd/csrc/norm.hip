@@ -193,8 +193,8 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ x, const half_t* __re
     const int n = blockIdx.y;
     const int cpg = C / groups;
     const int c8 = tid % cw, plane = tid / cw;
-    float sc[8], sh[8];             // x * sc + (beta - mean * sc): one fma per element; the rounding of mean * sc costs
-#pragma unroll                      // 1e-7 |mean| / std of the output scale - below the fp16 output step up to |mean| ~ 1000 std
+    float sc[8], mn[8], bt[8];      // (x - mean) * sc + beta: the difference first (exact where x equals the mean, rounded relative to the
+#pragma unroll                      // DEVIATION elsewhere), so that no |mean| / std enters the error - x * sc + (beta - mean * sc) rounded mean * sc
     for (int e = 0; e < 8; ++e) {
         const int c = c8 * 8 + e;
         const int g = c / cpg;
@@ -202,7 +202,8 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ x, const half_t* __re
         const float var = stats[((int64_t)n * groups + g) * 2 + 1];
         const float a = rsqrtf(var + eps) * gamma[c];
         sc[e] = a;
-        sh[e] = beta[c] - mean * a;
+        mn[e] = mean;
+        bt[e] = beta[c];
     }
     const int64_t p0 = (int64_t)blockIdx.x * pix_per_block;
     const int64_t p1 = (p0 + pix_per_block < pixels) ? p0 + pix_per_block : pixels;
@@ -224,7 +225,7 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ x, const half_t* __re
         for (int u = 0; u < 4; ++u) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                float f = (float)v[u][e] * sc[e] + sh[e];
+                float f = __builtin_fmaf((float)v[u][e] - mn[e], sc[e], bt[e]);
                 if (silu) f = vcx_silu(f);
                 v[u][e] = (half_t)f;
             }
@@ -235,7 +236,7 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ x, const half_t* __re
         h8 v = *reinterpret_cast<const h8*>(xp + pix * Cx);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float f = (float)v[e] * sc[e] + sh[e];
+            float f = __builtin_fmaf((float)v[e] - mn[e], sc[e], bt[e]);
             if (silu) f = vcx_silu(f);
             v[e] = (half_t)f;
         }
