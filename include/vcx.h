@@ -37,8 +37,8 @@ extern "C" {
  * struct_size - a descriptor of another layout is rejected instead of read past its end; ldcs; vcx_clip_preprocess_f32,
  * vcx_add_nchw_f32_to_nhwc_f16.  6: vcx_ddim_ws_bytes, ws_bytes argument of the DDIM steps.  7: vcx_groupnorm_fold_linear_f16,
  * vcx_gemm_units_f16, vcx_attn_flash_d512_f16.  8: vcx_gemm_desc grows rowstats / rowstats_eps (VCX_GEMM_ROWSTATS) and
- * tail_a0 / tail_a1 (K tail of a convolution from linear sources); vcx_groupnorm_apply2_f16. */
-#define VCX_ABI_VERSION 9
+ * tail_a0 / tail_a1 (K tail of a convolution from linear sources); vcx_groupnorm_apply2_f16.  10: vcx_gemm_route. */
+#define VCX_ABI_VERSION 10
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -151,19 +151,39 @@ int vcx_gemm_f16(const vcx_gemm_desc* desc_host, void* stream);
 /* The same linear layer with ONE weight / bias set per `unit_rows` consecutive rows: rows [u unit_rows, (u + 1) unit_rows) use
  * W + u w_unit_stride and bias + u bias_unit_stride (element strides) - the (Wn, bn) sets of vcx_groupnorm_fold_linear_f16, one per
  * frame (SpatialTransformer.norm -> proj_in, attention.py:265-269,299) or per video (TemporalTransformer, attention.py:331-336,369-372).
- * Linear mode, VCX_GEMM_BIAS_N at most, M a whole number of units.  Routes, the first that applies:
- *  - N = K = 320 with unit_rows % 32 == 0, >= 1024 and M >= 8192: ONE launch of the weight-stationary kernel (a block keeps its unit's
- *    weights in registers);
- *  - more than one unit, K % 64 == 0, N % 8 == 0, A and C of the whole call addressable with 32-bit byte offsets (below 0xFFFF0000, the
- *    output up to 256 rows past its end), at most 65535 units, knob GEMM_DMA on: the tiled engine's per-unit form - ONE tile plan over
- *    units x ceil(unit_rows / tile rows) row tiles (no tile straddles two units), at most two launches.  Not where vcx_gemm_f16 would run
- *    each unit on its weight-stationary kernel (K = 320, N = 320 j <= 1280, unit_rows >= 8192), nor under a forced GEMM_CFG 6;
- *  - every other shape unit by unit through vcx_gemm_f16.  VCX_GEMM_UNITS_LOOP=1 in the environment (read per call) sends the second
- *    route here too (tests, A/B runs).
- * The second and third route give the same bits.  A forced GEMM_CFG forces the per-unit form's tile configuration too; under
- * VCX_GEMM_PLAN_TRACE it prints its segments with ` units <U> unit_rows <R>` appended (U = the units of the segment).
+ * Linear mode, VCX_GEMM_BIAS_N at most, M a whole number of units.  Routes, the first that applies (vcx_gemm_route tells which):
+ *  - VCX_ROUTE_UNITS_WS320: more than one unit, N = K = 320 with unit_rows % 32 == 0, >= 1024 and M >= 8192: ONE launch of the
+ *    weight-stationary kernel (a block keeps its unit's weights in registers);
+ *  - VCX_ROUTE_UNITS_GROUPED: more than one unit, K % 64 == 0, N % 8 == 0, A and C of the whole call addressable with 32-bit byte offsets
+ *    (below 0xFFFF0000, the output up to 256 rows past its end), at most 65535 units, knob GEMM_DMA on: the tiled engine's per-unit form -
+ *    ONE tile plan over units x ceil(unit_rows / tile rows) row tiles (no tile straddles two units), at most two launches.  Not where
+ *    vcx_gemm_f16 would run a unit on its weight-stationary kernel (VCX_ROUTE_WS320 for a call of unit_rows rows), nor under a forced GEMM_CFG 6;
+ *  - VCX_ROUTE_UNITS_LOOP: every other shape unit by unit through vcx_gemm_f16.  VCX_GEMM_UNITS_LOOP=1 in the environment (read per call)
+ *    sends the second route here too (tests, A/B runs).
+ * ONE unit is vcx_gemm_f16's call and takes its route.  The second and third route give the same bits.  A forced GEMM_CFG forces the
+ * per-unit form's tile configuration too; under VCX_GEMM_PLAN_TRACE it prints its segments with ` units <U> unit_rows <R>` appended
+ * (U = the units of the segment).
  * VCX_GEMM_ROWSTATS: in the weight-stationary one-launch form, or with one unit (vcx_gemm_f16's weight-stationary kernel, the same bits). */
 int vcx_gemm_units_f16(const vcx_gemm_desc* desc_host, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, void* stream);
+
+/* ABI 10.  Which kernel would take the call - vcx_gemm_f16 (unit_rows = 0) or vcx_gemm_units_f16 (unit_rows > 0) - under the knobs of
+ * this moment: the launchers' own validation and route function, so a caller that must know beforehand whether a layer can write a
+ * by-product (VCX_GEMM_ROWSTATS / COLSTATS, a folded LayerNorm, a K tail) sets the flag and asks, instead of restating the rules.
+ * Pointers are neither checked nor dereferenced (null is fine; strides, shapes and flags decide) and no device is touched.
+ * Returns a VCX_ROUTE_* value; VCX_ROUTE_REFUSED: a valid descriptor that no kernel implements (the launcher would return VCX_EINVAL),
+ * the reason is in vcx_last_error().  A descriptor the launcher's validation rejects: VCX_EINVAL. */
+enum {
+    VCX_ROUTE_REFUSED = 0,
+    VCX_ROUTE_REGISTER = 1,      /* register-staged kernel (csrc/gemm.hip): whatever the DMA kernel cannot address           */
+    VCX_ROUTE_TILED = 2,         /* tiled DMA engine under one tile plan (csrc/gemm_dma.hip)                                */
+    VCX_ROUTE_WS320 = 3,         /* weight-stationary kernels, K = 320 (csrc/gemm_ws.hip): plain / ROWSTATS / COLSTATS ...  */
+    VCX_ROUTE_WS320_GEGLU = 4,   /* ... the GEGLU projection                                                                */
+    VCX_ROUTE_WS320_LNF = 5,     /* ... a LayerNorm-folded projection                                                       */
+    VCX_ROUTE_UNITS_WS320 = 6,   /* vcx_gemm_units_f16: see there                                                           */
+    VCX_ROUTE_UNITS_GROUPED = 7,
+    VCX_ROUTE_UNITS_LOOP = 8
+};
+int vcx_gemm_route(const vcx_gemm_desc* desc_host, int unit_rows);
 
 /* ------------------------------------------------------------------------------------
  * GroupNorm(32 groups) on channels-last fp16 with fp32 statistics.

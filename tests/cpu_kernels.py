@@ -152,10 +152,6 @@ def group_norm(x, gamma, beta, eps, silu, groups=32, out=None, stats=None, x2=No
     return out
 
 
-def conv_tail_ok(M, cin, cout, taps, tail_ks, in_rows=None):
-    return cin % 64 == 0 and cout % 8 == 0 and all(k % 64 == 0 and k > 0 for k in tail_ks) and 0 < len(tail_ks) <= 2
-
-
 def row_stats(x, eps=1e-5):
     xf = x.float()
     mean = xf.mean(1)
@@ -289,20 +285,15 @@ def timestep_embedding(t, dim, max_period=10000.0):
     return torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1) if dim % 2 else emb
 
 
-_TUNE = {}
-
-
 def install(monkeypatch):
-    """Swap the launchers of viewcrafter_amd.ops for the functions above (one test's lifetime)."""
-    from viewcrafter_amd import _lib, ops
-    _TUNE.clear()
+    """Swap the launchers of viewcrafter_amd.ops for the functions above (one test's lifetime).  The route predicates (ops.*_ok,
+    units_route) and the knobs (tune_get / tune_set) stay the product's: libvcx answers them without a GPU."""
+    from viewcrafter_amd import ops
     table = dict(require_gpu=lambda: None, gemm=gemm, group_norm_stats_from_colstats=group_norm_stats_from_colstats, group_norm=group_norm,
                  group_norm_stats=group_norm_stats, group_norm_fold_linear=group_norm_fold_linear, gemm_units=gemm_units,
-                 row_stats=row_stats, layer_norm=layer_norm, conv_tail_ok=conv_tail_ok, flash_attn=flash_attn, flash_attn_d512=flash_attn_d512, flash_attn_dual=flash_attn_dual, temporal_attn=temporal_attn, temporal_attn_rel=temporal_attn_rel,
+                 row_stats=row_stats, layer_norm=layer_norm, flash_attn=flash_attn, flash_attn_d512=flash_attn_d512, flash_attn_dual=flash_attn_dual, temporal_attn=temporal_attn, temporal_attn_rel=temporal_attn_rel,
                  softmax_rows_=softmax_rows_, copy2d=copy2d, avgpool2x2=avgpool2x2, upsample2x=upsample2x, add_nchw_=add_nchw_, ncthw_to_nthwc=ncthw_to_nthwc, nthwc_to_ncthw=nthwc_to_ncthw,
                  timestep_embedding=timestep_embedding, silu_f32=lambda x: F.silu(x.float()), gelu_=lambda x: x.copy_(F.gelu(x.float()).to(_f16)),
-                 to_f16=lambda x: x.to(_f16).contiguous(), to_f32=lambda x: x.float().contiguous(),
-                 tune_get=lambda name: _TUNE.get(name, _lib.TUNE[name][1]),
-                 tune_set=lambda name, v: _TUNE.update({name: int(v)}))
+                 to_f16=lambda x: x.to(_f16).contiguous(), to_f32=lambda x: x.float().contiguous())
     for name, fn in table.items():
         monkeypatch.setattr(ops, name, fn)

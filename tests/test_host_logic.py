@@ -661,14 +661,17 @@ def test_folded_packs_follow_the_parent_blocks_layernorm_and_lnfold_ok_mirrors_t
     plain_w, plain_b = A._plain_of(blk.attn1.packed()["qkv"])
     assert plain_b is None and torch.equal(plain_w, torch.cat([blk.attn1.to_q.weight, blk.attn1.to_k.weight, blk.attn1.to_v.weight]).detach().half())
     # lnfold_ok: mirrors dma_ok of csrc/gemm.hip (knob, K % 64, GEMM N % 8, 32-bit extents incl. 256 rows past the end)
-    monkeypatch.setattr(ops, "tune_get", lambda name: 1)
+    assert ops.tune_get("GEMM_DMA") == 1
     assert ops.lnfold_ok(460800, 960, 320) and ops.lnfold_ok(460800, 320, 320, transposed=True)
     assert not ops.lnfold_ok(460800, 960, 72)                       # K % 64
     assert not ops.lnfold_ok(1001, 320, 320, transposed=True)       # GEMM N = tokens % 8
     assert not ops.lnfold_ok(3_500_000, 960, 640)                   # 4.5 GB of token rows: beyond 32-bit byte offsets
     assert not ops.lnfold_ok(1_200_000, 2560, 320)                  # output rows x ldc beyond 4 GiB
-    monkeypatch.setattr(ops, "tune_get", lambda name: 0)
-    assert not ops.lnfold_ok(460800, 960, 320)                      # knob GEMM_DMA = 0: register-staged kernel, no folded epilogue
+    ops.tune_set("GEMM_DMA", 0)
+    try:
+        assert not ops.lnfold_ok(460800, 960, 320)                  # knob GEMM_DMA = 0: register-staged kernel, no folded epilogue
+    finally:
+        ops.tune_set("GEMM_DMA", 1)
 
 
 # ------------------------------------------------------------------ batch invariance of the host's route decisions (full width, no GPU)

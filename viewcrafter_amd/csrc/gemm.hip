@@ -21,6 +21,7 @@
 #include "vcx_common.h"
 
 #include "gemm_args.h"
+#include <stdarg.h>
 #include <stdlib.h>
 
 using namespace vcxgemm;
@@ -504,25 +505,30 @@ int dispatch(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_t s) 
 
 }  // namespace
 
-static bool force_cfg_unset() { return vcx_tune(VCX_TUNE_GEMM_CFG) < 0; }      // a forced tile configuration (A/B tools, soak) means the tiled engine
 
-extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
+// ---- host side: validate -> route -> run --------------------------------------------------------------------------------------------
+// validate*: every check of a descriptor that does not depend on which kernel takes the call.  gemm_route: the ONE place that decides
+// the kernel - a pure function of the descriptor and the knobs, so vcx_gemm_route answers the host graph's questions (which by-product
+// can this layer write?) with the launchers' own code and without a device.  run: fill_args + the launch of the route.
+// `ptrs` = false (vcx_gemm_route): the pointer and alignment checks are skipped, null pointers are fine.
+
+static int validate(const vcx_gemm_desc* d, bool ptrs) {
     VCX_REQUIRE(d != nullptr, "vcx_gemm_f16: null descriptor");
     // ABI 5: the caller states the size of the struct it filled in.  A binding written against another header version (the
     // 144-byte ABI-1 or 168-byte ABI-4 layouts started with the A pointer) is refused here instead of being read past its end.
     VCX_REQUIRE(d->struct_size == sizeof(vcx_gemm_desc), "vcx_gemm_f16: descriptor struct_size %zu != %zu (sizeof(vcx_gemm_desc), ABI %d)",
                 (size_t)d->struct_size, sizeof(vcx_gemm_desc), VCX_ABI_VERSION);
-    VCX_REQUIRE(d->A && d->W && d->C, "vcx_gemm_f16: null A/W/C");
+    VCX_REQUIRE(!ptrs || (d->A && d->W && d->C), "vcx_gemm_f16: null A/W/C");
     VCX_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "vcx_gemm_f16: empty problem M=%d N=%d K=%d", d->M, d->N, d->K);
     VCX_REQUIRE(d->K % 8 == 0 && d->ldw % 8 == 0 && d->lda % 8 == 0,
                 "vcx_gemm_f16: K (%d), ldw (%d), lda (%lld) must be multiples of 8", d->K, d->ldw, (long long)d->lda);
-    VCX_REQUIRE(((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->W & 15) == 0 && ((uintptr_t)d->C & 15) == 0,
+    VCX_REQUIRE(!ptrs || (((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->W & 15) == 0 && ((uintptr_t)d->C & 15) == 0),
                 "vcx_gemm_f16: A/W/C must be 16-byte aligned");
     const int flags = d->flags;
-    VCX_REQUIRE(!(flags & (VCX_GEMM_BIAS_N | VCX_GEMM_BIAS_M)) || d->bias, "vcx_gemm_f16: bias flag without bias");
-    VCX_REQUIRE(!(flags & VCX_GEMM_ROWADD) || (d->rowadd && d->rowadd_div > 0 && (d->rowadd_ld == 0 || (d->rowadd_ld >= d->N && d->rowadd_ld % 4 == 0))),
+    VCX_REQUIRE(!ptrs || !(flags & (VCX_GEMM_BIAS_N | VCX_GEMM_BIAS_M)) || d->bias, "vcx_gemm_f16: bias flag without bias");
+    VCX_REQUIRE(!(flags & VCX_GEMM_ROWADD) || ((!ptrs || d->rowadd) && d->rowadd_div > 0 && (d->rowadd_ld == 0 || (d->rowadd_ld >= d->N && d->rowadd_ld % 4 == 0))),
                 "vcx_gemm_f16: bad rowadd (rowadd_ld must be 0 or a multiple of 4 >= N)");
-    VCX_REQUIRE(!(flags & VCX_GEMM_RESIDUAL) || d->residual, "vcx_gemm_f16: residual flag without pointer");
+    VCX_REQUIRE(!ptrs || !(flags & VCX_GEMM_RESIDUAL) || d->residual, "vcx_gemm_f16: residual flag without pointer");
     const bool conv = d->mode == 1;
     const bool geglu = flags & VCX_GEMM_GEGLU;
     const bool f32 = flags & VCX_GEMM_OUT_F32;
@@ -535,7 +541,7 @@ extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
     const int lnf = (flags & VCX_GEMM_LNFOLD) ? 1 : (flags & VCX_GEMM_LNFOLD_T) ? 2 : 0;
     if (lnf) {
         VCX_REQUIRE(!((flags & VCX_GEMM_LNFOLD) && (flags & VCX_GEMM_LNFOLD_T)), "vcx_gemm_f16: LNFOLD and LNFOLD_T are exclusive");
-        VCX_REQUIRE(d->ln_stats && d->ln_colsum && ((uintptr_t)d->ln_stats & 15) == 0 && ((uintptr_t)d->ln_colsum & 15) == 0,
+        VCX_REQUIRE(!ptrs || (d->ln_stats && d->ln_colsum && ((uintptr_t)d->ln_stats & 15) == 0 && ((uintptr_t)d->ln_colsum & 15) == 0),
                     "vcx_gemm_f16: LNFOLD needs 16-byte aligned ln_stats and ln_colsum");
         VCX_REQUIRE(!conv && !f32 && !(flags & VCX_GEMM_ROWADD), "vcx_gemm_f16: LNFOLD is for linear layers with fp16 output, without ROWADD");
         VCX_REQUIRE(lnf == 1 ? !(flags & VCX_GEMM_BIAS_M) : !(flags & VCX_GEMM_BIAS_N) && !geglu,
@@ -543,7 +549,7 @@ extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
         VCX_REQUIRE((lnf == 1 ? d->N : d->M) % 4 == 0 && (lnf == 1 ? d->N : d->M) >= 4, "vcx_gemm_f16: LNFOLD needs the colsum side to be a multiple of 4");
     }
     if (flags & VCX_GEMM_COLSTATS) {
-        VCX_REQUIRE(d->colstats && ((uintptr_t)d->colstats & 15) == 0, "vcx_gemm_f16: COLSTATS needs a 16-byte aligned colstats buffer");
+        VCX_REQUIRE(!ptrs || (d->colstats && ((uintptr_t)d->colstats & 15) == 0), "vcx_gemm_f16: COLSTATS needs a 16-byte aligned colstats buffer");
         VCX_REQUIRE(!geglu && !f32 && !lnf && d->M % 64 == 0 && d->N % 8 == 0,
                     "vcx_gemm_f16: COLSTATS is for fp16 outputs (no GEGLU / LNFOLD) with M %% 64 == 0 and N %% 8 == 0 (M=%d N=%d)", d->M, d->N);
         VCX_REQUIRE(d->ldcs == 0 || (d->ldcs >= d->N && d->ldcs % 2 == 0), "vcx_gemm_f16: COLSTATS ldcs (%lld) must be 0 or an even number >= N", (long long)d->ldcs);
@@ -560,79 +566,112 @@ extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
     const int tail = conv ? d->tail_k0 + d->tail_k1 : 0;
     VCX_REQUIRE(conv || (d->tail_k0 == 0 && d->tail_k1 == 0), "vcx_gemm_f16: a K tail (tail_k0 / tail_k1) belongs to a convolution (mode 1)");
     if (tail) {
-        VCX_REQUIRE(d->tail_k0 % 64 == 0 && d->tail_k1 % 64 == 0 && (d->tail_k0 == 0 || (d->tail_a0 && d->tail_lda0 >= d->tail_k0 && d->tail_lda0 % 8 == 0)) &&
-                        (d->tail_k1 == 0 || (d->tail_a1 && d->tail_lda1 >= d->tail_k1 && d->tail_lda1 % 8 == 0)) && !(d->tail_k0 == 0 && d->tail_k1 != 0),
+        VCX_REQUIRE(d->tail_k0 % 64 == 0 && d->tail_k1 % 64 == 0 && (d->tail_k0 == 0 || ((!ptrs || d->tail_a0) && d->tail_lda0 >= d->tail_k0 && d->tail_lda0 % 8 == 0)) &&
+                        (d->tail_k1 == 0 || ((!ptrs || d->tail_a1) && d->tail_lda1 >= d->tail_k1 && d->tail_lda1 % 8 == 0)) && !(d->tail_k0 == 0 && d->tail_k1 != 0),
                     "vcx_gemm_f16: K tail: tail_k %% 64 == 0, sources with tail_lda >= tail_k, tail_lda %% 8 == 0, tail_a0 first (tail=%d+%d)", d->tail_k0, d->tail_k1);
-        VCX_REQUIRE((((uintptr_t)d->tail_a0 | (uintptr_t)d->tail_a1) & 15) == 0 && !geglu && !f32 && !lnf, "vcx_gemm_f16: K tail: 16-byte aligned sources, fp16 output, no GEGLU / LNFOLD");
+        VCX_REQUIRE((!ptrs || (((uintptr_t)d->tail_a0 | (uintptr_t)d->tail_a1) & 15) == 0) && !geglu && !f32 && !lnf, "vcx_gemm_f16: K tail: 16-byte aligned sources, fp16 output, no GEGLU / LNFOLD");
     }
     // vector epilogue alignment
     if (!geglu) {
         VCX_REQUIRE(d->N < 4 || d->N % 4 != 0 || d->ldc % 4 == 0, "vcx_gemm_f16: ldc must be a multiple of 4");
         if (flags & VCX_GEMM_RESIDUAL)
-            VCX_REQUIRE(d->ldr % 4 == 0 && ((uintptr_t)d->residual & 7) == 0, "vcx_gemm_f16: residual alignment");
-        if ((flags & VCX_GEMM_BIAS_N) && d->N >= 4) VCX_REQUIRE(((uintptr_t)d->bias & 15) == 0, "vcx_gemm_f16: bias alignment");
-        if (flags & VCX_GEMM_ROWADD) VCX_REQUIRE(((uintptr_t)d->rowadd & 15) == 0 && d->N % 4 == 0, "vcx_gemm_f16: rowadd alignment");
+            VCX_REQUIRE(d->ldr % 4 == 0 && (!ptrs || ((uintptr_t)d->residual & 7) == 0), "vcx_gemm_f16: residual alignment");
+        if ((flags & VCX_GEMM_BIAS_N) && d->N >= 4) VCX_REQUIRE(!ptrs || ((uintptr_t)d->bias & 15) == 0, "vcx_gemm_f16: bias alignment");
+        if (flags & VCX_GEMM_ROWADD) VCX_REQUIRE((!ptrs || ((uintptr_t)d->rowadd & 15) == 0) && d->N % 4 == 0, "vcx_gemm_f16: rowadd alignment");
     } else {
         VCX_REQUIRE(d->ldc % 4 == 0, "vcx_gemm_f16: ldc must be a multiple of 4");
     }
-
-    GemmArgs a;
-    a.A = (const half_t*)d->A;
-    a.W = (const half_t*)d->W;
-    a.C = d->C;
-    a.bias = d->bias;
-    a.rowadd = d->rowadd;
-    a.R = (const half_t*)d->residual;
-    a.lda = d->lda;
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.ldw = d->ldw; a.ldc = d->ldc; a.ldr = d->ldr;
-    a.in_h = d->in_h; a.in_w = d->in_w; a.out_h = d->out_h; a.out_w = d->out_w;
-    a.cin = d->cin; a.kh = d->kh; a.kw = d->kw; a.stride = d->stride; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.ups = d->ups;
-    a.rowadd_div = d->rowadd_div > 0 ? d->rowadd_div : 1;
-    a.rowadd_ld = d->rowadd_ld > 0 ? d->rowadd_ld : d->N;
-    a.flags = flags;
-    a.alpha = d->alpha;
-    const bool use160 = !geglu && (d->N % 160 == 0);
-    const int bn = use160 ? 160 : 128;
-    a.tiles_m = (d->M + BM - 1) / BM;
-    a.tiles_n = (d->N + bn - 1) / bn;
-    a.m_begin = 0;
-    a.ln_stats = d->ln_stats;
-    a.ln_colsum = d->ln_colsum;
-    a.colstats = d->colstats;
-    a.ldcs = d->ldcs > 0 ? d->ldcs : d->N;
-    a.unit_rows = 0; a.units = 1; a.w_unit_stride = 0; a.bias_unit_stride = 0;
-    a.rowstats = d->rowstats; a.rowstats_eps = d->rowstats_eps;
-    a.A2 = (const half_t*)d->tail_a0; a.A3 = (const half_t*)d->tail_a1; a.lda2 = d->tail_lda0; a.lda3 = d->tail_lda1;
-    a.k2 = conv ? d->tail_k0 : 0; a.k3 = conv ? d->tail_k1 : 0; a.a2_bytes = a.a3_bytes = 0;
     if (flags & VCX_GEMM_ROWSTATS)
-        VCX_REQUIRE(d->rowstats && ((uintptr_t)d->rowstats & 7) == 0 && d->rowstats_eps >= 0.f, "vcx_gemm_f16: ROWSTATS needs an 8-byte aligned rowstats buffer and eps >= 0");
-    hipStream_t s = (hipStream_t)stream;
-    const double flops = 2.0 * d->M * (double)d->N * d->K;
-    const double bytes = 2.0 * ((double)d->M * d->K / (conv ? d->kh * d->kw : 1) + (double)d->N * d->K + (double)d->M * d->N);
-    VcxProfScope prof(VCX_FAM_GEMM, s, flops, bytes);
+        VCX_REQUIRE((!ptrs || (d->rowstats && ((uintptr_t)d->rowstats & 7) == 0)) && d->rowstats_eps >= 0.f, "vcx_gemm_f16: ROWSTATS needs an 8-byte aligned rowstats buffer and eps >= 0");
+    return VCX_OK;
+}
+
+static int validate_units(const vcx_gemm_desc* d, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, bool ptrs) {
+    VCX_REQUIRE(d != nullptr && d->struct_size == sizeof(vcx_gemm_desc), "vcx_gemm_units_f16: null descriptor or wrong struct_size");
+    VCX_REQUIRE((!ptrs || (d->A && d->W && d->C)) && d->M > 0 && d->N > 0 && d->K > 0, "vcx_gemm_units_f16: null A/W/C or empty problem");
+    VCX_REQUIRE(d->mode == 0 && !(d->flags & ~(VCX_GEMM_BIAS_N | VCX_GEMM_ROWSTATS)), "vcx_gemm_units_f16: linear layers with a per-column bias (and ROWSTATS) at most (mode %d flags 0x%x)", d->mode, d->flags);
+    VCX_REQUIRE(!(d->flags & VCX_GEMM_ROWSTATS) || ((!ptrs || (d->rowstats && ((uintptr_t)d->rowstats & 7) == 0)) && d->rowstats_eps >= 0.f), "vcx_gemm_units_f16: ROWSTATS needs an 8-byte aligned rowstats buffer and eps >= 0");
+    VCX_REQUIRE(unit_rows > 0 && d->M % unit_rows == 0, "vcx_gemm_units_f16: M (%d) must be a whole number of units of %d rows", d->M, unit_rows);
+    VCX_REQUIRE(w_unit_stride % 8 == 0 && bias_unit_stride % 4 == 0, "vcx_gemm_units_f16: unit strides must keep W 16-byte and bias 16-byte aligned");
+    VCX_REQUIRE(!ptrs || !(d->flags & VCX_GEMM_BIAS_N) || d->bias, "vcx_gemm_units_f16: bias flag without bias");
+    VCX_REQUIRE(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->ldc % 8 == 0 && (!ptrs || ((((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->C) & 15) == 0 && ((uintptr_t)d->bias & 15) == 0)),
+                "vcx_gemm_units_f16: strides must be multiples of 8, pointers 16-byte aligned");
+    return VCX_OK;
+}
+
+// The knobs a route depends on, read once per call: gemm_route itself reads no global.  VCX_GEMM_UNITS_LOOP (environment, read per call:
+// tests, A/B runs) concerns vcx_gemm_units_f16 only, so vcx_gemm_f16 does not pay for a getenv.
+struct Knobs { int dma, ws, cfg; bool units_loop; };
+static Knobs read_knobs(int unit_rows) {
+    const char* loop_env = unit_rows > 0 ? getenv("VCX_GEMM_UNITS_LOOP") : nullptr;
+    return Knobs{vcx_tune(VCX_TUNE_GEMM_DMA), vcx_tune(VCX_TUNE_GEMM_WS), vcx_tune(VCX_TUNE_GEMM_CFG), loop_env && loop_env[0] && loop_env[0] != '0'};
+}
+
+struct GemmRoute {
+    int kind;                    // VCX_ROUTE_* (include/vcx.h)
+    int epi;                     // TILED / UNITS_GROUPED: the epilogue kind plan_tiles chooses configurations by
+    unsigned long long a_bytes, w_bytes, c_bytes, r_bytes, a2_bytes, a3_bytes;      // operand / output extents (w_bytes: of ONE unit's weights)
+    char why[384];               // REFUSED: the text for vcx_last_error
+};
+static GemmRoute& take(GemmRoute& r, int kind) { r.kind = kind; return r; }
+static GemmRoute& refuse(GemmRoute& r, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(r.why, sizeof(r.why), fmt, ap);
+    va_end(ap);
+    return take(r, VCX_ROUTE_REFUSED);
+}
+
+// Which kernel takes a (validated) call: unit_rows = 0 for vcx_gemm_f16, > 0 for vcx_gemm_units_f16.  Pure: no HIP call, no global, and
+// A / W / C are never dereferenced.  Routes are tried in this order; the first that applies wins.
+static GemmRoute gemm_route(const vcx_gemm_desc& d, int unit_rows, const Knobs& k) {
+    GemmRoute r;
+    r.why[0] = 0;
+    const int flags = d.flags;
+    const bool conv = d.mode == 1, geglu = flags & VCX_GEMM_GEGLU, f32 = flags & VCX_GEMM_OUT_F32;
+    const int lnf = (flags & VCX_GEMM_LNFOLD) ? 1 : (flags & VCX_GEMM_LNFOLD_T) ? 2 : 0;
+    const int k2 = conv ? d.tail_k0 : 0, k3 = conv ? d.tail_k1 : 0;
+    r.epi = geglu ? (conv ? EPI_GEGLU_ONLY128 : EPI_GEGLU) : ((f32 || lnf == 2) ? EPI_PLAIN_ONLY128 : EPI_PLAIN);
     // DMA kernel (gemm_dma.hip) whenever its addressing assumptions hold; the register-staged kernel otherwise.
-    const bool dma_enabled = vcx_tune(VCX_TUNE_GEMM_DMA) != 0;
     const unsigned long long lim = 0xFFFF0000ull;
-    const unsigned long long a_ext = conv ? 2ull * (unsigned long long)(d->M / (d->out_h * d->out_w)) * d->in_h * d->in_w * d->lda
-                                          : 2ull * ((unsigned long long)(d->M - 1) * d->lda + d->K);
-    const unsigned long long w_ext = 2ull * ((unsigned long long)(d->N - 1) * d->ldw + d->K);
+    r.a_bytes = conv ? 2ull * (unsigned long long)(d.M / (d.out_h * d.out_w)) * d.in_h * d.in_w * d.lda
+                     : 2ull * ((unsigned long long)(d.M - 1) * d.lda + d.K);
+    r.w_bytes = 2ull * ((unsigned long long)(d.N - 1) * d.ldw + d.K);
     // output / residual: 32-bit byte offsets up to 256 rows past the end must not wrap (rows >= M are dropped by the
     // descriptor's range check, which only works if their offset is still >= the extent)
     const unsigned long long esz = f32 ? 4 : 2;
-    const unsigned long long c_ext = esz * ((unsigned long long)(d->M - 1) * d->ldc + (geglu ? d->N / 2 : d->N));
-    const unsigned long long r_ext = d->residual ? 2ull * ((unsigned long long)(d->M - 1) * d->ldr + d->N) : 0;
-    const bool out_ok = esz * (unsigned long long)(d->M + 256) * d->ldc < lim && 2ull * (unsigned long long)(d->M + 256) * d->ldr < lim;
-    const unsigned long long a2_ext = a.k2 ? 2ull * ((unsigned long long)(d->M - 1) * d->tail_lda0 + a.k2) : 0;
-    const unsigned long long a3_ext = a.k3 ? 2ull * ((unsigned long long)(d->M - 1) * d->tail_lda1 + a.k3) : 0;
-    const bool dma_ok = dma_enabled && d->K % 64 == 0 && d->N % ((geglu || f32) ? 4 : 8) == 0 && (!conv || d->cin % 64 == 0) &&   // fp16 output goes out in dwordx4 pieces of 8 columns
-                        a_ext < lim && w_ext < lim && (!geglu || d->N >= 64) && out_ok && a2_ext < lim && a3_ext < lim;
-    a.a2_bytes = (unsigned)a2_ext; a.a3_bytes = (unsigned)a3_ext;
-    VCX_REQUIRE(!tail || dma_ok, "vcx_gemm_f16: a K tail needs the DMA kernel (cin %% 64 == 0, K %% 64 == 0, N %% 8 == 0, extents < 4 GiB); cin=%d K=%d N=%d", d->cin, d->K, d->N);
-    a.a_bytes = (unsigned)a_ext;
-    a.w_bytes = (unsigned)w_ext;
-    a.c_bytes = (unsigned)c_ext;
-    a.r_bytes = (unsigned)r_ext;
+    r.c_bytes = esz * ((unsigned long long)(d.M - 1) * d.ldc + (geglu ? d.N / 2 : d.N));
+    r.r_bytes = d.residual ? 2ull * ((unsigned long long)(d.M - 1) * d.ldr + d.N) : 0;
+    const bool c_ok = esz * (unsigned long long)(d.M + 256) * d.ldc < lim;
+    const bool out_ok = c_ok && 2ull * (unsigned long long)(d.M + 256) * d.ldr < lim;
+    r.a2_bytes = k2 ? 2ull * ((unsigned long long)(d.M - 1) * d.tail_lda0 + k2) : 0;
+    r.a3_bytes = k3 ? 2ull * ((unsigned long long)(d.M - 1) * d.tail_lda1 + k3) : 0;
+    const bool dma_ok = k.dma != 0 && d.K % 64 == 0 && d.N % ((geglu || f32) ? 4 : 8) == 0 && (!conv || d.cin % 64 == 0) &&   // fp16 output goes out in dwordx4 pieces of 8 columns
+                        r.a_bytes < lim && r.w_bytes < lim && (!geglu || d.N >= 64) && out_ok && r.a2_bytes < lim && r.a3_bytes < lim;
+    const bool force_cfg_unset = k.cfg < 0;      // a forced tile configuration (A/B tools, soak) means the tiled engine
+
+    // ---- vcx_gemm_units_f16: one weight / bias set per unit of rows (the routes and their why: include/vcx.h).  The per-unit form of
+    // the tiled engine gives the bits of the unit-by-unit loop; units that vcx_gemm_f16 would give to its weight-stationary kernel stay
+    // on the loop, so that the bits stay those of the loop whatever that kernel does.  ONE unit is vcx_gemm_f16's call, with ROWSTATS too.
+    const int units = unit_rows > 0 ? d.M / unit_rows : 1;
+    if (units > 1) {
+        if (d.K == 320 && d.N == 320 && unit_rows % 32 == 0 && unit_rows >= 1024 && d.M >= 8192 && r.a_bytes < lim && c_ok && units <= 65535 &&
+            k.dma != 0 && k.ws != 0 && force_cfg_unset)
+            return take(r, VCX_ROUTE_UNITS_WS320);
+        if (flags & VCX_GEMM_ROWSTATS)
+            return refuse(r, "vcx_gemm_units_f16: ROWSTATS needs the one-launch weight-stationary form (N = K = 320, unit_rows %% 32 == 0, >= 1024, M >= 8192); M=%d N=%d K=%d unit_rows=%d",
+                          d.M, d.N, d.K, unit_rows);
+        if (units <= 65535 && d.K % 64 == 0 && d.N % 8 == 0 && r.a_bytes < lim && r.w_bytes < lim && c_ok && k.dma != 0 && k.cfg <= 5 && !k.units_loop) {
+            vcx_gemm_desc one = d;
+            one.M = unit_rows;
+            if (gemm_route(one, 0, k).kind != VCX_ROUTE_WS320) return take(r, VCX_ROUTE_UNITS_GROUPED);
+        }
+        return take(r, VCX_ROUTE_UNITS_LOOP);
+    }
+
+    // ---- vcx_gemm_f16
+    if ((k2 || k3) && !dma_ok)
+        return refuse(r, "vcx_gemm_f16: a K tail needs the DMA kernel (cin %% 64 == 0, K %% 64 == 0, N %% 8 == 0, extents < 4 GiB); cin=%d K=%d N=%d", d.cin, d.K, d.N);
     // Weight-stationary kernel (gemm_ws.hip) for the memory-bound K = 320 linear layers of level 0 (N = 320, 640, 960): the weight stays
     // in the register file, only the activation rows stream.  From 128 tiles of 64 rows on (below that the tiled engine's small
     // configuration is as good).  Not the LayerNorm-folded projections: a lean folded epilogue was built and measured level with the
@@ -642,9 +681,9 @@ extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
     // cross-XCD streams on the spare CUs).  For EVERY M: its
     // bias rides in the accumulators, so its last bits differ from the tiled engine's, and a row's bits must not depend on how many
     // rows the call has (B = 2 equals two B = 1 forwards bit for bit).  Beyond ten column blocks per row stream the tiled engine wins.
-    if (dma_ok && !conv && geglu && !f32 && !lnf && d->K == 320 && d->N % 256 == 0 && d->N <= 2560 && !(flags & ~(VCX_GEMM_GEGLU | VCX_GEMM_BIAS_N)) &&
-        d->alpha == 1.0f && ((vcx_tune(VCX_TUNE_GEMM_WS) | 2) == 3 || vcx_tune(VCX_TUNE_GEMM_WS) == 5) && force_cfg_unset())
-        return launch_ws320_geglu(a, s);
+    if (dma_ok && !conv && geglu && !f32 && !lnf && d.K == 320 && d.N % 256 == 0 && d.N <= 2560 && !(flags & ~(VCX_GEMM_GEGLU | VCX_GEMM_BIAS_N)) &&
+        d.alpha == 1.0f && ((k.ws | 2) == 3 || k.ws == 5) && force_cfg_unset)
+        return take(r, VCX_ROUTE_WS320_GEGLU);
     // ... and for the LayerNorm-folded projections of level 0 (q | k | v of the spatial self-attention, N = 960, and the 640-column ones) on
     // the same skeleton with a lighter epilogue (gemm_ws320_lnf_kernel; knob GEMM_WS = 4: everything weight-stationary but this).  For
     // every M, like the GEGLU kernel: its bits differ from the tiled engine's (32x32x16 sums K in another order).
@@ -652,145 +691,148 @@ extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
     // least three quarters full - N = 512 (-15 %), 960 (-3 %), 1280 (-10 %); 640 (a half-empty third block) +5 %, 1920 level.  The kernel
     // is bound by what a CU can pull through LDS-DMA (every column block streams all activation rows), not by its matrix work
     // (profiles/r05an_ws_lnf_ablate.txt).  Knob GEMM_WS = 5 sends every N % 64 == 0 up to 2560 there (tests).
-    {
-        const int wsk = vcx_tune(VCX_TUNE_GEMM_WS);
-        const int pad = (d->N + 255) / 256 * 256 - d->N;
-        if (dma_ok && !conv && !geglu && !f32 && lnf == 1 && d->K == 320 && d->N % 64 == 0 && d->N <= 2560 &&
-            ((wsk >= 1 && wsk <= 3 && pad <= 64 && d->N >= 512 && d->N <= 1536) || wsk == 5) &&
-            !(flags & ~(VCX_GEMM_LNFOLD | VCX_GEMM_BIAS_N)) && 8ull * (unsigned long long)d->M < lim && force_cfg_unset())
-            return launch_ws320_lnfold(a, s);
-    }
+    const int pad = (d.N + 255) / 256 * 256 - d.N;
+    if (dma_ok && !conv && !geglu && !f32 && lnf == 1 && d.K == 320 && d.N % 64 == 0 && d.N <= 2560 &&
+        ((k.ws >= 1 && k.ws <= 3 && pad <= 64 && d.N >= 512 && d.N <= 1536) || k.ws == 5) &&
+        !(flags & ~(VCX_GEMM_LNFOLD | VCX_GEMM_BIAS_N)) && 8ull * (unsigned long long)d.M < lim && force_cfg_unset)
+        return take(r, VCX_ROUTE_WS320_LNF);
     // ROWSTATS (LayerNorm statistics of the output rows) exists where one block owns whole rows: the pipelined weight-stationary kernel, N = 320
-    const bool rs_ok = !(flags & VCX_GEMM_ROWSTATS) || (d->N == 320 && !(flags & ~(VCX_GEMM_ROWSTATS | VCX_GEMM_BIAS_N | VCX_GEMM_RESIDUAL)) && 8ull * (unsigned long long)d->M < lim);
-    if (dma_ok && !conv && !geglu && !f32 && !lnf && d->K == 320 && d->N % 320 == 0 && d->N <= 1280 && d->M >= 8192 && rs_ok &&
-        !(flags & VCX_GEMM_BIAS_M) && vcx_tune(VCX_TUNE_GEMM_WS) != 0 && force_cfg_unset())
-        return launch_ws320(a, s);
-    VCX_REQUIRE(!(flags & VCX_GEMM_ROWSTATS), "vcx_gemm_f16: ROWSTATS needs the weight-stationary kernel (linear, N = K = 320, M >= 8192, BIAS_N / RESIDUAL at most, knob GEMM_WS on); M=%d N=%d K=%d flags=0x%x",
-                d->M, d->N, d->K, flags);
+    const bool rs_ok = !(flags & VCX_GEMM_ROWSTATS) || (d.N == 320 && !(flags & ~(VCX_GEMM_ROWSTATS | VCX_GEMM_BIAS_N | VCX_GEMM_RESIDUAL)) && 8ull * (unsigned long long)d.M < lim);
+    if (dma_ok && !conv && !geglu && !f32 && !lnf && d.K == 320 && d.N % 320 == 0 && d.N <= 1280 && d.M >= 8192 && rs_ok &&
+        !(flags & VCX_GEMM_BIAS_M) && k.ws != 0 && force_cfg_unset)
+        return take(r, VCX_ROUTE_WS320);
+    if (flags & VCX_GEMM_ROWSTATS)
+        return refuse(r, "vcx_gemm_f16: ROWSTATS needs the weight-stationary kernel (linear, N = K = 320, M >= 8192, BIAS_N / RESIDUAL at most, knob GEMM_WS on); M=%d N=%d K=%d flags=0x%x",
+                      d.M, d.N, d.K, flags);
     if (dma_ok) {
-        // tile choice: plan_tiles above; a forced configuration (knob GEMM_CFG >= 0; tools/gemm_quick.py, tests) replaces the plan
-        const int force = vcx_tune(VCX_TUNE_GEMM_CFG);      // -1 in production
-        const int ncu = persistent_grid(1 << 30, 1);
-        const int epi = geglu ? (conv ? EPI_GEGLU_ONLY128 : EPI_GEGLU) : ((f32 || lnf == 2) ? EPI_PLAIN_ONLY128 : EPI_PLAIN);
-        TilePlan plan;
-        if (force >= 0 && !(geglu && (force == 1 || force == 3))) {
-            VCX_REQUIRE(force <= 6, "vcx_gemm_f16: unknown tile configuration %d (knob GEMM_CFG)", force);
-            plan = forced_plan(d->M, d->N, force, geglu, ncu);
-        } else if (force >= 0) {      // (a forced 160-column configuration has no GEGLU epilogue: the rule of rounds 1-6, as before)
-            int cfg = 0;
-            if ((d->N % 256 == 0 || d->N >= 1024) && (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) >= 384) cfg = 2;
-            plan = forced_plan(d->M, d->N, cfg, geglu, ncu);
-        } else {
-            plan = plan_tiles(d->M, d->N, d->K, epi, ncu);
-        }
-        const bool trace = getenv("VCX_GEMM_PLAN_TRACE") != nullptr;      // read per call: tools/gemm_cfg_scan.py and the tests switch it on around single calls
-        for (int i = 0; i < plan.n; ++i) {
-            const TileSeg& g = plan.seg[i];
-            const TileCost& t = TILE_COST[g.cfg];
-            if (trace) fprintf(stderr, "[vcx] gemm plan M=%d N=%d K=%d seg %d/%d: cfg %d rows %d+%d grid %d\n", d->M, d->N, d->K, i + 1, plan.n, g.cfg, g.m_begin, g.rows, g.grid);
-            GemmArgs c = a;
-            c.m_begin = g.m_begin;
-            c.M = i + 1 < plan.n ? g.m_begin + g.rows : d->M;      // rows >= M are dropped: the first segment ends where the second begins
-            c.tiles_m = (g.rows + t.tbm - 1) / t.tbm;
-            c.tiles_n = (d->N + t.tbn - 1) / t.tbn;
-            const int rc = launch_dma(c, g.cfg, conv, geglu, f32, s, g.grid);      // the grid the plan priced (and the trace prints) is the grid that runs
-            if (rc) return rc;
-        }
-        return VCX_OK;
+        if (k.cfg > 6) return refuse(r, "vcx_gemm_f16: unknown tile configuration %d (knob GEMM_CFG)", k.cfg);
+        return take(r, VCX_ROUTE_TILED);
     }
-    VCX_REQUIRE(!(flags & VCX_GEMM_COLSTATS), "vcx_gemm_f16: COLSTATS needs the DMA kernel (K / cin %% 64 == 0, extents < 4 GiB); K=%d cin=%d", d->K, d->cin);
-    VCX_REQUIRE(!lnf, "vcx_gemm_f16: LNFOLD needs the DMA kernel (K %% 64 == 0, N %% 8 == 0, extents < 4 GiB); K=%d N=%d", d->K, d->N);
-    return use160 ? dispatch<160>(a, conv, geglu, f32, s) : dispatch<128>(a, conv, geglu, f32, s);
+    if (flags & VCX_GEMM_COLSTATS)
+        return refuse(r, "vcx_gemm_f16: COLSTATS needs the DMA kernel (K / cin %% 64 == 0, extents < 4 GiB); K=%d cin=%d", d.K, d.cin);
+    if (lnf) return refuse(r, "vcx_gemm_f16: LNFOLD needs the DMA kernel (K %% 64 == 0, N %% 8 == 0, extents < 4 GiB); K=%d N=%d", d.K, d.N);
+    return take(r, VCX_ROUTE_REGISTER);
 }
 
-// One weight / bias set per unit of rows (include/vcx.h).  Three routes, the first that applies:
-//  1. N = K = 320 (the level-0 projections): ONE launch of the weight-stationary kernel - a block keeps its unit's weights in registers anyway.
-//  2. the tiled engine's per-unit form (gemm_dma.hip, UNITS), ONE plan over units x tiles-per-unit tiles and at most two launches:
-//     units > 1, K % 64 == 0, N % 8 == 0, the 32-bit extents of the whole call (`dma_ok`'s rule, output offsets up to 256 rows past the
-//     end), units <= 65535, knob GEMM_DMA on.  The same bits as route 3 - the tile shape does not enter a row's arithmetic - so the
-//     choice between the two is a matter of cost alone.  Left on route 3: units that vcx_gemm_f16 would give to its weight-stationary
-//     kernel (K = 320, N = 320 ... 1280, unit_rows >= 8192), so that the bits stay those of the loop whatever that kernel does; a forced
-//     GEMM_CFG 6 (the GEGLU configuration); VCX_GEMM_UNITS_LOOP=1 (read per call: tests, A/B runs).
-//  3. unit by unit through vcx_gemm_f16.
-// ONE unit (a single video, B = 1) goes to vcx_gemm_f16 with ROWSTATS too: the same pipelined weight-stationary kernel and epilogue, so its
-// rows and statistics are the bits of the same video inside a batch (B = 2); that kernel's own grid measured faster than the one-launch
-// form's for one unit.
-extern "C" int vcx_gemm_units_f16(const vcx_gemm_desc* d, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, void* stream) {
-    VCX_REQUIRE(d != nullptr && d->struct_size == sizeof(vcx_gemm_desc), "vcx_gemm_units_f16: null descriptor or wrong struct_size");
-    VCX_REQUIRE(d->A && d->W && d->C && d->M > 0 && d->N > 0 && d->K > 0, "vcx_gemm_units_f16: null A/W/C or empty problem");
-    VCX_REQUIRE(d->mode == 0 && !(d->flags & ~(VCX_GEMM_BIAS_N | VCX_GEMM_ROWSTATS)), "vcx_gemm_units_f16: linear layers with a per-column bias (and ROWSTATS) at most (mode %d flags 0x%x)", d->mode, d->flags);
-    VCX_REQUIRE(!(d->flags & VCX_GEMM_ROWSTATS) || (d->rowstats && ((uintptr_t)d->rowstats & 7) == 0 && d->rowstats_eps >= 0.f), "vcx_gemm_units_f16: ROWSTATS needs an 8-byte aligned rowstats buffer and eps >= 0");
-    VCX_REQUIRE(unit_rows > 0 && d->M % unit_rows == 0, "vcx_gemm_units_f16: M (%d) must be a whole number of units of %d rows", d->M, unit_rows);
-    VCX_REQUIRE(w_unit_stride % 8 == 0 && bias_unit_stride % 4 == 0, "vcx_gemm_units_f16: unit strides must keep W 16-byte and bias 16-byte aligned");
-    VCX_REQUIRE(!(d->flags & VCX_GEMM_BIAS_N) || d->bias, "vcx_gemm_units_f16: bias flag without bias");
-    VCX_REQUIRE(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->ldc % 8 == 0 && (((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->C) & 15) == 0 && ((uintptr_t)d->bias & 15) == 0,
-                "vcx_gemm_units_f16: strides must be multiples of 8, pointers 16-byte aligned");
-    const int units = d->M / unit_rows;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned long long lim = 0xFFFF0000ull;
-    const unsigned long long a_ext = 2ull * ((unsigned long long)(d->M - 1) * d->lda + d->K), c_ext = 2ull * ((unsigned long long)(d->M - 1) * d->ldc + d->N);
-    if (units > 1 && d->K == 320 && d->N == 320 && unit_rows % 32 == 0 && unit_rows >= 1024 && d->M >= 8192 && a_ext < lim &&
-        2ull * (unsigned long long)(d->M + 256) * d->ldc < lim && units <= 65535 && vcx_tune(VCX_TUNE_GEMM_DMA) != 0 && vcx_tune(VCX_TUNE_GEMM_WS) != 0 &&
-        force_cfg_unset()) {
-        GemmArgs a{};
-        a.A = (const half_t*)d->A; a.W = (const half_t*)d->W; a.C = d->C; a.bias = d->bias;
-        a.lda = d->lda; a.M = d->M; a.N = d->N; a.K = d->K; a.ldw = d->ldw; a.ldc = d->ldc; a.ldr = 0;
-        a.rowadd_div = 1; a.rowadd_ld = d->N; a.flags = d->flags; a.alpha = d->alpha; a.m_begin = 0;
-        a.ldcs = d->N;
-        a.a_bytes = (unsigned)a_ext; a.c_bytes = (unsigned)c_ext; a.w_bytes = 0; a.r_bytes = 0;
-        a.unit_rows = unit_rows; a.units = units; a.w_unit_stride = w_unit_stride; a.bias_unit_stride = bias_unit_stride;
-        a.rowstats = d->rowstats; a.rowstats_eps = d->rowstats_eps;
-        VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * d->M * (double)d->N * d->K, 2.0 * ((double)d->M * d->K + (double)units * d->N * d->K + (double)d->M * d->N));
-        return launch_ws320_units(a, s);
-    }
-    VCX_REQUIRE(units == 1 || !(d->flags & VCX_GEMM_ROWSTATS), "vcx_gemm_units_f16: ROWSTATS needs the one-launch weight-stationary form (N = K = 320, unit_rows %% 32 == 0, >= 1024, M >= 8192); M=%d N=%d K=%d unit_rows=%d",
-                d->M, d->N, d->K, unit_rows);
-    const int force = vcx_tune(VCX_TUNE_GEMM_CFG);
-    const char* loop_env = getenv("VCX_GEMM_UNITS_LOOP");
-    const unsigned long long w_ext = 2ull * ((unsigned long long)(d->N - 1) * d->ldw + d->K);      // of ONE unit: a tile's descriptor starts at its unit's weights
-    const bool ws_per_unit = d->K == 320 && d->N % 320 == 0 && d->N <= 1280 && unit_rows >= 8192 && vcx_tune(VCX_TUNE_GEMM_WS) != 0 && force < 0;
-    if (units > 1 && units <= 65535 && d->K % 64 == 0 && d->N % 8 == 0 && a_ext < lim && w_ext < lim && 2ull * (unsigned long long)(d->M + 256) * d->ldc < lim &&
-        vcx_tune(VCX_TUNE_GEMM_DMA) != 0 && force <= 5 && !ws_per_unit && !(loop_env && loop_env[0] && loop_env[0] != '0')) {
-        GemmArgs a{};
-        a.A = (const half_t*)d->A; a.W = (const half_t*)d->W; a.C = d->C; a.bias = d->bias;
-        a.lda = d->lda; a.M = d->M; a.N = d->N; a.K = d->K; a.ldw = d->ldw; a.ldc = d->ldc; a.ldr = 0;
-        a.rowadd_div = 1; a.rowadd_ld = d->N; a.flags = d->flags; a.alpha = d->alpha; a.m_begin = 0;
-        a.ldcs = d->N;
-        a.a_bytes = (unsigned)a_ext; a.c_bytes = (unsigned)c_ext; a.w_bytes = (unsigned)w_ext; a.r_bytes = 0;
-        a.unit_rows = unit_rows; a.units = units; a.w_unit_stride = w_unit_stride; a.bias_unit_stride = bias_unit_stride;
-        VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * d->M * (double)d->N * d->K, 2.0 * ((double)d->M * d->K + (double)units * d->N * d->K + (double)d->M * d->N));
-        const int ncu = persistent_grid(1 << 30, 1);
-        TilePlan plan;
-        if (force >= 0) plan = TilePlan{1, {plan_seg(force, 0, d->M, d->N, ncu, unit_rows), TileSeg{0, 0, 0, 0}}, 0.f};      // a forced configuration: the whole call on it
-        else plan = plan_tiles(d->M, d->N, d->K, EPI_PLAIN, ncu, unit_rows);
-        const bool trace = getenv("VCX_GEMM_PLAN_TRACE") != nullptr;
-        for (int i = 0; i < plan.n; ++i) {
-            const TileSeg& g = plan.seg[i];
-            const TileCost& t = TILE_COST[g.cfg];
-            const int u0 = g.m_begin / unit_rows, nu = g.rows / unit_rows;      // segments begin and end at unit boundaries
-            if (trace) fprintf(stderr, "[vcx] gemm plan M=%d N=%d K=%d seg %d/%d: cfg %d rows %d+%d grid %d units %d unit_rows %d\n", d->M, d->N, d->K, i + 1, plan.n, g.cfg, g.m_begin, g.rows, g.grid, nu, unit_rows);
-            GemmArgs c = a;
-            c.m_begin = g.m_begin;
-            c.M = g.m_begin + g.rows;
-            c.units = nu;
-            c.W = a.W + (int64_t)u0 * w_unit_stride;
-            if (a.bias) c.bias = a.bias + (int64_t)u0 * bias_unit_stride;
-            c.tiles_m = nu * ((unit_rows + t.tbm - 1) / t.tbm);
-            c.tiles_n = (d->N + t.tbn - 1) / t.tbn;
-            const int rc = launch_dma(c, g.cfg, false, false, false, s, g.grid);
-            if (rc) return rc;
+// the kernels' argument block of a call (unit_rows = 0: one weight set); a launch of the tile plan then narrows its copy to its rows
+static GemmArgs fill_args(const vcx_gemm_desc& d, const GemmRoute& r, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride) {
+    const bool conv = d.mode == 1;
+    GemmArgs a;
+    a.A = (const half_t*)d.A; a.W = (const half_t*)d.W; a.C = d.C; a.bias = d.bias; a.rowadd = d.rowadd; a.R = (const half_t*)d.residual;
+    a.lda = d.lda; a.M = d.M; a.N = d.N; a.K = d.K; a.ldw = d.ldw; a.ldc = d.ldc; a.ldr = d.ldr;
+    a.in_h = d.in_h; a.in_w = d.in_w; a.out_h = d.out_h; a.out_w = d.out_w;
+    a.cin = d.cin; a.kh = d.kh; a.kw = d.kw; a.stride = d.stride; a.pad_h = d.pad_h; a.pad_w = d.pad_w; a.ups = d.ups;
+    a.rowadd_div = d.rowadd_div > 0 ? d.rowadd_div : 1;
+    a.rowadd_ld = d.rowadd_ld > 0 ? d.rowadd_ld : d.N;
+    a.flags = d.flags; a.alpha = d.alpha; a.m_begin = 0;
+    const int bn = (!(d.flags & VCX_GEMM_GEGLU) && d.N % 160 == 0) ? 160 : 128;      // the register-staged kernel's tiles; every other launcher sets its own
+    a.tiles_m = (d.M + BM - 1) / BM;
+    a.tiles_n = (d.N + bn - 1) / bn;
+    a.ln_stats = d.ln_stats; a.ln_colsum = d.ln_colsum; a.colstats = d.colstats; a.ldcs = d.ldcs > 0 ? d.ldcs : d.N;
+    a.unit_rows = unit_rows; a.units = unit_rows > 0 ? d.M / unit_rows : 1; a.w_unit_stride = w_unit_stride; a.bias_unit_stride = bias_unit_stride;
+    a.rowstats = d.rowstats; a.rowstats_eps = d.rowstats_eps;
+    a.A2 = (const half_t*)d.tail_a0; a.A3 = (const half_t*)d.tail_a1; a.lda2 = d.tail_lda0; a.lda3 = d.tail_lda1;
+    a.k2 = conv ? d.tail_k0 : 0; a.k3 = conv ? d.tail_k1 : 0;
+    a.a_bytes = (unsigned)r.a_bytes; a.w_bytes = (unsigned)r.w_bytes; a.c_bytes = (unsigned)r.c_bytes; a.r_bytes = (unsigned)r.r_bytes;
+    a.a2_bytes = (unsigned)r.a2_bytes; a.a3_bytes = (unsigned)r.a3_bytes;
+    return a;
+}
+
+// tile choice of the tiled engine: plan_tiles above; a forced configuration (knob GEMM_CFG >= 0; tools/gemm_quick.py, tests) replaces the plan
+static TilePlan tile_plan(const vcx_gemm_desc& d, const GemmRoute& r, int force, int unit_rows) {
+    const int ncu = persistent_grid(1 << 30, 1);
+    const bool geglu = d.flags & VCX_GEMM_GEGLU;
+    if (force < 0) return plan_tiles(d.M, d.N, d.K, r.epi, ncu, unit_rows);
+    if (unit_rows > 0) return TilePlan{1, {plan_seg(force, 0, d.M, d.N, ncu, unit_rows), TileSeg{0, 0, 0, 0}}, 0.f};      // the per-unit form: the whole call on it
+    if (!(geglu && (force == 1 || force == 3))) return forced_plan(d.M, d.N, force, geglu, ncu);
+    int cfg = 0;      // (a forced 160-column configuration has no GEGLU epilogue: the rule of rounds 1-6, as before)
+    if ((d.N % 256 == 0 || d.N >= 1024) && (long long)((d.M + 255) / 256) * ((d.N + 255) / 256) >= 384) cfg = 2;
+    return forced_plan(d.M, d.N, cfg, geglu, ncu);
+}
+
+// the launches of a plan, one per segment.  Per-unit form (a.unit_rows > 0): segments begin and end at unit boundaries, and a launch
+// starts at its first unit's weights
+static int run_plan(const GemmArgs& a, const TilePlan& plan, bool conv, hipStream_t s) {
+    const bool trace = getenv("VCX_GEMM_PLAN_TRACE") != nullptr;      // read per call: tools/gemm_cfg_scan.py and the tests switch it on around single calls
+    for (int i = 0; i < plan.n; ++i) {
+        const TileSeg& g = plan.seg[i];
+        const TileCost& t = TILE_COST[g.cfg];
+        const int u0 = a.unit_rows > 0 ? g.m_begin / a.unit_rows : 0, nu = a.unit_rows > 0 ? g.rows / a.unit_rows : 0;
+        if (trace) {
+            char per_unit[64] = "";
+            if (a.unit_rows > 0) snprintf(per_unit, sizeof(per_unit), " units %d unit_rows %d", nu, a.unit_rows);
+            fprintf(stderr, "[vcx] gemm plan M=%d N=%d K=%d seg %d/%d: cfg %d rows %d+%d grid %d%s\n", a.M, a.N, a.K, i + 1, plan.n, g.cfg, g.m_begin, g.rows, g.grid, per_unit);
         }
-        return VCX_OK;
-    }
-    for (int u = 0; u < units; ++u) {
-        vcx_gemm_desc du = *d;
-        du.A = (const half_t*)d->A + (int64_t)u * unit_rows * d->lda;
-        du.C = (half_t*)d->C + (int64_t)u * unit_rows * d->ldc;
-        du.W = (const half_t*)d->W + (int64_t)u * w_unit_stride;
-        if (d->bias) du.bias = d->bias + (int64_t)u * bias_unit_stride;
-        du.M = unit_rows;
-        const int rc = vcx_gemm_f16(&du, stream);
+        GemmArgs c = a;
+        c.m_begin = g.m_begin;
+        c.M = g.m_begin + g.rows;      // rows >= M are dropped: the first segment ends where the second begins
+        c.tiles_m = a.unit_rows > 0 ? nu * ((a.unit_rows + t.tbm - 1) / t.tbm) : (g.rows + t.tbm - 1) / t.tbm;
+        c.tiles_n = (a.N + t.tbn - 1) / t.tbn;
+        if (a.unit_rows > 0) {
+            c.units = nu;
+            c.W = a.W + (int64_t)u0 * a.w_unit_stride;
+            if (a.bias) c.bias = a.bias + (int64_t)u0 * a.bias_unit_stride;
+        }
+        const int rc = launch_dma(c, g.cfg, conv, a.flags & VCX_GEMM_GEGLU, a.flags & VCX_GEMM_OUT_F32, s, g.grid);      // the grid the plan priced (and the trace prints) is the grid that runs
         if (rc) return rc;
     }
     return VCX_OK;
+}
+
+// the launch(es) of a routed call.  Unit by unit (UNITS_LOOP, or the single unit that is vcx_gemm_f16's call): each unit is validated
+// and routed as the call of its own that it is
+static int run(const vcx_gemm_desc& d, const GemmRoute& r, const Knobs& k, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, void* stream) {
+    if (r.kind == VCX_ROUTE_REFUSED) {
+        vcx_set_error("%s", r.why);
+        return VCX_EINVAL;
+    }
+    if (unit_rows > 0 && r.kind != VCX_ROUTE_UNITS_WS320 && r.kind != VCX_ROUTE_UNITS_GROUPED) {
+        for (int u = 0; u < d.M / unit_rows; ++u) {
+            vcx_gemm_desc du = d;
+            du.A = (const half_t*)d.A + (int64_t)u * unit_rows * d.lda;
+            du.C = (half_t*)d.C + (int64_t)u * unit_rows * d.ldc;
+            du.W = (const half_t*)d.W + (int64_t)u * w_unit_stride;
+            if (d.bias) du.bias = d.bias + (int64_t)u * bias_unit_stride;
+            du.M = unit_rows;
+            const int rc = vcx_gemm_f16(&du, stream);
+            if (rc) return rc;
+        }
+        return VCX_OK;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const bool conv = d.mode == 1, geglu = d.flags & VCX_GEMM_GEGLU, f32 = d.flags & VCX_GEMM_OUT_F32;
+    GemmArgs a = fill_args(d, r, unit_rows, w_unit_stride, bias_unit_stride);
+    const double flops = 2.0 * d.M * (double)d.N * d.K;
+    const double bytes = 2.0 * ((double)d.M * d.K / (conv ? d.kh * d.kw : 1) + (double)a.units * d.N * d.K + (double)d.M * d.N);
+    VcxProfScope prof(VCX_FAM_GEMM, s, flops, bytes);
+    switch (r.kind) {
+    case VCX_ROUTE_WS320_GEGLU: return launch_ws320_geglu(a, s);
+    case VCX_ROUTE_WS320_LNF: return launch_ws320_lnfold(a, s);
+    case VCX_ROUTE_WS320: return launch_ws320(a, s);
+    case VCX_ROUTE_UNITS_WS320: return launch_ws320_units(a, s);
+    case VCX_ROUTE_TILED:
+    case VCX_ROUTE_UNITS_GROUPED: return run_plan(a, tile_plan(d, r, k.cfg, unit_rows), conv, s);
+    default: return !geglu && d.N % 160 == 0 ? dispatch<160>(a, conv, geglu, f32, s) : dispatch<128>(a, conv, geglu, f32, s);
+    }
+}
+
+extern "C" int vcx_gemm_f16(const vcx_gemm_desc* d, void* stream) {
+    if (const int rc = validate(d, true)) return rc;
+    const Knobs k = read_knobs(0);
+    return run(*d, gemm_route(*d, 0, k), k, 0, 0, 0, stream);
+}
+
+extern "C" int vcx_gemm_units_f16(const vcx_gemm_desc* d, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride, void* stream) {
+    if (const int rc = validate_units(d, unit_rows, w_unit_stride, bias_unit_stride, true)) return rc;
+    const Knobs k = read_knobs(unit_rows);
+    return run(*d, gemm_route(*d, unit_rows, k), k, unit_rows, w_unit_stride, bias_unit_stride, stream);
+}
+
+// the route the launchers above would take (include/vcx.h): the same validate + gemm_route, without the pointer checks and without a device
+extern "C" int vcx_gemm_route(const vcx_gemm_desc* d, int unit_rows) {
+    VCX_REQUIRE(unit_rows >= 0, "vcx_gemm_route: unit_rows %d (0 = vcx_gemm_f16, > 0 = vcx_gemm_units_f16)", unit_rows);
+    if (const int rc = unit_rows > 0 ? validate_units(d, unit_rows, 0, 0, false) : validate(d, false)) return rc;
+    const GemmRoute r = gemm_route(*d, unit_rows, read_knobs(unit_rows));
+    if (r.kind == VCX_ROUTE_REFUSED) vcx_set_error("%s", r.why);
+    return r.kind;
 }

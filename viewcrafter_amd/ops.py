@@ -14,7 +14,7 @@ import os
 import torch
 
 from ._lib import (GEMM_BIAS_M, GEMM_BIAS_N, GEMM_COLSTATS, GEMM_CONV_SLABK, GEMM_GEGLU, GEMM_LNFOLD, GEMM_LNFOLD_T, GEMM_OUT_F32, GEMM_RESIDUAL, GEMM_ROWADD, GEMM_ROWSTATS, PROF_FAMILIES,
-                   TUNE, GemmDesc, VcxError, check, lib)
+                   ROUTE_UNITS_GROUPED, ROUTE_UNITS_LOOP, ROUTE_UNITS_WS320, TUNE, GemmDesc, VcxError, check, lib)
 from .packing import conv_slab_major
 
 _f16 = torch.float16
@@ -55,6 +55,38 @@ def require_gpu():
 # ------------------------------------------------------------------------------------------
 # GEMM / convolution
 # ------------------------------------------------------------------------------------------
+def _gemm_desc(M, N, K, lda, ldc, *, ldw=None, ldr=0, conv=None, tail=(), flags=0, alpha=1.0):
+    """The pointer-free part of a vcx_gemm_desc: shape, strides, convolution geometry (`conv`, see gemm), K tail as (k, row stride) pairs,
+    flags.  gemm() / gemm_units() add their pointers to it; the *_ok predicates below send it to vcx_gemm_route as it is, so what they
+    ask about is the descriptor the launcher would get."""
+    ldw = K if ldw is None else ldw
+    if max(M, N, K, ldw, ldc, ldr, conv["in_w"] if conv else 0) >= 1 << 31:      # ctypes would truncate them silently
+        raise VcxError(f"gemm: M={M} N={N} K={K} ldw={ldw} ldc={ldc} ldr={ldr} do not fit the descriptor's 32-bit fields")
+    d = GemmDesc()
+    d.lda, d.M, d.N, d.K, d.ldw, d.ldc, d.ldr = lda, M, N, K, ldw, ldc, ldr
+    if conv is not None:
+        d.mode = 1
+        d.in_h, d.in_w, d.out_h, d.out_w = conv["in_h"], conv["in_w"], conv["out_h"], conv["out_w"]
+        d.cin, d.kh, d.kw = conv["cin"], conv["kh"], conv["kw"]
+        d.stride, d.pad_h, d.pad_w, d.ups = conv["stride"], conv["pad_h"], conv["pad_w"], conv.get("ups", 0)
+        if conv.get("slabk", conv_slab_major(conv["cin"], conv["kh"] * conv["kw"])):     # the order pack_conv() produced
+            flags |= GEMM_CONV_SLABK
+    for j, (k, ld) in zip("01", tail):
+        setattr(d, "tail_k" + j, k)
+        setattr(d, "tail_lda" + j, ld)
+    d.flags, d.alpha = flags, alpha
+    return d
+
+
+def _takes(M, N, K, lda, ldc, unit_rows=0, **kw):
+    """Does a kernel take the call _gemm_desc(...) describes - vcx_gemm_f16, or vcx_gemm_units_f16 with unit_rows > 0 - with every
+    by-product its flags ask for?  The dispatcher's own answer (vcx_gemm_route): it refuses a flag that the route's kernel does not have."""
+    try:
+        return lib().vcx_gemm_route(ctypes.byref(_gemm_desc(M, N, K, lda, ldc, **kw)), unit_rows) > 0
+    except VcxError:          # a size beyond the descriptor's fields
+        return False
+
+
 def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, residual=None, ldr=None, rowadd=None,
          rowadd_div=0, geglu=False, out_f32=False, alpha=1.0, conv=None, ldw=None, ln_stats=None, ln_colsum=None, ln_t=False, colstats=None,
          colstats_ld=None, colstats_col=0, rowstats=None, rowstats_eps=1e-5, tail=None):
@@ -75,9 +107,14 @@ def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, res
         ldc = n_out
     elif ldc is None:
         ldc = out.stride(0)
-    d = GemmDesc()
+    if tail and (conv is None or len(tail) > 2):
+        raise VcxError("gemm: a K tail belongs to a convolution and has one or two sources")
+    for j, t in enumerate(tail or ()):
+        if t.dim() != 2 or t.shape[0] != M or t.stride(1) != 1:
+            raise VcxError(f"gemm: tail source {j} must be [M = {M}, k] with unit column stride, got {tuple(t.shape)}")
+    d = _gemm_desc(M, N, K, lda, ldc, ldw=ldw, conv=conv, tail=[(t.shape[1], t.stride(0)) for t in tail or ()], alpha=alpha)
     d.A, d.W, d.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    flags = 0
+    flags = d.flags
     if bias is not None:
         d.bias = bias.data_ptr()
         flags |= GEMM_BIAS_M if bias_m else GEMM_BIAS_N
@@ -115,28 +152,11 @@ def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, res
         d.rowstats, d.rowstats_eps = rowstats.data_ptr(), float(rowstats_eps)
         flags |= GEMM_ROWSTATS
     if tail:
-        if conv is None or len(tail) > 2:
-            raise VcxError("gemm: a K tail belongs to a convolution and has one or two sources")
         _dev16(*tail)
-        for j, t in enumerate(tail):
-            if t.dim() != 2 or t.shape[0] != M or t.stride(1) != 1:
-                raise VcxError(f"gemm: tail source {j} must be [M = {M}, k] with unit column stride, got {tuple(t.shape)}")
-            if j == 0:
-                d.tail_a0, d.tail_lda0, d.tail_k0 = t.data_ptr(), t.stride(0), t.shape[1]
-            else:
-                d.tail_a1, d.tail_lda1, d.tail_k1 = t.data_ptr(), t.stride(0), t.shape[1]
-    d.lda, d.M, d.N, d.K = lda, M, N, K
-    d.ldw = ldw if ldw is not None else K
-    d.ldc = ldc
-    if conv is not None:
-        d.mode = 1
-        d.in_h, d.in_w, d.out_h, d.out_w = conv["in_h"], conv["in_w"], conv["out_h"], conv["out_w"]
-        d.cin, d.kh, d.kw = conv["cin"], conv["kh"], conv["kw"]
-        d.stride, d.pad_h, d.pad_w, d.ups = conv["stride"], conv["pad_h"], conv["pad_w"], conv.get("ups", 0)
-        if conv.get("slabk", conv_slab_major(conv["cin"], conv["kh"] * conv["kw"])):     # the order pack_conv() produced
-            flags |= GEMM_CONV_SLABK
+        d.tail_a0 = tail[0].data_ptr()
+        if len(tail) > 1:
+            d.tail_a1 = tail[1].data_ptr()
     d.flags = flags
-    d.alpha = alpha
     check(lib().vcx_gemm_f16(ctypes.byref(d), _stream()), "vcx_gemm_f16")
     return out
 
@@ -144,19 +164,19 @@ def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, res
 def rowstats_ok(M, N, K, *, lda=None, ldc=None, ldr=0, unit_rows=None, video_rows=None):
     """Will the layer producing an [M, N] output - vcx_gemm_f16 (bias / residual at most), or vcx_gemm_units_f16 with `unit_rows` rows per
     weight set - write LayerNorm's row statistics of its output (VCX_GEMM_ROWSTATS)?  Only the pipelined weight-stationary kernel has
-    that epilogue: a mirror of its dispatch conditions in csrc/gemm.hip (N = K = 320, M >= 8192, 32-bit extents, knobs GEMM_DMA /
-    GEMM_WS on and no forced tile configuration); elsewhere the consumer makes its statistics pass (row_stats).
+    that epilogue; whether it takes the flagged call is the dispatcher's answer (vcx_gemm_route).  Elsewhere the consumer makes its
+    statistics pass (row_stats).
     The epilogue's statistics and row_stats agree to rounding, not bit for bit, so a row's route must not depend on the batch it runs
-    in: the size threshold is decided on `video_rows`, the rows of ONE video (default M), and M >= 8192 follows from it for every
-    batch.  Only the 4 GiB extents are checked on the whole call."""
-    lim = 0xFFFF0000
-    lda, ldc = K if lda is None else lda, N if ldc is None else ldc
+    in.  That is this function's own rule: the dispatcher is asked about ONE video alone (`video_rows` rows, default M), with per-unit
+    weights also about two videos - the smallest batch, where a video may be one unit among several and other conditions hold - and
+    about the call itself; all must be taken.  Only the 4 GiB extents then depend on the whole call."""
     per_video = M if video_rows is None else video_rows
-    ok = (LN_ROWSTATS and N == 320 and K == 320 and per_video >= 8192 and M >= per_video and tune_get("GEMM_DMA") != 0 and tune_get("GEMM_WS") != 0
-          and tune_get("GEMM_CFG") < 0 and 2 * ((M - 1) * lda + K) < lim and 2 * (M + 256) * ldc < lim and 2 * (M + 256) * ldr < lim and 8 * M < lim)
-    if unit_rows is not None:
-        ok = ok and M % unit_rows == 0 and M // unit_rows <= 65535 and unit_rows % 32 == 0 and unit_rows >= 1024
-    return ok
+    if not LN_ROWSTATS or M < per_video:
+        return False
+    flags = GEMM_ROWSTATS | GEMM_BIAS_N | (GEMM_RESIDUAL if ldr else 0)
+    lda, ldc = K if lda is None else lda, N if ldc is None else ldc
+    calls = {per_video, M} | ({2 * per_video} if unit_rows else set())
+    return all(_takes(m, N, K, lda, ldc, unit_rows or 0, ldr=ldr, flags=flags) for m in sorted(calls))
 
 
 def rowstats_buffer(M, device):
@@ -177,10 +197,8 @@ def gemm_units(a, wn, bn, *, unit_rows, out=None, rowstats=None, rowstats_eps=1e
         raise VcxError(f"gemm_units: a {tuple(a.shape)} / wn {tuple(wn.shape)} / bn {tuple(bn.shape)} do not describe {units} units of {unit_rows} rows")
     if out is None:
         out = torch.empty((M, N), dtype=_f16, device=a.device)
-    d = GemmDesc()
+    d = _gemm_desc(M, N, K, a.stride(0), out.stride(0), flags=GEMM_BIAS_N)
     d.A, d.W, d.C, d.bias = a.data_ptr(), wn.data_ptr(), out.data_ptr(), bn.data_ptr()
-    d.lda, d.M, d.N, d.K, d.ldw, d.ldc = a.stride(0), M, N, K, K, out.stride(0)
-    d.flags, d.alpha = GEMM_BIAS_N, 1.0
     if rowstats is not None:
         _dev32(rowstats)
         if rowstats.numel() != 2 * M or not rowstats.is_contiguous():
@@ -192,26 +210,17 @@ def gemm_units(a, wn, bn, *, unit_rows, out=None, rowstats=None, rowstats_eps=1e
 
 
 def units_route(M, N, K, unit_rows, *, lda=None, ldc=None):
-    """The route vcx_gemm_units_f16 takes for M rows in units of unit_rows: a mirror of its dispatcher in csrc/gemm.hip.
-    "single" (one unit: vcx_gemm_f16), "ws320" (one launch of the weight-stationary kernel, N = K = 320), "grouped" (the tiled engine's
-    per-unit form: one plan for all units) or "loop" (vcx_gemm_f16 unit by unit).  Knobs and VCX_GEMM_UNITS_LOOP are read per call, as
-    the dispatcher reads them."""
-    lim = 0xFFFF0000
-    lda, ldc = K if lda is None else lda, N if ldc is None else ldc
+    """The route vcx_gemm_units_f16 takes for M rows in units of unit_rows, as its dispatcher says (vcx_gemm_route; knobs and
+    VCX_GEMM_UNITS_LOOP as they are at the time of the call): "single" (one unit: vcx_gemm_f16's call), "ws320" (one launch of the
+    weight-stationary kernel, N = K = 320), "grouped" (the tiled engine's per-unit form: one plan for all units) or "loop" (vcx_gemm_f16
+    unit by unit)."""
     if unit_rows <= 0 or M <= 0 or M % unit_rows != 0:
         raise VcxError(f"units_route: M ({M}) must be a whole number of units of {unit_rows} rows")
-    units = M // unit_rows
-    if units == 1:
-        return "single"
-    dma, ws, force = tune_get("GEMM_DMA") != 0, tune_get("GEMM_WS") != 0, tune_get("GEMM_CFG")
-    extents = 2 * ((M - 1) * lda + K) < lim and 2 * (M + 256) * ldc < lim
-    if (K == 320 and N == 320 and unit_rows % 32 == 0 and unit_rows >= 1024 and M >= 8192 and extents and units <= 65535 and dma and ws and force < 0):
-        return "ws320"
-    ws_per_unit = K == 320 and N % 320 == 0 and N <= 1280 and unit_rows >= 8192 and ws and force < 0      # vcx_gemm_f16 would take each unit weight-stationary
-    if (units <= 65535 and K % 64 == 0 and N % 8 == 0 and extents and 2 * ((N - 1) * K + K) < lim and dma and force <= 5 and not ws_per_unit
-            and os.environ.get("VCX_GEMM_UNITS_LOOP", "0")[:1] in ("", "0")):
-        return "grouped"
-    return "loop"
+    d = _gemm_desc(M, N, K, K if lda is None else lda, N if ldc is None else ldc, flags=GEMM_BIAS_N)
+    route = lib().vcx_gemm_route(ctypes.byref(d), unit_rows)
+    if route <= 0:
+        raise VcxError("units_route: " + lib().vcx_last_error().decode("utf-8", "replace"))
+    return {ROUTE_UNITS_WS320: "ws320", ROUTE_UNITS_GROUPED: "grouped", ROUTE_UNITS_LOOP: "loop"}.get(route, "single")
 
 
 def units_one_launch_ok(M, N, K, unit_rows, *, lda=None, ldc=None):
@@ -222,17 +231,13 @@ def units_one_launch_ok(M, N, K, unit_rows, *, lda=None, ldc=None):
 
 def lnfold_ok(rows, n_out, K, *, lda=None, ldc=None, transposed=False):
     """Will vcx_gemm_f16 take a folded-LayerNorm projection (VCX_GEMM_LNFOLD / _T) of `rows` token rows x K channels onto n_out
-    outputs?  The epilogue exists in the DMA kernel only; this mirrors its preconditions in csrc/gemm.hip (`dma_ok`: knob
-    GEMM_DMA, K % 64 == 0, GEMM N % 8 == 0, every extent and the output offsets up to 256 rows past the end below 4 GiB).  Where it
-    says no - a longer clip or a larger frame than any shipped config - the caller runs layer_norm + the plain projection, as
+    outputs?  The epilogue exists in the DMA kernels only; the dispatcher says whether one of them takes the call (vcx_gemm_route).
+    Where it says no - a longer clip or a larger frame than any shipped config - the caller runs layer_norm + the plain projection, as
     before the fold existed, instead of getting VCX_EINVAL from every transformer block."""
-    lim = 0xFFFF0000
     lda = K if lda is None else lda
-    M, N = (n_out, rows) if transposed else (rows, n_out)          # GEMM axes: LNFOLD_T puts the weight rows on M
-    ldc = N if ldc is None else ldc
-    a_rows, a_ld, w_rows, w_ld = (n_out, K, rows, lda) if transposed else (rows, lda, n_out, K)
-    return (tune_get("GEMM_DMA") != 0 and K % 64 == 0 and N % 8 == 0 and (n_out % 4 == 0 and n_out >= 4)
-            and 2 * ((a_rows - 1) * a_ld + K) < lim and 2 * ((w_rows - 1) * w_ld + K) < lim and 2 * (M + 256) * ldc < lim)
+    if transposed:          # LNFOLD_T puts the weight rows on M, the token rows are the W operand
+        return _takes(n_out, rows, K, K, rows if ldc is None else ldc, ldw=lda, flags=GEMM_LNFOLD_T | GEMM_BIAS_M)
+    return _takes(rows, n_out, K, lda, n_out if ldc is None else ldc, flags=GEMM_LNFOLD | GEMM_BIAS_N)
 
 
 def linear(x, w, bias=None, **kw):
@@ -260,14 +265,16 @@ def conv2d(x, w, bias, *, kh, kw, stride=1, pad_h=None, pad_w=None, ups=0, out_h
     return out.view(n, Ho, Wo, -1)
 
 
+def _rows_geom(M, in_rows, cin, taps):
+    """Convolution geometry for a route query that knows row counts only: ONE image of in_rows pixels and M outputs, taps x 1 taps."""
+    return dict(in_h=1, in_w=M if in_rows is None else in_rows, out_h=1, out_w=M, cin=cin, kh=taps, kw=1, stride=1, pad_h=0, pad_w=0)
+
+
 def conv_tail_ok(M, cin, cout, taps, tail_ks, in_rows=None):
     """Will vcx_gemm_f16 take a convolution over a cin-channel image with a K tail of widths tail_ks (the 1x1 skip convolution of a
-    ResBlock folded into its second convolution)?  The DMA kernel only: a mirror of `dma_ok` in csrc/gemm.hip."""
-    lim = 0xFFFF0000
-    K = taps * cin + sum(tail_ks)
-    return (tune_get("GEMM_DMA") != 0 and cin % 64 == 0 and cout % 8 == 0 and all(k % 64 == 0 and k > 0 for k in tail_ks) and 0 < len(tail_ks) <= 2
-            and 2 * (in_rows if in_rows is not None else M) * cin < lim and 2 * (cout - 1) * K + 2 * K < lim and 2 * (M + 256) * cout < lim
-            and all(2 * M * k < lim for k in tail_ks))
+    ResBlock folded into its second convolution)?  The DMA kernel only: the dispatcher's answer (vcx_gemm_route)."""
+    return (0 < len(tail_ks) <= 2 and all(k > 0 for k in tail_ks)
+            and _takes(M, cout, taps * cin + sum(tail_ks), cin, cout, conv=_rows_geom(M, in_rows, cin, taps), tail=[(k, k) for k in tail_ks]))
 
 
 def temporal_conv3(x, w, bias, **kwargs):
@@ -282,14 +289,12 @@ def temporal_conv3(x, w, bias, **kwargs):
 # normalisation
 # ------------------------------------------------------------------------------------------
 def colstats_ok(M, pixels, cin, cout, in_rows=None):
-    """Can the layer producing an [M, cout] output - a convolution over a cin-channel image, or a linear layer with K = cin - write
-    column moments for a GroupNorm whose statistics span `pixels` consecutive output rows?  (VCX_GEMM_COLSTATS: DMA kernel -
-    cin % 64 == 0, cout % 8 == 0, 32-bit byte offsets - whole 64-row strips per statistics unit.)"""
-    lim = 0xFFFF0000
-    # (a mirror of the kernel-side test in vcx_gemm_f16, like lnfold_ok: with the DMA kernel switched off by the A/B knob the producers
-    # fall back to a statistics pass instead of asking for an epilogue that kernel does not have - ADVICE r4)
-    return (tune_get("GEMM_DMA") != 0 and pixels % 64 == 0 and M % 64 == 0 and cin % 64 == 0 and cout % 8 == 0 and 2 * (M + 256) * cout < lim
-            and 2 * (in_rows if in_rows is not None else M) * cin < lim)
+    """Can the layer producing an [M, cout] output - a convolution over a cin-channel image of in_rows pixels, or a linear layer with
+    K = cin - write column moments for a GroupNorm whose statistics span `pixels` consecutive output rows?  (VCX_GEMM_COLSTATS.)
+    Whole 64-row strips per statistics unit are the host graph's rule; whether a kernel with that epilogue takes the call is the
+    dispatcher's answer (vcx_gemm_route).  A convolution is asked about with one tap: its taps multiply the weight's extent only."""
+    return (pixels % 64 == 0 and M % 64 == 0
+            and _takes(M, cout, cin, cin, cout, conv=None if in_rows is None else _rows_geom(M, in_rows, cin, 1), flags=GEMM_COLSTATS))
 
 
 def colstats_buffer(M, cout, device):
