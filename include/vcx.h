@@ -257,6 +257,14 @@ int vcx_layernorm_f16(const void* x, void* y, const float* gamma, const float* b
  * nk >= 4096 and no VCX_ATTN_ACCUMULATE the software-pipelined one-wave-per-SIMD kernel
  * (csrc/attention_v2.hip), otherwise the phased kernel (csrc/attention.hip); same contract,
  * results agree to fp16 rounding (different summation order).  Knob VCX_TUNE_FLASH_IMPL.
+ * Rounding points (every attention entry point; tests/rounding_quality.py MODELS holds them with their source lines and
+ * tests/test_rounding_gpu.py holds each kernel to them): the scores, the exponentials, the row sums and the P V accumulation are fp32;
+ * the UNNORMALISED probabilities exp(s - m) are rounded to fp16 for the P V product and 1 / l (l: the fp32 sum of the unrounded ones)
+ * scales the fp32 result, which is rounded to fp16 once.  m is a running maximum that moves only when a key tile exceeds it by more
+ * than 2^8 for some query of the wave (never behind by more; the temporal kernels use the exact row maximum), so the largest
+ * probability of a row is 2^x, 0 <= x <= 8, rounded like the others - on a sharply peaked softmax that costs up to 0.2 of an fp16
+ * rounding error more than an exact maximum would (profiles/rounding_quality.md).  VCX_ATTN_ACCUMULATE reads the stored fp16 O back:
+ * the first result is rounded before the sum.
  * ---------------------------------------------------------------------------------- */
 #define VCX_ATTN_ACCUMULATE 1
 #define VCX_ATTN_LOG2_LOGITS 2
@@ -268,8 +276,11 @@ int vcx_attn_flash_d64_f16(const void* q, const void* k, const void* vt, void* o
 /* Two key/value sets in one pass:  O = softmax(scale Q K1^T) V1 + softmax(scale Q K2^T) V2
  * - the text (+) image cross-attention of attention.py:129-142 (image_cross_attention_scale
  * = 1) without reading Q twice and without writing O, reading it back and writing it again.
- * Same addressing as above per set (kv_rows / kv_div / ldk / ldvt / nk with suffix 1, 2);
- * the two partial results are added in fp32 and rounded once.  flags: VCX_ATTN_LOG2_LOGITS. */
+ * Same addressing as above per set (kv_rows / kv_div / ldk / ldvt / nk with suffix 1, 2).  The first set's normalised result waits
+ * for the second as PACKED FP16 - in registers, or parked in LDS by the LDS-resident kernels, which have room for no more - and the sum
+ * of that and the fp32 second result is rounded: one rounding point more than the single form (like VCX_ATTN_ACCUMULATE, without
+ * the trip through memory).  Only the flash kernel's form with one query block per wave (nq small against 256-row blocks, or knob
+ * FLASH_QB = 1 with XATTN_RESIDENT = 0) keeps the first result in fp32 and rounds once.  flags: VCX_ATTN_LOG2_LOGITS. */
 int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const void* vt1, const void* k2,
                                 const void* vt2, void* o, int n_groups, int heads, int nq,
                                 int nk1, int kv_rows1, int kv_div1, int64_t ldk1, int64_t ldvt1,
@@ -303,7 +314,9 @@ int vcx_attn_temporal_d64_masked_f16(const void* qkv, void* o, int B, int T, int
  * c(d) = clamp(d, -R, R) + R, tables of 2R + 1 <= 64 rows.  The two table contractions are 64-wide GEMMs of the CALLER:
  *   relg [(b t p)][heads][64] fp16 (in)  = q Ek^T per query row and head (slots 2R + 1 .. 63 unused) - added to the scores before scale and softmax;
  *   relp [(b t p)][heads][64] fp16 (out) = the probabilities of a query by clipped distance (keys beyond +-R summed into slots 0 / 2R); the caller
- *   ZEROES it before the call and adds relp Ev to o afterwards.  flags: VCX_ATTN_CAUSAL. */
+ *   ZEROES it before the call and adds relp Ev to o afterwards.  flags: VCX_ATTN_CAUSAL.
+ * Rounding: o as vcx_attn_temporal_d64_f16 (fp16 unnormalised probabilities against the exact row maximum, the fp32 result scaled by
+ * 1 / l and rounded once); relp from those fp16 probabilities times 1 / l - rounded per slot, the end slots after their fp32 sum. */
 int vcx_attn_temporal_d64_rel_f16(const void* qkv, void* o, const void* relg, void* relp, int R, int B, int T, int64_t P,
                                   int heads, int64_t ld, int k_off, int v_off, int64_t ldo, float scale, int flags,
                                   void* stream);

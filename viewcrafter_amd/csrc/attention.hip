@@ -57,8 +57,8 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // (VALU and MFMA issue do not overlap on a SIMD - tools/ubench.hip - so every VALU instruction removed is time).
 //
 // DUAL: text (+) image cross-attention (attention.py:129-142) in one launch: the key / value loop runs twice, over (k, vt)
-// and over (k2, vt2), each with its own softmax normalisation; the first result stays in registers (fp32) and the sum is
-// rounded once.  Q is read once and O written once - run as two launches these layers are pure overhead (Q read twice,
+// and over (k2, vt2), each with its own softmax normalisation; the first result stays in registers (fp32 at QB = 1, packed fp16 at
+// QB = 2: include/vcx.h) and the sum is rounded.  Q is read once and O written once - as two launches these layers are overhead (Q read twice,
 // O written, read back and written again at 2.2-2.6 TB/s).
 template <int QB, bool PRE, bool DUAL = false>
 __global__ void __launch_bounds__(256, 2) flash_d64_kernel(FlashArgs p) {
