@@ -37,8 +37,9 @@ extern "C" {
  * struct_size - a descriptor of another layout is rejected instead of read past its end; ldcs; vcx_clip_preprocess_f32,
  * vcx_add_nchw_f32_to_nhwc_f16.  6: vcx_ddim_ws_bytes, ws_bytes argument of the DDIM steps.  7: vcx_groupnorm_fold_linear_f16,
  * vcx_gemm_units_f16, vcx_attn_flash_d512_f16.  8: vcx_gemm_desc grows rowstats / rowstats_eps (VCX_GEMM_ROWSTATS) and
- * tail_a0 / tail_a1 (K tail of a convolution from linear sources); vcx_groupnorm_apply2_f16.  10: vcx_gemm_route. */
-#define VCX_ABI_VERSION 10
+ * tail_a0 / tail_a1 (K tail of a convolution from linear sources); vcx_groupnorm_apply2_f16.  10: vcx_gemm_route.  11: MXFP8 operands - vcx_quant_mxfp8_f16,
+ * vcx_layernorm_mxfp8_f16, vcx_gemm_mxfp8, vcx_gemm_mxfp8_ok; VCX_GEMM_MXFP8_OUT. */
+#define VCX_ABI_VERSION 11
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -108,6 +109,7 @@ int vcx_device_arch(char* name_host, int len);
  * the weight-stationary kernel, linear mode, N = K = 320, M >= 8192, BIAS_N / RESIDUAL at most, fp16 output (the attention output
  * projections and proj_in of the C = 320 level); with vcx_gemm_units_f16 too.  Any other shape: VCX_EINVAL. */
 #define VCX_GEMM_ROWSTATS 0x400
+#define VCX_GEMM_MXFP8_OUT 0x800 /* vcx_gemm_mxfp8 only (below): the GEGLU result leaves as MXFP8 bytes + scales, not fp16 */
 
 typedef struct vcx_gemm_desc {
     size_t struct_size;   /* = sizeof(vcx_gemm_desc) of the header the caller was compiled against; anything else is VCX_EINVAL */
@@ -232,6 +234,48 @@ int vcx_groupnorm_fold_linear_f16(const float* W, const float* bias, const float
 int vcx_rowstats_f16(const void* x, float* stats, int64_t rows, int C, float eps, void* stream);
 int vcx_layernorm_f16(const void* x, void* y, const float* gamma, const float* beta,
                       int64_t rows, int C, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * MXFP8 operands (ABI 11): OCP MX with e4m3fn elements and e8m0 scales, for the block-scaled matrix instruction
+ * v_mfma_scale_f32_16x16x128_f8f6f4.  Opt-in (the GEGLU feed-forward under VCX_FF_MXFP8=1); nothing else uses it.
+ *
+ * A matrix [rows][K] (K % 32 == 0) is two dense arrays, ONE layout for every producer and consumer:
+ *   elements  uint8 [rows][Kp]        Kp = K rounded up to a multiple of 128; row pitch Kp bytes
+ *   scales    uint8 [rows][Kp / 32]   one byte per block of 32 consecutive K-elements of a row; row pitch Kp / 32 bytes (a multiple of 4)
+ * Padding (k >= K): element bytes 0x00, scale bytes 127.  Element base addresses are 16-byte, scale base addresses 4-byte aligned.
+ * For a block of 32 fp16 values x, with amax = max |x| (exact):
+ *   scale byte s = 0             if amax == 0
+ *                = 0xFF          if the block holds an inf or NaN; every element byte of that block is 0x7F (NaN)
+ *                = E - 8 + 127   otherwise, E = floor(log2 amax) read from the exponent field (fp16 subnormals: their true exponent), so
+ *                                s is in [95, 134]
+ *   element byte = e4m3fn, round to nearest even, of clamp(x * 2^(8 - E), -448, 448)   (for amax == 0: of x, i.e. 0x00, or 0x80 for -0)
+ * The product by 2^(8 - E) is exact; scaled magnitudes in (448, 512) clamp to 448; finite input never yields 0x7F / 0xFF.
+ * The represented value is float(element) * 2^(s - 127).  tests/mx_emulation.py is this definition in torch, packing.pack_mxfp8 applies
+ * it to weights; the three producers below agree with it byte for byte.
+ * ---------------------------------------------------------------------------------- */
+/* x fp16 [rows][K] with row pitch ldx elements (ldx % 8 == 0) -> q / scales as above. */
+int vcx_quant_mxfp8_f16(const void* x, int64_t ldx, void* q, void* scales, int64_t rows, int K, void* stream);
+/* quant(vcx_layernorm_f16(x)) bit for bit in one pass: vcx_layernorm_f16's arithmetic and summation order, every normalised value rounded to
+ * fp16 as that kernel stores it, then quantised; the fp16 rows are never written.  x fp16 [rows][C] dense, C % 32 == 0. */
+int vcx_layernorm_mxfp8_f16(const void* x, void* q, void* scales, const float* gamma, const float* beta, int64_t rows, int C, float eps,
+                            void* stream);
+/* out[m, n] = epilogue( sum_k A[m, k] W[n, k] ), both operands MXFP8 over the same K (A: M rows, W: N rows), fp32 accumulation.
+ * Operands reach LDS by buffer-load DMA with descriptor zero-fill, persistent XCD-aware tile walk, no atomics.  One tile shape and
+ * one K order: a row's result depends neither on M nor on the tile or the grid it runs in.  flags (exactly one of):
+ *   VCX_GEMM_BIAS_N                                          out fp16 [M][ldc] = acc + bias[n]
+ *   VCX_GEMM_BIAS_N | VCX_GEMM_RESIDUAL                      ... + residual[m * ldr + n]
+ *   VCX_GEMM_BIAS_N | VCX_GEMM_GEGLU                         out fp16 [M][ldc], N / 2 columns: x * gelu_erf(gate), W / bias rows packed as
+ *                                                            for VCX_GEMM_GEGLU above
+ *   VCX_GEMM_BIAS_N | VCX_GEMM_GEGLU | VCX_GEMM_MXFP8_OUT    the same values, rounded to fp16 and quantised: out = element bytes
+ *                                                            [M][Kp(N / 2)], out_scales [M][Kp(N / 2) / 32], padding included -
+ *                                                            quant(the fp16-out form's result) bit for bit (ldc ignored)
+ * bias fp32 [N] (required); out_scales / residual NULL where the flags do not ask for them.  Shapes: vcx_gemm_mxfp8_ok. */
+int vcx_gemm_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, void* out_scales, const float* bias,
+                   const void* residual, int64_t M, int64_t N, int64_t K, int64_t ldc, int64_t ldr, int flags, void* stream);
+/* 1 if vcx_gemm_mxfp8 takes the shape with dense output / residual rows, else 0 with the reason in vcx_last_error(): one of the four flag
+ * words above, K % 32 == 0, N % 8 == 0 (GEGLU: N % 64 == 0, i.e. N / 2 % 32 == 0), every operand, output and residual extent below
+ * 4 GiB (32-bit buffer offsets, as in the fp16 DMA engine).  Touches no device; callers ask it instead of restating the rules. */
+int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags);
 
 /* ------------------------------------------------------------------------------------
  * Flash attention, head dim 64, no mask:  O = softmax(scale * Q K^T) V

@@ -1,0 +1,77 @@
+"""rel-L2 / PSNR against the fp32 oracle at the config-1 latent (16 x 40 x 64, inference_pvd_512.yaml, synthetic weights) with the MXFP8
+feed-forward switch off and on: one UNet forward, and a 10-step DDIM trajectory (eta 0, CFG 7.5, guidance rescale 0.7) of the product
+sampler against the oracle sampler on the oracle UNet.  Figures for profiles/mxfp8_ff.md.      python tools/mxfp8_accuracy.py [--steps 10]"""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+DEV = "cuda"
+
+
+def rel_l2(a, b):
+    a, b = a.detach().double().flatten(), b.detach().double().flatten()
+    return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+def psnr(a, b, peak=2.0):
+    mse = float(((a.detach().double() - b.detach().double()) ** 2).mean())
+    return 10 * torch.log10(torch.tensor(peak * peak / max(mse, 1e-30))).item()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--yaml", default="inference_pvd_512.yaml")
+    a = ap.parse_args()
+    from oracle import lvdm_oracle as O
+    from viewcrafter_amd.builder import build_diffusion_model, randomize_parameters
+    from viewcrafter_amd.config import load_yaml
+    from viewcrafter_amd.lvdm.models.samplers.ddim import DDIMSampler
+    from viewcrafter_amd.lvdm.modules import attention as A
+    path = os.path.join(ROOT, "configs", a.yaml)
+    model = build_diffusion_model(path, device=DEV, conditioners="identity")
+    randomize_parameters(model, seed=0)
+    params = load_yaml(path)["model"]["params"]
+    unet = model.model.diffusion_model
+    hp = dict(params["unet_config"]["params"])
+    sd = {k: v.detach() for k, v in unet.state_dict().items()}
+    T, h, w = 16, 40, 64
+    g = torch.Generator().manual_seed(77)
+    x = torch.randn(1, 8, T, h, w, generator=g).to(DEV)
+    ctx = torch.randn(1, 77 + 256, 1024, generator=g).to(DEV)
+    uctx = torch.randn(1, 77 + 256, 1024, generator=g).to(DEV)
+    x_T = torch.randn(1, 4, T, h, w, generator=g).to(DEV)
+    cat = (torch.randn(1, 4, T, h, w, generator=g) * 0.8).to(DEV)
+    ts, fs = torch.tensor([799], device=DEV), torch.tensor([10], device=DEV)
+    cond, uc = {"c_crossattn": [ctx], "c_concat": [cat]}, {"c_crossattn": [uctx], "c_concat": [cat]}
+    tables = O.diffusion_tables(params["timesteps"], params["linear_start"], params["linear_end"], params["rescale_betas_zero_snr"])
+    scale_arr = O.dynamic_rescale_table(params["timesteps"], params["base_scale"])
+
+    def apply_oracle(xx, t, c):
+        return O.unet_forward(sd, hp, torch.cat([xx, c["c_concat"][0]], dim=1), t.to(DEV), c["c_crossattn"][0], fs)
+
+    was = A.FF_MXFP8
+    try:
+        with torch.no_grad():
+            ref_fwd = O.unet_forward(sd, hp, x, ts, ctx, fs)
+            ref_traj, _ = O.ddim_sample(apply_oracle, tables, scale_arr, x_T, cond, uc, steps=a.steps, eta=0.0, cfg_scale=7.5, guidance_rescale=0.7,
+                                        spacing="uniform_trailing", parameterization="v")
+            for flag in (False, True):
+                A.FF_MXFP8 = flag
+                y = unet._forward(x, ts, context=ctx, fs=fs)
+                ours, _ = DDIMSampler(model).sample(S=a.steps, conditioning=cond, batch_size=1, shape=[4, T, h, w], verbose=False,
+                                                    unconditional_guidance_scale=7.5, unconditional_conditioning=uc, eta=0.0, cfg_img=None, mask=None,
+                                                    x0=None, fs=fs, timestep_spacing="uniform_trailing", guidance_rescale=0.7, x_T=x_T,
+                                                    log_every_t=a.steps, unconditional_conditioning_img_nonetext=None)
+                print(f"VCX_FF_MXFP8={int(flag)}: UNet forward vs fp32 oracle rel-L2 {rel_l2(y, ref_fwd):.3e} PSNR {psnr(y, ref_fwd):.2f} dB | "
+                      f"{a.steps}-step trajectory, final latent rel-L2 {rel_l2(ours, ref_traj):.3e} PSNR {psnr(ours, ref_traj):.2f} dB", flush=True)
+    finally:
+        A.FF_MXFP8 = was
+
+
+if __name__ == "__main__":
+    main()

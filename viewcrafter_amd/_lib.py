@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libvcx.so")
 
 # every symbol include/vcx.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
-    "vcx_abi_version", "vcx_last_error", "vcx_device_arch", "vcx_gemm_f16", "vcx_gemm_units_f16", "vcx_gemm_route",
+    "vcx_abi_version", "vcx_last_error", "vcx_device_arch", "vcx_gemm_f16", "vcx_gemm_units_f16", "vcx_gemm_route", "vcx_quant_mxfp8_f16", "vcx_layernorm_mxfp8_f16", "vcx_gemm_mxfp8", "vcx_gemm_mxfp8_ok",
     "vcx_groupnorm_ws_bytes", "vcx_groupnorm_stats_f16", "vcx_groupnorm_apply_f16", "vcx_groupnorm_apply2_f16", "vcx_groupnorm_stats_from_colstats_f32", "vcx_groupnorm_fold_linear_f16", "vcx_layernorm_f16", "vcx_rowstats_f16",
     "vcx_attn_flash_d64_f16", "vcx_attn_flash_d512_f16", "vcx_attn_flash_dual_d64_f16", "vcx_attn_temporal_d64_f16", "vcx_attn_temporal_d64_masked_f16", "vcx_attn_temporal_d64_rel_f16", "vcx_softmax_rows_f16",
     "vcx_silu_f32", "vcx_gelu_f16", "vcx_clip_preprocess_f32", "vcx_add_nchw_f32_to_nhwc_f16", "vcx_timestep_embedding_f32", "vcx_cast_f32_to_f16", "vcx_cast_f16_to_f32",
@@ -21,12 +21,12 @@ SYMBOLS = [
     "vcx_profile_begin", "vcx_profile_end", "vcx_tune_set", "vcx_tune_get",
 ]
 
-ABI_VERSION = 10         # include/vcx.h VCX_ABI_VERSION
+ABI_VERSION = 11         # include/vcx.h VCX_ABI_VERSION
 # experiment knobs (include/vcx.h VCX_TUNE_*): name -> (index, default)
 TUNE = {"GEMM_CFG": (0, -1), "GEMM_DMA": (1, 1), "FLASH_QB": (2, 0), "XATTN_RESIDENT": (3, 1), "FLASH_IMPL": (4, 0), "EXP0": (5, 0),
         "EXP1": (6, 0), "GEMM_WS": (7, 1)}
 GEMM_BIAS_N, GEMM_BIAS_M, GEMM_ROWADD, GEMM_RESIDUAL, GEMM_GEGLU, GEMM_OUT_F32, GEMM_CONV_SLABK = 1, 2, 4, 8, 16, 32, 64
-GEMM_LNFOLD, GEMM_LNFOLD_T, GEMM_COLSTATS, GEMM_ROWSTATS = 0x80, 0x100, 0x200, 0x400
+GEMM_LNFOLD, GEMM_LNFOLD_T, GEMM_COLSTATS, GEMM_ROWSTATS, GEMM_MXFP8_OUT = 0x80, 0x100, 0x200, 0x400, 0x800
 # vcx_gemm_route (include/vcx.h VCX_ROUTE_*): 0 = refused, negative = an invalid descriptor
 ROUTE_REFUSED, ROUTE_REGISTER, ROUTE_TILED, ROUTE_WS320, ROUTE_WS320_GEGLU, ROUTE_WS320_LNF, ROUTE_UNITS_WS320, ROUTE_UNITS_GROUPED, ROUTE_UNITS_LOOP = range(9)
 PROF_FAMILIES = ("gemm", "flash_attn", "temporal_attn", "groupnorm", "layernorm", "elementwise")
@@ -80,6 +80,11 @@ def lib():
     L.vcx_gemm_f16.argtypes = [POINTER(GemmDesc), c_void_p]
     L.vcx_gemm_units_f16.argtypes = [POINTER(GemmDesc), c_int, c_int64, c_int64, c_void_p]
     L.vcx_gemm_route.argtypes = [POINTER(GemmDesc), c_int]
+    L.vcx_quant_mxfp8_f16.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]
+    L.vcx_layernorm_mxfp8_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]
+    L.vcx_gemm_mxfp8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                 c_int64, c_int, c_void_p]
+    L.vcx_gemm_mxfp8_ok.argtypes = [c_int64, c_int64, c_int64, c_int]
     L.vcx_groupnorm_ws_bytes.argtypes = [c_int, c_int64, c_int]
     L.vcx_groupnorm_stats_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]
     L.vcx_groupnorm_apply_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,

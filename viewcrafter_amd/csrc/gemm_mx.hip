@@ -1,0 +1,400 @@
+// vcx_gemm_mxfp8: out[m, n] = sum_k A[m, k] W[n, k] with both operands in MXFP8 (include/vcx.h "MXFP8 operands": e4m3fn element bytes,
+// one e8m0 scale byte per 32 K-elements) on the block-scaled matrix instruction v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulation.
+//
+// The structure is gemm_dma.hip's: operand tiles go HBM -> LDS with `buffer_load_dwordx4 ... lds` through descriptors whose range check
+// zero-fills rows beyond M / N, the 128-byte LDS row (there 64 fp16, here one 128-element K-step) carries the same XOR swizzle, the walk
+// over tiles is persistent and XCD-aware (tile_coords), loads run one K-step ahead in a second LDS buffer.  The scale bytes of a K-step
+// - one dword per tile row - come through LDS by the same DMA (`buffer_load_dword ... lds`), never by a VGPR load inside the K loop.
+//
+// Operand roles as in the fp16 engine: weight = A operand of the instruction, activation = B operand, so a lane's four accumulator
+// registers are four consecutive output columns of one row (gemm_epilogue.h).
+//
+// Operand map of the instruction with fp8 operands, measured with one-hot operands and coded scales (tools/ubench_mfma_scale_map.hip) - NOT
+// 32 consecutive K-elements per lane: lane l = (row l & 15, group g = l >> 4) supplies K-elements 16 g .. 16 g + 15 in its registers 0-3
+// and 64 + 16 g .. 64 + 16 g + 15 in its registers 4-7 - the 16-byte chunks g and 4 + g of the 128-byte row, the same two chunks the fp16
+// engine's lane reads - while its scale byte is the one of K-block g (elements 32 g .. 32 g + 31) of its row: a lane's scale applies to
+// elements held by its neighbours (groups 2 (g >> 1) and 2 (g >> 1) + 1 hold block g's elements).  tests/test_mxfp8_gpu.py checks the
+// whole path with exact data and per-(row, block) scales: a lane that fed 32 consecutive elements was an exact mismatch.
+//
+// ONE tile shape (128 x 128, 2 x 2 waves, 64 x 64 per wave) and one K order: a row's result does not depend on M, on the tile it falls
+// into or on the grid.  A wave's 64 packed GEGLU columns are 32 output columns - one MX block of the next layer's K axis - so the
+// quantising epilogue takes a block's maximum inside the wave, across the four lane groups, with two lane swaps.  No atomics.
+#include "gemm_epilogue.h"
+#include "mx_format.h"
+
+using namespace vcxgemm;
+using namespace vcxmx;
+
+namespace {
+
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef int i8v __attribute__((ext_vector_type(8)));
+typedef int i4v __attribute__((ext_vector_type(4)));
+constexpr unsigned OOB = 0xFFFFFFFFu;
+constexpr int KSTEP = 128;            // K-elements (= bytes) per LDS row and per matrix instruction
+
+struct MxArgs {
+    const unsigned char* A;           // [M][kp] element bytes
+    const unsigned char* As;          // [M][kp / 32] scale bytes
+    const unsigned char* W;           // [N][kp]
+    const unsigned char* Ws;          // [N][kp / 32]
+    void* C;                          // fp16 [M][ldc], or element bytes [M][kpo] (VCX_GEMM_MXFP8_OUT)
+    unsigned char* Cs;                // scale bytes [M][kpo / 32] (VCX_GEMM_MXFP8_OUT)
+    const float* bias;
+    const half_t* R;
+    int M, N, kp, kpo;
+    int ldc, ldr, flags;
+    int tiles_m, tiles_n;
+    unsigned a_bytes, as_bytes, w_bytes, ws_bytes, c_bytes, cs_bytes, r_bytes;
+};
+
+template <int TBM_, int TBN_, int NWM_, int NWN_>
+struct MxCfg {
+    static constexpr int TBM = TBM_, TBN = TBN_, NWM = NWM_, NWN = NWN_;
+    static constexpr int THREADS = 64 * NWM * NWN;
+    static constexpr int MF = TBM / NWM / 16, NF = TBN / NWN / 16;
+    static constexpr int XROWS = TBM * 8 / THREADS, WROWS = TBN * 8 / THREADS, RSTEP = THREADS / 8;
+    static constexpr size_t TILE = (size_t)(TBM + TBN) * KSTEP;             // element bytes of one stage
+    static constexpr size_t SCALES = (size_t)(TBM + TBN) * 4;               // scale dwords of one stage
+    static constexpr size_t STAGES = 2 * (TILE + SCALES);
+    static constexpr size_t STRIP = (size_t)TBN * NWM * sizeof(float);      // gemm_epilogue's strip of column addends per wave
+    static constexpr size_t SMEM = STAGES + STRIP;
+    static_assert(TBM + TBN == THREADS && TBM % 64 == 0, "scale DMA: one dword per thread, a wave's 64 rows on one operand");
+};
+
+__device__ __forceinline__ int mx_lds_off(int row, int chunk) {      // byte offset of a 16-byte chunk of a [rows][128] byte tile (lds_off's swizzle)
+    return row * KSTEP + ((chunk ^ ((row >> 1) & 7)) << 4);
+}
+
+// GEGLU epilogue (bias + x * gelu_erf(gate)), fp16 or MXFP8 output from the SAME statements: the gated value is rounded to fp16 exactly once,
+// QOUT then quantises the 32-column blocks of those fp16 values - quant(the fp16-out result) bit for bit.
+// Packed weight columns come in 64-column blocks [32 value | 32 gate] (packing.pack_geglu); a wave owns one block: fragments 0, 1 are
+// values, 2, 3 their gates, output column = block * 32 + a * 16 + lg * 4 + r.
+template <class Cfg, bool QOUT>
+__device__ __forceinline__ void mx_geglu_epilogue(const MxArgs& p, f4 (&acc)[Cfg::NF][Cfg::MF], int tile_m, int tile_n, int wm, int wn, int lane) {
+    static_assert(Cfg::NF == 4, "one 64-column packed block per wave");
+    constexpr int WM = Cfg::TBM / Cfg::NWM, WN = Cfg::TBN / Cfg::NWN;
+    typedef unsigned u2v __attribute__((ext_vector_type(2)));
+    const int lr = lane & 15, lg = lane >> 4;
+    const int nb = tile_n * Cfg::TBN + wn * WN;          // first packed column of the wave's block
+    const bool col_ok = nb + 64 <= p.N;                  // (QOUT: blocks beyond N are the output's K padding)
+    const int jout = nb >> 1;
+    f4 bx[2], bg[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const bool hb = col_ok && (p.flags & VCX_GEMM_BIAS_N);
+        bx[a] = hb ? *reinterpret_cast<const f4*>(p.bias + nb + a * 16 + lg * 4) : f4{0.f, 0.f, 0.f, 0.f};
+        bg[a] = hb ? *reinterpret_cast<const f4*>(p.bias + nb + 32 + a * 16 + lg * 4) : f4{0.f, 0.f, 0.f, 0.f};
+    }
+    const __amdgpu_buffer_rsrc_t srd_c = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)p.c_bytes, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t srd_s = __builtin_amdgcn_make_buffer_rsrc(QOUT ? (void*)p.Cs : p.C, 0, QOUT ? (int)p.cs_bytes : 0, 0x00020000);
+#pragma unroll
+    for (int b = 0; b < Cfg::MF; ++b) {
+        const int m = tile_m * Cfg::TBM + wm * WM + b * 16 + lr;
+        h4 o[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float xv = acc[a][b][r] + bx[a][r];
+                const float gv = acc[a + 2][b][r] + bg[a][r];
+                o[a][r] = (half_t)(xv * gelu_erf(gv));
+            }
+        if constexpr (!QOUT) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                const unsigned voff = (col_ok && m < p.M) ? ((unsigned)m * (unsigned)p.ldc + (unsigned)(jout + a * 16 + lg * 4)) * 2u : OOB;
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, o[a]), srd_c, voff, 0, 0);
+            }
+        } else {
+            // the block's maximum: 8 values in the lane, then across the four lane groups that share the row (lanes lr + 16 lg)
+            const h8 o8 = {o[0][0], o[0][1], o[0][2], o[0][3], o[1][0], o[1][1], o[1][2], o[1][3]};
+            unsigned hmax = mx_absmax_bits(o8);
+            const auto s16 = __builtin_amdgcn_permlane16_swap(hmax, hmax, false, false);
+            hmax = max(s16[0], s16[1]);
+            const auto s32 = __builtin_amdgcn_permlane32_swap(hmax, hmax, false, false);
+            hmax = max(s32[0], s32[1]);
+            float mul;
+            unsigned sb = mx_scale_byte(hmax, mul);
+            uint2 qb = mx_quant8(o8, sb, mul);
+            if (!col_ok) {
+                sb = MX_SCALE_ONE;
+                qb = make_uint2(0u, 0u);
+            }
+            const unsigned ok = m < p.M;
+            const unsigned qoff = (unsigned)m * (unsigned)p.kpo + (unsigned)(jout + lg * 4);
+            __builtin_amdgcn_raw_buffer_store_b32(qb.x, srd_c, ok ? qoff : OOB, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(qb.y, srd_c, ok ? qoff + 16u : OOB, 0, 0);
+            const unsigned soff = (unsigned)m * (unsigned)(p.kpo >> 5) + (unsigned)(jout >> 5);
+            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)sb, srd_s, (ok && lg == 0) ? soff : OOB, 0, 0);
+        }
+    }
+}
+
+// EPI: 0 = bias / residual, fp16 out (gemm_epilogue.h, the fp16 engine's epilogue); 1 = GEGLU, fp16 out; 2 = GEGLU, MXFP8 out
+template <class Cfg, int EPI>
+__global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int TBM = Cfg::TBM, TBN = Cfg::TBN, NFRAG = Cfg::NF, MFRAG = Cfg::MF;
+    constexpr int XROWS = Cfg::XROWS, WROWS = Cfg::WROWS, RSTEP = Cfg::RSTEP;
+    constexpr int WM = TBM / Cfg::NWM, WN = TBN / Cfg::NWN;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // ALL of the kernel's LDS: [2] tiles, [2] scale dwords, strips
+    unsigned char* sT = smem_raw;                                     // stage b: X tile [TBM][128], then W tile [TBN][128]
+    unsigned* sS = reinterpret_cast<unsigned*>(smem_raw + 2 * Cfg::TILE);      // stage b: [TBM] activation-row dwords, then [TBN] weight-row dwords
+
+    const __amdgpu_buffer_rsrc_t srd_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.A), 0, (int)p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.W), 0, (int)p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_as = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.As), 0, (int)p.as_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_ws = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.Ws), 0, (int)p.ws_bytes, 0x00020000);
+
+    const int ntiles = p.tiles_m * p.tiles_n;
+    const int G = gridDim.x;
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int chunk = tid & 7;   // LDS chunk position inside the 128-byte row
+    const int r0 = tid >> 3;     // tile row of this thread's first DMA instruction
+    const bool scale_is_a = wave < TBM / 64;      // wave-uniform: this wave's scale dwords belong to activation rows
+
+    unsigned xoff[XROWS], woff[WROWS], soff_v;
+    auto init_load = [&](int t) {
+        int tile_m, tile_n;
+        tile_coords(t, ntiles, p.tiles_n, tile_m, tile_n);
+#pragma unroll
+        for (int i = 0; i < XROWS; ++i) {
+            const int r = r0 + RSTEP * i;
+            const int m = tile_m * TBM + r;
+            const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;   // source chunk that lands at position `chunk`
+            xoff[i] = m < p.M ? (unsigned)m * (unsigned)p.kp + csrc : OOB;
+        }
+#pragma unroll
+        for (int i = 0; i < WROWS; ++i) {
+            const int r = r0 + RSTEP * i;
+            const int n = tile_n * TBN + r;
+            const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;
+            woff[i] = n < p.N ? (unsigned)n * (unsigned)p.kp + csrc : OOB;
+        }
+        const unsigned spitch = (unsigned)(p.kp >> 5);
+        if (scale_is_a) {
+            const int m = tile_m * TBM + tid;
+            soff_v = m < p.M ? (unsigned)m * spitch : OOB;
+        } else {
+            const int n = tile_n * TBN + (tid - TBM);
+            soff_v = n < p.N ? (unsigned)n * spitch : OOB;
+        }
+    };
+    // issue the DMA of K-step kt of the load tile into LDS stage `buf`
+    auto load_tile = [&](int kt, int buf) {
+        unsigned char* dx = sT + buf * Cfg::TILE + wave * 8 * KSTEP;
+        unsigned char* dw = sT + buf * Cfg::TILE + TBM * KSTEP + wave * 8 * KSTEP;
+        const unsigned soff = (unsigned)kt * KSTEP;
+#pragma unroll
+        for (int i = 0; i < XROWS; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_a, (lds_ptr_t)(dx + RSTEP * i * KSTEP), 16, xoff[i], soff, 0, 0);
+#pragma unroll
+        for (int i = 0; i < WROWS; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_w, (lds_ptr_t)(dw + RSTEP * i * KSTEP), 16, woff[i], soff, 0, 0);
+        // the K-step's four scale bytes of every tile row: one dword per thread, lane-linear behind the wave's base
+        unsigned* ds = sS + buf * (TBM + TBN) + wave * 64;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(scale_is_a ? srd_as : srd_ws, (lds_ptr_t)ds, 4, soff_v, (unsigned)kt * 4u, 0, 0);
+    };
+
+    const int wm = wave % Cfg::NWM, wn = wave / Cfg::NWM;
+    const int lr = lane & 15, lg = lane >> 4;
+
+    f4 acc[NFRAG][MFRAG];
+#pragma unroll
+    for (int a = 0; a < NFRAG; ++a)
+#pragma unroll
+        for (int b = 0; b < MFRAG; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
+
+    const int nk = p.kp / KSTEP;
+    int ltile = blockIdx.x, lkt = 0;
+    int ctile = blockIdx.x, ckt = 0;
+    int tile_m, tile_n;
+    tile_coords(ctile, ntiles, p.tiles_n, tile_m, tile_n);
+    init_load(ltile);
+    load_tile(0, 0);
+    __builtin_amdgcn_s_waitcnt(0x0f70 | 0);   // vmcnt(0): first K-step landed in LDS
+    __syncthreads();
+    int cur = 0;
+    for (;;) {
+        if (++lkt == nk) {
+            lkt = 0;
+            ltile += G;
+            if (ltile < ntiles) init_load(ltile);
+        }
+        const bool more = ltile < ntiles;
+        if (more) load_tile(lkt, cur ^ 1);        // async: lands in the other stage while this one is consumed
+        const unsigned char* cx = sT + cur * Cfg::TILE;
+        const unsigned char* cw = cx + TBM * KSTEP;
+        const unsigned* csx = sS + cur * (TBM + TBN);
+        const unsigned* csw = csx + TBM;
+        auto frag = [&](const unsigned char* base, int row) {      // the lane's 32 K-elements of `row`: 16-byte chunks lg and 4 + lg (see the file header)
+            const i4v lo = *reinterpret_cast<const i4v*>(base + mx_lds_off(row, lg));
+            const i4v hi = *reinterpret_cast<const i4v*>(base + mx_lds_off(row, 4 + lg));
+            return i8v{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        };
+        {
+            i8v xf[MFRAG];
+            int xs[MFRAG];
+#pragma unroll
+            for (int b = 0; b < MFRAG; ++b) {
+                xf[b] = frag(cx, wm * WM + b * 16 + lr);
+                xs[b] = (int)(csx[wm * WM + b * 16 + lr] >> (8 * lg));      // byte 0 = the scale of the lane's own block
+            }
+            i8v wcur = frag(cw, wn * WN + lr);
+            int wscur = (int)(csw[wn * WN + lr] >> (8 * lg));
+#pragma unroll
+            for (int a = 0; a < NFRAG; ++a) {
+                i8v wnext = wcur;
+                int wsnext = wscur;
+                if (a + 1 < NFRAG) {      // the next weight fragment is requested ahead of the MFMAs that use the current one
+                    wnext = frag(cw, wn * WN + (a + 1) * 16 + lr);
+                    wsnext = (int)(csw[wn * WN + (a + 1) * 16 + lr] >> (8 * lg));
+                }
+#pragma unroll
+                for (int b = 0; b < MFRAG; ++b)
+                    acc[a][b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wcur, xf[b], acc[a][b], 0, 0, 0, wscur, 0, xs[b]);
+                wcur = wnext;
+                wscur = wsnext;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (ckt == nk - 1) {
+            if constexpr (EPI == 0) {
+                GemmArgs q{};
+                q.C = p.C;
+                q.bias = p.bias;
+                q.R = p.R;
+                q.M = p.M;
+                q.N = p.N;
+                q.ldc = p.ldc;
+                q.ldr = p.ldr;
+                q.flags = p.flags;
+                q.alpha = 1.0f;
+                q.rowadd_div = 1;
+                q.c_bytes = p.c_bytes;
+                q.r_bytes = p.r_bytes;
+                float* sB = reinterpret_cast<float*>(smem_raw + Cfg::STAGES) + wave * WN;   // the wave's private strip of column addends
+                gemm_epilogue<Cfg, false, false, 0>(q, acc, tile_m, tile_n, wm, wn, lane, sB);
+            } else {
+                mx_geglu_epilogue<Cfg, EPI == 2>(p, acc, tile_m, tile_n, wm, wn, lane);
+            }
+#pragma unroll
+            for (int a = 0; a < NFRAG; ++a)
+#pragma unroll
+                for (int b = 0; b < MFRAG; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
+        }
+        // the DMA of the next K-step must have landed, and every wave must be done reading `cur`, before the roles swap
+        __builtin_amdgcn_s_waitcnt(0x0f70 | 0);
+        __syncthreads();
+        cur ^= 1;
+        if (++ckt == nk) {
+            ckt = 0;
+            ctile += G;
+            if (ctile >= ntiles) break;
+            tile_coords(ctile, ntiles, p.tiles_n, tile_m, tile_n);
+        }
+    }
+#endif
+}
+
+template <class Cfg, int EPI>
+int launch_mx(const MxArgs& a, hipStream_t s) {
+    static VcxLdsAttr lds;
+    auto kern = gemm_mx_kernel<Cfg, EPI>;
+    if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)Cfg::SMEM, "vcx_gemm_mxfp8")) return VCX_ELAUNCH;
+    const int nb = persistent_grid(a.tiles_m * a.tiles_n, 2);
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(Cfg::THREADS), Cfg::SMEM, s, a);
+    return vcx_check_launch("vcx_gemm_mxfp8");
+}
+
+using Cfg128 = MxCfg<128, 128, 2, 2>;
+constexpr unsigned long long LIM = 0xFFFF0000ull;      // 32-bit buffer offsets, as in the fp16 DMA engine
+
+// the epilogue a flag word selects: 0 / 1 / 2 as gemm_mx_kernel's EPI, -1 = a combination this entry point does not have
+int epi_of(int flags) {
+    if (flags == VCX_GEMM_BIAS_N || flags == (VCX_GEMM_BIAS_N | VCX_GEMM_RESIDUAL)) return 0;
+    if (flags == (VCX_GEMM_BIAS_N | VCX_GEMM_GEGLU)) return 1;
+    if (flags == (VCX_GEMM_BIAS_N | VCX_GEMM_GEGLU | VCX_GEMM_MXFP8_OUT)) return 2;
+    return -1;
+}
+
+// shape rules and extents of a call with the given row pitches (elements of the output / residual); `why` gets the reason of a refusal
+bool mx_takes(int64_t M, int64_t N, int64_t K, int flags, int64_t ldc, int64_t ldr, const char** why) {
+    const int epi = epi_of(flags);
+    *why = "flags: BIAS_N, BIAS_N | RESIDUAL, BIAS_N | GEGLU or BIAS_N | GEGLU | MXFP8_OUT";
+    if (epi < 0) return false;
+    *why = "need M, N, K > 0, K % 32 == 0, N % 8 == 0 (GEGLU: N % 64 == 0, whole packed blocks; MXFP8 out: N / 2 % 32 == 0)";
+    if (M <= 0 || N <= 0 || K <= 0 || K % MX_BLOCK != 0 || N % 8 != 0 || (epi && N % 64 != 0)) return false;
+    if (M >= (1ll << 31) || N >= (1ll << 31) || K >= (1ll << 31)) return false;
+    const unsigned long long kp = (unsigned long long)mx_kp(K), nout = epi ? N / 2 : N, kpo = (unsigned long long)mx_kp((int64_t)nout);
+    *why = "an operand, output or residual extent of 4 GiB or more (32-bit buffer offsets)";
+    if ((unsigned long long)M * kp >= LIM || (unsigned long long)N * kp >= LIM) return false;
+    // the tile grid reaches up to 127 rows past M: their offsets must not wrap back into the buffer
+    const unsigned long long mt = (unsigned long long)(M + 127) / 128 * 128;
+    if (mt * kp >= (1ull << 32)) return false;
+    if (epi == 2) return mt * kpo < LIM;
+    if (ldc < (int64_t)nout || mt * (unsigned long long)ldc * 2 >= LIM) return false;
+    if ((flags & VCX_GEMM_RESIDUAL) && (ldr < (int64_t)nout || mt * (unsigned long long)ldr * 2 >= LIM)) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags) {
+    const char* why;
+    const int64_t nout = (flags & VCX_GEMM_GEGLU) ? N / 2 : N;
+    if (mx_takes(M, N, K, flags, nout, nout, &why)) return 1;
+    vcx_set_error("vcx_gemm_mxfp8_ok(M=%lld, N=%lld, K=%lld, flags=0x%x): %s", (long long)M, (long long)N, (long long)K, flags, why);
+    return 0;
+}
+
+extern "C" int vcx_gemm_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, void* out_scales,
+                              const float* bias, const void* residual, int64_t M, int64_t N, int64_t K, int64_t ldc, int64_t ldr, int flags,
+                              void* stream) {
+    const int epi = epi_of(flags);
+    VCX_REQUIRE(a && a_scales && w && w_scales && out && bias, "vcx_gemm_mxfp8: null pointer");
+    VCX_REQUIRE(epi != 2 || out_scales, "vcx_gemm_mxfp8: VCX_GEMM_MXFP8_OUT needs out_scales");
+    VCX_REQUIRE(!(flags & VCX_GEMM_RESIDUAL) || residual, "vcx_gemm_mxfp8: VCX_GEMM_RESIDUAL needs a residual");
+    const char* why;
+    VCX_REQUIRE(mx_takes(M, N, K, flags, ldc, ldr, &why), "vcx_gemm_mxfp8(M=%lld, N=%lld, K=%lld, flags=0x%x, ldc=%lld, ldr=%lld): %s", (long long)M,
+                (long long)N, (long long)K, flags, (long long)ldc, (long long)ldr, why);
+    VCX_REQUIRE((((uintptr_t)a | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)residual) & 15) == 0 && ldc % 8 == 0 && ldr % 8 == 0
+                    && (((uintptr_t)a_scales | (uintptr_t)w_scales | (uintptr_t)out_scales) & 3) == 0,
+                "vcx_gemm_mxfp8: operands, output, bias and residual must be 16-byte aligned (ldc, ldr %% 8 == 0), scale arrays 4-byte aligned");
+    MxArgs p{};
+    p.A = (const unsigned char*)a;
+    p.As = (const unsigned char*)a_scales;
+    p.W = (const unsigned char*)w;
+    p.Ws = (const unsigned char*)w_scales;
+    p.C = out;
+    p.Cs = (unsigned char*)out_scales;
+    p.bias = bias;
+    p.R = (const half_t*)residual;
+    p.M = (int)M;
+    p.N = (int)N;
+    p.kp = (int)mx_kp(K);
+    const int64_t nout = epi ? N / 2 : N;
+    p.kpo = (int)mx_kp(nout);
+    p.ldc = (int)ldc;
+    p.ldr = (int)ldr;
+    p.flags = flags;
+    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
+    p.tiles_n = epi == 2 ? 2 * p.kpo / Cfg128::TBN : (int)((N + Cfg128::TBN - 1) / Cfg128::TBN);
+    p.a_bytes = (unsigned)(M * p.kp);
+    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
+    p.w_bytes = (unsigned)(N * p.kp);
+    p.ws_bytes = (unsigned)(N * (p.kp / MX_BLOCK));
+    p.c_bytes = epi == 2 ? (unsigned)(M * p.kpo) : (unsigned)(2 * ((M - 1) * ldc + nout));
+    p.cs_bytes = epi == 2 ? (unsigned)(M * (p.kpo / MX_BLOCK)) : 0u;
+    p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + nout)) : 0u;
+    hipStream_t s = (hipStream_t)stream;
+    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * K, (double)(M + N) * p.kp + 2.0 * M * nout);
+    switch (epi) {
+        case 0: return launch_mx<Cfg128, 0>(p, s);
+        case 1: return launch_mx<Cfg128, 1>(p, s);
+        default: return launch_mx<Cfg128, 2>(p, s);
+    }
+}

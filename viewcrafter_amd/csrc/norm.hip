@@ -1,5 +1,6 @@
 // GroupNorm (+SiLU) and LayerNorm on channels-last fp16 with fp32 statistics (HBM-bound).
-#include "vcx_common.h"
+#include <type_traits>
+#include "mx_format.h"
 
 namespace {
 
@@ -248,19 +249,11 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ x, const half_t* __re
 // LayerNorm: LPR lanes per row (8..64, chosen so a lane holds <= 4 chunks of 8 channels), the row stays in registers:
 // one HBM read, mean then centred variance from the registers (as torch computes them), one HBM write.
 // ---------------------------------------------------------------------------------------
-// STATS: write (mean, rstd) per row instead of the normalised row - the read-only pass in front of a projection that has the
-// LayerNorm folded into its weights and epilogue (VCX_GEMM_LNFOLD_*): same summation order, hence the same statistics bit for bit.
-template <int LPR, int CPL, bool STATS = false>
-__global__ void __launch_bounds__(256) layernorm_kernel(const half_t* __restrict__ x, half_t* __restrict__ y,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        int64_t rows, int C, float eps) {
-    constexpr int RPB = 256 / LPR;                 // rows per block
-    const int sub = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool rvalid = row < rows;
+// The row's chunks, its statistics and the normalisation of a chunk: ONE body for layernorm_kernel and the LayerNorm-quantiser
+// (layernorm_mx_kernel), whose output is defined as the quantised output of the former, bit for bit.
+template <int LPR, int CPL>
+__device__ __forceinline__ void ln_row_stats(const half_t* __restrict__ xr, int sub, int C, float eps, h8 (&v)[CPL], float& mean, float& rstd) {
     const int nc8 = C >> 3;
-    const half_t* xr = x + (rvalid ? row : 0) * C;
-    h8 v[CPL];
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
@@ -273,7 +266,7 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const half_t* __restrict
     }
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
+    mean = s / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
@@ -287,7 +280,35 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const half_t* __restrict
     }
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = rsqrtf(q / (float)C + eps);
+    rstd = rsqrtf(q / (float)C + eps);
+}
+// the 8 normalised channels of chunk c, rounded to fp16
+__device__ __forceinline__ h8 ln_normalise8(const h8& v, float mean, float rstd, const float* __restrict__ gamma, const float* __restrict__ beta, int c) {
+    const f4 g0 = *reinterpret_cast<const f4*>(gamma + c * 8), g1 = *reinterpret_cast<const f4*>(gamma + c * 8 + 4);
+    const f4 b0 = *reinterpret_cast<const f4*>(beta + c * 8), b1 = *reinterpret_cast<const f4*>(beta + c * 8 + 4);
+    h8 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        o[e] = (half_t)(((float)v[e] - mean) * rstd * g0[e] + b0[e]);
+        o[e + 4] = (half_t)(((float)v[e + 4] - mean) * rstd * g1[e] + b1[e]);
+    }
+    return o;
+}
+
+// STATS: write (mean, rstd) per row instead of the normalised row - the read-only pass in front of a projection that has the
+// LayerNorm folded into its weights and epilogue (VCX_GEMM_LNFOLD_*): same summation order, hence the same statistics bit for bit.
+template <int LPR, int CPL, bool STATS = false>
+__global__ void __launch_bounds__(256) layernorm_kernel(const half_t* __restrict__ x, half_t* __restrict__ y,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        int64_t rows, int C, float eps) {
+    constexpr int RPB = 256 / LPR;                 // rows per block
+    const int sub = threadIdx.x % LPR;
+    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+    const bool rvalid = row < rows;
+    const int nc8 = C >> 3;
+    h8 v[CPL];
+    float mean, rstd;
+    ln_row_stats<LPR, CPL>(x + (rvalid ? row : 0) * C, sub, C, eps, v, mean, rstd);
     if (!rvalid) return;
     if (STATS) {
         if (sub == 0) reinterpret_cast<float2*>(y)[row] = make_float2(mean, rstd);
@@ -297,17 +318,7 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const half_t* __restrict
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
         const int c = sub + j * LPR;
-        if (c < nc8) {
-            const f4 g0 = *reinterpret_cast<const f4*>(gamma + c * 8), g1 = *reinterpret_cast<const f4*>(gamma + c * 8 + 4);
-            const f4 b0 = *reinterpret_cast<const f4*>(beta + c * 8), b1 = *reinterpret_cast<const f4*>(beta + c * 8 + 4);
-            h8 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o[e] = (half_t)(((float)v[j][e] - mean) * rstd * g0[e] + b0[e]);
-                o[e + 4] = (half_t)(((float)v[j][e + 4] - mean) * rstd * g1[e] + b1[e]);
-            }
-            *reinterpret_cast<h8*>(yr + c * 8) = o;
-        }
+        if (c < nc8) *reinterpret_cast<h8*>(yr + c * 8) = ln_normalise8(v[j], mean, rstd, gamma, beta, c);
     }
 }
 
@@ -319,24 +330,75 @@ void launch_ln(const half_t* x, half_t* y, const float* g, const float* b, int64
     else hipLaunchKernelGGL((layernorm_kernel<LPR, CPL, true>), grid, dim3(256), 0, s, x, y, g, b, rows, C, eps);   // y = float2 stats
 }
 
-void dispatch_ln(const half_t* xp, half_t* yp, const float* gamma, const float* beta, int64_t rows, int C, float eps, hipStream_t s) {
+// The (lanes per row, chunks per lane) geometry of a LayerNorm over C channels, handed to `f` as two integral constants: ONE table for
+// the LayerNorm kernel and for the LayerNorm-quantiser below, whose statistics must sum in the same order.
+template <int V> using ln_ic = std::integral_constant<int, V>;
+template <class F>
+void with_ln_geometry(int C, F&& f) {
     const int nc8 = C >> 3;
     // C = 320 and C = 640 (the token widths of levels 0 / 1): half the lanes per row and five 16-byte chunks per lane - 5 loads in flight
     // per thread, 32 / 16 rows per block - measured 3-8 % faster than the 3-chunk forms on those widths (profiles/r04o_ln_variants.txt;
     // twice the lanes per row is 20-40 % slower)
-    if (nc8 > 32 && nc8 <= 40) return launch_ln<8, 5>(xp, yp, gamma, beta, rows, C, eps, s);
-    if (nc8 > 64 && nc8 <= 80) return launch_ln<16, 5>(xp, yp, gamma, beta, rows, C, eps, s);
-    if (nc8 <= 8) launch_ln<8, 1>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 16) launch_ln<8, 2>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 32) launch_ln<16, 2>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 48) launch_ln<16, 3>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 64) launch_ln<16, 4>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 96) launch_ln<32, 3>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 128) launch_ln<32, 4>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 192) launch_ln<64, 3>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 256) launch_ln<64, 4>(xp, yp, gamma, beta, rows, C, eps, s);
-    else if (nc8 <= 512) launch_ln<64, 8>(xp, yp, gamma, beta, rows, C, eps, s);
-    else launch_ln<64, 16>(xp, yp, gamma, beta, rows, C, eps, s);
+    if (nc8 > 32 && nc8 <= 40) return f(ln_ic<8>{}, ln_ic<5>{});
+    if (nc8 > 64 && nc8 <= 80) return f(ln_ic<16>{}, ln_ic<5>{});
+    if (nc8 <= 8) f(ln_ic<8>{}, ln_ic<1>{});
+    else if (nc8 <= 16) f(ln_ic<8>{}, ln_ic<2>{});
+    else if (nc8 <= 32) f(ln_ic<16>{}, ln_ic<2>{});
+    else if (nc8 <= 48) f(ln_ic<16>{}, ln_ic<3>{});
+    else if (nc8 <= 64) f(ln_ic<16>{}, ln_ic<4>{});
+    else if (nc8 <= 96) f(ln_ic<32>{}, ln_ic<3>{});
+    else if (nc8 <= 128) f(ln_ic<32>{}, ln_ic<4>{});
+    else if (nc8 <= 192) f(ln_ic<64>{}, ln_ic<3>{});
+    else if (nc8 <= 256) f(ln_ic<64>{}, ln_ic<4>{});
+    else if (nc8 <= 512) f(ln_ic<64>{}, ln_ic<8>{});
+    else f(ln_ic<64>{}, ln_ic<16>{});
+}
+
+void dispatch_ln(const half_t* xp, half_t* yp, const float* gamma, const float* beta, int64_t rows, int C, float eps, hipStream_t s) {
+    with_ln_geometry(C, [&](auto lpr, auto cpl) { launch_ln<decltype(lpr)::value, decltype(cpl)::value>(xp, yp, gamma, beta, rows, C, eps, s); });
+}
+
+// LayerNorm + MXFP8 quantiser in one pass (vcx_layernorm_mxfp8_f16): layernorm_kernel's thread geometry and its two helpers above - the same
+// loads, statistics and normalisation, every normalised value rounded to fp16 as that kernel stores it - then the 32-element blocks of
+// those fp16 values are quantised (mx_format.h): quant(vcx_layernorm_f16(x)) bit for bit, without the fp16 row in memory.  Chunk c of a
+// row is in lane c % LPR (LPR % 4 == 0): the four chunks of a block are four neighbouring lanes at the same j.
+template <int LPR, int CPL>
+__global__ void __launch_bounds__(256) layernorm_mx_kernel(const half_t* __restrict__ x, unsigned char* __restrict__ qo, unsigned char* __restrict__ so,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           int64_t rows, int C, int kp, float eps) {
+    using namespace vcxmx;
+    constexpr int RPB = 256 / LPR;                 // rows per block
+    const int sub = threadIdx.x % LPR;
+    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+    const bool rvalid = row < rows;
+    const int nc8 = C >> 3;
+    h8 v[CPL];
+    float mean, rstd;
+    ln_row_stats<LPR, CPL>(x + (rvalid ? row : 0) * C, sub, C, eps, v, mean, rstd);
+    unsigned char* qr = qo + (rvalid ? row : 0) * (int64_t)kp;
+    unsigned char* sr = so + (rvalid ? row : 0) * (int64_t)(kp / MX_BLOCK);
+    // every lane walks every j (no early return): the quad exchange of a block's maximum needs its four lanes, and C % 32 == 0 makes a
+    // quad real or absent as a whole
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        const int c = sub + j * LPR;
+        const bool real = c < nc8;
+        h8 o = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (real) o = ln_normalise8(v[j], mean, rstd, gamma, beta, c);
+        const unsigned hmax = mx_quad_max(mx_absmax_bits(o));
+        float mul;
+        const unsigned sb = mx_scale_byte(hmax, mul);
+        if (real && rvalid) {
+            *reinterpret_cast<uint2*>(qr + c * 8) = mx_quant8(o, sb, mul);
+            if ((c & 3) == 0) sr[c >> 2] = (unsigned char)sb;
+        }
+    }
+    // padding up to kp: zero elements under the scale byte 127
+    if (rvalid)
+        for (int c = nc8 + sub; c < (kp >> 3); c += LPR) {
+            *reinterpret_cast<uint2*>(qr + c * 8) = make_uint2(0u, 0u);
+            if ((c & 3) == 0) sr[c >> 2] = (unsigned char)MX_SCALE_ONE;
+        }
 }
 
 // thread geometry shared by the two GroupNorm kernels: cw channel chunks x pl pixel lanes, ~320 threads
@@ -648,6 +710,24 @@ extern "C" int vcx_layernorm_f16(const void* x, void* y, const float* gamma, con
     VcxProfScope prof(VCX_FAM_LN, s, 0.0, 4.0 * rows * (double)C);
     dispatch_ln((const half_t*)x, (half_t*)y, gamma, beta, rows, C, eps, s);
     return vcx_check_launch("vcx_layernorm_f16");
+}
+
+extern "C" int vcx_layernorm_mxfp8_f16(const void* x, void* q, void* scales, const float* gamma, const float* beta, int64_t rows, int C,
+                                       float eps, void* stream) {
+    VCX_REQUIRE(x && q && scales && gamma && beta, "vcx_layernorm_mxfp8_f16: null pointer");
+    VCX_REQUIRE(rows > 0 && C > 0 && C % 32 == 0, "vcx_layernorm_mxfp8_f16: need C %% 32 == 0 (C=%d)", C);
+    VCX_REQUIRE((((uintptr_t)x | (uintptr_t)q | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0 && ((uintptr_t)scales & 3) == 0,
+                "vcx_layernorm_mxfp8_f16: pointers must be 16-byte aligned (scales: 4-byte)");
+    VCX_REQUIRE(rows < (1ll << 31) && C <= 8192, "vcx_layernorm_mxfp8_f16: too many rows or C > 8192");
+    hipStream_t s = (hipStream_t)stream;
+    const int kp = (int)vcxmx::mx_kp(C);
+    VcxProfScope prof(VCX_FAM_LN, s, 0.0, rows * (2.0 * C + kp + kp / 32.0));
+    with_ln_geometry(C, [&](auto lpr, auto cpl) {
+        constexpr int LPR = decltype(lpr)::value, CPL = decltype(cpl)::value;
+        hipLaunchKernelGGL((layernorm_mx_kernel<LPR, CPL>), dim3((unsigned)((rows + 256 / LPR - 1) / (256 / LPR))), dim3(256), 0, s, (const half_t*)x,
+                           (unsigned char*)q, (unsigned char*)scales, gamma, beta, rows, C, kp, eps);
+    });
+    return vcx_check_launch("vcx_layernorm_mxfp8_f16");
 }
 
 extern "C" int vcx_rowstats_f16(const void* x, float* stats, int64_t rows, int C, float eps, void* stream) {

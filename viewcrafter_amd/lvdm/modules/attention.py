@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from ... import ops
-from ...packing import fold_layernorm, pack_geglu
+from ...packing import fold_layernorm, pack_geglu, pack_mxfp8
 from ..common import default
 from .flow import GN_STATS_LEVEL, out_kwargs
 
@@ -41,6 +41,16 @@ FOLD_LAYERNORM = os.environ.get("VCX_LN_FOLD", "1") != "0"
 # everywhere: GEMM +1.0 ms, step level; round 3: profiles/r03_experiments.md section 8).  VCX_LN_FOLD_FF=0: never; VCX_LN_FOLD_FF_MIN_DIM: the width.
 FOLD_LAYERNORM_FF = os.environ.get("VCX_LN_FOLD_FF", "1") != "0"
 FOLD_LAYERNORM_FF_MIN_DIM = int(os.environ.get("VCX_LN_FOLD_FF_MIN_DIM", "640"))
+# Opt-in (VCX_FF_MXFP8=1, default off): the two linears of the GEGLU feed-forward on the block-scaled MXFP8 matrix pipe (include/vcx.h "MXFP8
+# operands", csrc/gemm_mx.hip) - LayerNorm + quantiser in one pass, GEGLU projection with MXFP8 output, ff.2 with bias and residual reading
+# those bytes.  The LayerNorm is APPLIED, not folded: quantising the raw stream and subtracting mean x colsum afterwards would amplify
+# the quantisation error.  Accuracy with a real checkpoint is unmeasured; what was measured is in profiles/mxfp8_ff.md.  Off: no new
+# launch, no new allocation, every output bit as before.
+FF_MXFP8 = os.environ.get("VCX_FF_MXFP8", "0") == "1"
+# Widths whose feed-forward stays on the fp16 route although the switch is on.  320 (level 0) by default: isolated, its GEGLU projection is
+# slower in MXFP8 than on the weight-stationary fp16 kernel (1.08 against 0.98 ms at 460800 rows; the pair 1.49 against 1.45 ms), while
+# the 640- and 1280-wide pairs are 1.25x / 1.29x faster (profiles/mxfp8_ff.md).  VCX_FF_MXFP8_SKIP_DIMS="" puts every width on MX.
+FF_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_FF_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
 
 
 # TemporalTransformer.norm -> proj_in (reference attention.py:331-336,369-372) and SpatialTransformer.norm -> proj_in (:265-269,299):
@@ -284,9 +294,26 @@ class FeedForward(PackedModule):
         colsum = None if p1["colsum"] is None else pack_geglu(p1["w"], p1["colsum"])[1]
         return dict(w1=w1, b1=b1, colsum=colsum, w2=_f16(self.net[2].weight), b2=_f32(self.net[2].bias))
 
+    def _mx_ok(self, t):
+        """FF_MXFP8: does vcx_gemm_mxfp8 take BOTH linears at this row count (its own predicate)?  Either side refusing keeps the fp16 route."""
+        proj, out = self.net[0].proj, self.net[2]
+        rows = t.shape[0]
+        return (self.dim not in FF_MXFP8_SKIP_DIMS and t.is_contiguous() and proj.bias is not None and out.bias is not None
+                and ops.linear_mxfp8_ok(rows, proj.out_features, self.dim, geglu=True, mx_out=True)
+                and ops.linear_mxfp8_ok(rows, out.out_features, out.in_features, residual=True))
+
     def run(self, t, ln_params):
         """t + FF(LayerNorm(t)); ln_params = (gamma, beta, eps) of the LayerNorm in front (used when it is not folded into w1)."""
         pk = self.packed()
+        if FF_MXFP8 and self._mx_ok(t):
+            if "mx" not in pk:          # built lazily beside the fp16 packs, from the un-folded weights
+                proj = self.net[0].proj
+                w1, b1 = pack_geglu(_f16(proj.weight), _f32(proj.bias))
+                pk["mx"] = dict(w1=pack_mxfp8(w1), b1=b1, w2=pack_mxfp8(pk["w2"]))
+            mx = pk["mx"]
+            a = ops.layer_norm_mxfp8(t, *ln_params)
+            g = ops.linear_mxfp8(a, mx["w1"], mx["b1"], K=self.dim, geglu=True, mx_out=True)
+            return ops.linear_mxfp8(g, mx["w2"], pk["b2"], K=pk["w2"].shape[1], residual=t)
         if pk["colsum"] is not None and ops.lnfold_ok(t.shape[0], pk["w1"].shape[0], t.shape[1], lda=t.stride(0)):
             g = ops.linear(t, pk["w1"], pk["b1"], geglu=True, ln_stats=ops.row_stats(t, ln_params[2]), ln_colsum=pk["colsum"])
         else:

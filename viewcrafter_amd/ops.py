@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from ._lib import (GEMM_BIAS_M, GEMM_BIAS_N, GEMM_COLSTATS, GEMM_CONV_SLABK, GEMM_GEGLU, GEMM_LNFOLD, GEMM_LNFOLD_T, GEMM_OUT_F32, GEMM_RESIDUAL, GEMM_ROWADD, GEMM_ROWSTATS, PROF_FAMILIES,
+from ._lib import (GEMM_BIAS_M, GEMM_BIAS_N, GEMM_COLSTATS, GEMM_CONV_SLABK, GEMM_GEGLU, GEMM_LNFOLD, GEMM_LNFOLD_T, GEMM_MXFP8_OUT, GEMM_OUT_F32, GEMM_RESIDUAL, GEMM_ROWADD, GEMM_ROWSTATS, PROF_FAMILIES,
                    ROUTE_UNITS_GROUPED, ROUTE_UNITS_LOOP, ROUTE_UNITS_WS320, TUNE, GemmDesc, VcxError, check, lib)
 from .packing import conv_slab_major
 
@@ -396,6 +396,89 @@ def layer_norm(x, gamma, beta, eps=1e-5):
     out = torch.empty_like(x)
     check(lib().vcx_layernorm_f16(x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rows, C, eps,
                                   _stream()), "layernorm")
+    return out
+
+
+# ------------------------------------------------------------------------------------------
+# MXFP8 operands (include/vcx.h "MXFP8 operands"; opt-in: the GEGLU feed-forward under VCX_FF_MXFP8=1)
+# ------------------------------------------------------------------------------------------
+_u8 = torch.uint8
+
+
+def mx_kp(K):
+    """K extent of an MXFP8 buffer: K rounded up to a multiple of 128."""
+    return (K + 127) // 128 * 128
+
+
+def _mx_buffers(rows, K, device):
+    kp = mx_kp(K)
+    return torch.empty((rows, kp), dtype=_u8, device=device), torch.empty((rows, kp // 32), dtype=_u8, device=device)
+
+
+def _dev_mx(pair, rows, K, what):
+    q, s = pair
+    kp = mx_kp(K)
+    for t, shape in ((q, (rows, kp)), (s, (rows, kp // 32))):
+        if t.dtype is not _u8 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
+            raise VcxError(f"{what}: expected contiguous GPU uint8 {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def quant_mxfp8(x):
+    """x [rows, K] fp16 (row stride may exceed K) -> (element bytes [rows, Kp], scale bytes [rows, Kp / 32])."""
+    rows, K = x.shape
+    _dev16(x)
+    if x.stride(1) != 1:
+        raise VcxError("quant_mxfp8: unit column stride needed")
+    q, s = _mx_buffers(rows, K, x.device)
+    check(lib().vcx_quant_mxfp8_f16(x.data_ptr(), x.stride(0), q.data_ptr(), s.data_ptr(), rows, K, _stream()), "quant_mxfp8")
+    return q, s
+
+
+def layer_norm_mxfp8(x, gamma, beta, eps=1e-5):
+    """quant_mxfp8(layer_norm(x, gamma, beta, eps)), bit for bit, in one pass: the normalised fp16 rows are never written."""
+    rows, C = x.shape
+    _dev16(x)
+    _dev32(gamma, beta)
+    if not x.is_contiguous():
+        raise VcxError("layer_norm_mxfp8: dense rows needed")
+    q, s = _mx_buffers(rows, C, x.device)
+    check(lib().vcx_layernorm_mxfp8_f16(x.data_ptr(), q.data_ptr(), s.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rows, C, eps, _stream()),
+          "layernorm_mxfp8")
+    return q, s
+
+
+def _mx_flags(residual=False, geglu=False, mx_out=False):
+    return GEMM_BIAS_N | (GEMM_RESIDUAL if residual else 0) | (GEMM_GEGLU if geglu else 0) | (GEMM_MXFP8_OUT if mx_out else 0)
+
+
+def linear_mxfp8_ok(rows, N, K, *, residual=False, geglu=False, mx_out=False):
+    """Does vcx_gemm_mxfp8 take `rows` rows x K onto N (packed, for GEGLU) weight rows with this epilogue?  The library's answer."""
+    return lib().vcx_gemm_mxfp8_ok(rows, N, K, _mx_flags(residual, geglu, mx_out)) == 1
+
+
+def linear_mxfp8(a, w, bias, *, K, residual=None, geglu=False, mx_out=False):
+    """a, w: (element bytes, scale bytes) pairs of [rows, K] and [N, K] matrices (quant_mxfp8 / layer_norm_mxfp8 / a mx_out=True
+    layer; packing.pack_mxfp8).  Returns fp16 [rows, N] = a w^T + bias (+ residual), or with geglu=True (w and bias packed by
+    packing.pack_geglu) fp16 [rows, N / 2] = x * gelu(gate) - with mx_out=True that result as an MXFP8 pair, the next layer's operand."""
+    rows, N = a[0].shape[0], w[0].shape[0]
+    _dev_mx(a, rows, K, "linear_mxfp8 a")
+    _dev_mx(w, N, K, "linear_mxfp8 w")
+    _dev32(bias)
+    _dev16(residual)
+    if bias is None or bias.numel() != N or not bias.is_contiguous() or (mx_out and not geglu):
+        raise VcxError(f"linear_mxfp8: a contiguous fp32 bias [N = {N}] is required; mx_out goes with geglu")
+    n_out = N // 2 if geglu else N
+    if residual is not None and (tuple(residual.shape) != (rows, n_out) or residual.stride(1) != 1):
+        raise VcxError(f"linear_mxfp8: residual must be [{rows}, {n_out}] with unit column stride, got {tuple(residual.shape)}")
+    if mx_out:
+        out = _mx_buffers(rows, n_out, a[0].device)
+        c, cs = out[0].data_ptr(), out[1].data_ptr()
+    else:
+        out = torch.empty((rows, n_out), dtype=_f16, device=a[0].device)
+        c, cs = out.data_ptr(), None
+    check(lib().vcx_gemm_mxfp8(a[0].data_ptr(), a[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(), c, cs, bias.data_ptr(), _ptr(residual), rows, N, K,
+                               n_out, residual.stride(0) if residual is not None else 0, _mx_flags(residual is not None, geglu, mx_out), _stream()),
+          "gemm_mxfp8")
     return out
 
 

@@ -2,7 +2,8 @@
 
 Reference layouts (binding because checkpoints are loaded with strict=True):
 conv weights [Cout, Cin, kh, kw] / [Cout, Cin, 3, 1, 1] / [Cout, Cin, 1], linear [out, in].
-Kernel layouts: fp16 [N_out][K] with K ordered (tap, cin); GEGLU rows interleaved in blocks of 32.
+Kernel layouts: fp16 [N_out][K] with K ordered (tap, cin); GEGLU rows interleaved in blocks of 32; MXFP8 (opt-in feed-forward):
+element bytes [N_out][Kp] + scale bytes [N_out][Kp / 32].
 """
 import torch
 
@@ -58,3 +59,31 @@ def fold_layernorm(w, gamma, beta, bias=None):
     if bias is not None:
         bias_f = bias_f + bias.detach().float()
     return wf.contiguous(), colsum.contiguous(), bias_f.contiguous()
+
+
+def pack_mxfp8(w):
+    """fp16 [rows, K] (K % 32 == 0) -> (element bytes uint8 [rows, Kp], scale bytes uint8 [rows, Kp / 32]), Kp = K rounded up to 128: the
+    MXFP8 format of include/vcx.h ("MXFP8 operands") for weights, computed once at pack time with integer arithmetic on the fp16 bit
+    patterns - byte for byte what vcx_quant_mxfp8_f16 writes for the same values (tests/test_mxfp8_gpu.py).  Runs on the host (the
+    fp8 cast of every torch build, no device kernel) and returns tensors on w's device."""
+    if w.dtype is not torch.float16 or w.dim() != 2 or w.shape[1] % 32 != 0:
+        raise ValueError(f"pack_mxfp8: need an fp16 [rows, K] matrix with K % 32 == 0, got {w.dtype} {tuple(w.shape)}")
+    rows, K = w.shape
+    kp = (K + 127) // 128 * 128
+    x = w.detach().cpu().contiguous()
+    mag = (x.view(torch.int16).to(torch.int32) & 0x7FFF).view(rows, K // 32, 32).amax(dim=2)        # fp16 magnitudes order like their bits
+    expo = mag >> 10
+    lead = torch.zeros_like(mag)                     # position of a subnormal's leading mantissa bit
+    for bit in range(1, 10):
+        lead = torch.where(mag >> bit > 0, torch.full_like(mag, bit), lead)
+    E = torch.where(expo > 0, expo - 15, lead - 24)
+    bad, zero = mag >= 0x7C00, mag == 0
+    scale = torch.where(bad, torch.full_like(E, 255), torch.where(zero, torch.zeros_like(E), E + 119))
+    mul = torch.ldexp(torch.ones((), dtype=torch.float32), torch.where(bad | zero, torch.zeros_like(E), 8 - E))
+    y = (x.float().view(rows, K // 32, 32) * mul[..., None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    y = torch.where(bad[..., None], torch.full_like(y, 0x7F), y)
+    q = torch.zeros((rows, kp), dtype=torch.uint8)
+    q[:, :K] = y.view(rows, K)
+    s = torch.full((rows, kp // 32), 127, dtype=torch.uint8)
+    s[:, :K // 32] = scale.to(torch.uint8)
+    return q.to(w.device), s.to(w.device)
