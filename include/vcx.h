@@ -38,8 +38,9 @@ extern "C" {
  * vcx_add_nchw_f32_to_nhwc_f16.  6: vcx_ddim_ws_bytes, ws_bytes argument of the DDIM steps.  7: vcx_groupnorm_fold_linear_f16,
  * vcx_gemm_units_f16, vcx_attn_flash_d512_f16.  8: vcx_gemm_desc grows rowstats / rowstats_eps (VCX_GEMM_ROWSTATS) and
  * tail_a0 / tail_a1 (K tail of a convolution from linear sources); vcx_groupnorm_apply2_f16.  10: vcx_gemm_route.  11: MXFP8 operands - vcx_quant_mxfp8_f16,
- * vcx_layernorm_mxfp8_f16, vcx_gemm_mxfp8, vcx_gemm_mxfp8_ok; VCX_GEMM_MXFP8_OUT. */
-#define VCX_ABI_VERSION 11
+ * vcx_layernorm_mxfp8_f16, vcx_gemm_mxfp8, vcx_gemm_mxfp8_ok; VCX_GEMM_MXFP8_OUT.  12: ups = 2 (nearest-2x + 3x3 convolution folded into
+ * four 2x2 weight sets on the tiled engine). */
+#define VCX_ABI_VERSION 12
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -67,6 +68,15 @@ int vcx_device_arch(char* name_host, int len);
  * [0, in_h<<ups) x [0, in_w<<ups)  (ups=1 fuses F.interpolate(scale_factor=2,'nearest'),
  * openaimodel3d.py:100-103, ae_modules.py:124).  A temporal (3,1,1) convolution is the
  * same gather with in_h = T, in_w = H*W, kh = 3, kw = 1, pad_h = 1, pad_w = 0.
+ * ups = 2 (ABI 12): the same nearest-2x + 3x3 / padding 1 layer in its folded form.  The nine taps of output pixel (2i + a, 2j + b)
+ * land on 2x2 source pixels - rows (i - 1 + a, i + a), columns (j - 1 + b, j + b) - so the layer is four 2x2 convolutions on the
+ * source grid, one per parity class c = 2a + b, whose weights are sums of the original taps (viewcrafter_amd/packing.py
+ * pack_conv_ups_folded): 4/9 of the multiply-adds.  W = four dense sets [4][N][ldw], each packed like a 2x2 kernel in slab-major
+ * order; kh = kw = 2, stride = 1, K = 4 cin, in_h x in_w the source, out_h x out_w = 2 in_h x 2 in_w the result, M = n out_h out_w
+ * (pad_h / pad_w are not read).  Output, ldc and colstats are those of the ups = 1 call; the column moments group other pixels into
+ * a strip, so they differ from that call's in the last bits.  The tiled engine alone runs it (vcx_gemm_route: VCX_ROUTE_TILED): in_w % 16 == 0,
+ * in_h in_w % 64 == 0, cin % 64 == 0, N % 8 == 0, BIAS_N / COLSTATS at most, 32-bit extents, GEMM_CFG unset or 0..3; anything else is
+ * refused (VCX_ROUTE_REFUSED / VCX_EINVAL) and the caller runs ups = 1 with the nine-tap weights.
  * ---------------------------------------------------------------------------------- */
 #define VCX_GEMM_BIAS_N 0x1     /* + bias[n]                                              */
 #define VCX_GEMM_BIAS_M 0x2     /* + bias[m]  (used for the transposed V projection)     */

@@ -100,7 +100,7 @@ def make_problem(key):
         a = torch.randn(n_img * d["in_h"] * d["in_w"], d["lda"], device="cuda").half()
     else:
         a = torch.randn(M, d["lda"], device="cuda").half()
-    w = (torch.randn(N, d["ldw"], device="cuda") / K ** 0.5).half()
+    w = (torch.randn((4 * N if conv and d["ups"] == 2 else N), d["ldw"], device="cuda") / K ** 0.5).half()      # ups = 2: four weight sets, one per parity class
     n_out = N // 2 if flags & 16 else N
     out = torch.empty(M, max(d["ldc"], n_out), device="cuda", dtype=torch.float32 if flags & 32 else torch.float16)
     bias = torch.randn(max(M, N) if flags & 2 else N, device="cuda") if flags & 3 else None
@@ -158,7 +158,7 @@ def main():
     cum = 0.0
     for r in rows:
         cum += r["total_ms"]
-        kind = (f"conv{r['kh']}x{r['kw']}" + ("s2" if r["stride"] == 2 else "") + ("u" if r["ups"] else "") + ("+t" if r.get("tail_k0") else "") if r["mode"] == 1
+        kind = (f"conv{r['kh']}x{r['kw']}" + ("s2" if r["stride"] == 2 else "") + ("u" if r["ups"] == 1 else "uf" if r["ups"] == 2 else "") + ("+t" if r.get("tail_k0") else "") if r["mode"] == 1
                 else f"units/{r['M'] // r['in_h']}" if r["mode"] == 2 else "linear")
         print(f"{r['count']:4d} {r['M']:8d} {r['N']:6d} {r['K']:6d} {kind:>10} {r['flags']:5d} {r['ms']:8.3f} {r['total_ms']:8.2f} {r['tflops']:7.0f} {100*cum/tot:6.1f} {r['floor_ms']:7.3f} {'hbm' if r['hbm_bound'] else 'mfma':>5} {(r['ms'] - r['floor_ms']) * r['count']:7.2f}")
     if args.json:

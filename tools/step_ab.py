@@ -10,6 +10,7 @@ A variant is  name:key=value,key=value  with keys
     xattn    1 | 2   resident cross-attention kernel: second form | first form (knob XATTN_RESIDENT)
     ws       1 | 0   weight-stationary K = 320 kernel (knob GEMM_WS)
     lnrs     1 | 0   LayerNorm statistics from the producing layer's epilogue (VCX_GEMM_ROWSTATS; ops.LN_ROWSTATS)
+    upsfold  1 | 0   Upsample convolutions as four 2x2 weight sets on the source grid (ops.UPS_FOLD; 0 = the nine-tap ups = 1 call)
 e.g.   base:gnfold=0,xattn=2  gnfold:gnfold=1,xattn=2  xattn2:gnfold=0,xattn=1  all:gnfold=1,xattn=1
 --lib runs everything on another build of the library of the SAME ABI (e.g. tools/_abl/libvcx_gelu_select.so, built by
 tools/build_abl.sh): a library-level change is then compared across two invocations on the same box."""
@@ -77,6 +78,7 @@ def main():
         ops.tune_set("XATTN_RESIDENT", int(settings.get("xattn", "1")))
         ops.tune_set("GEMM_WS", int(settings.get("ws", "1")))
         ops.LN_ROWSTATS = settings.get("lnrs", "1") != "0"
+        ops.UPS_FOLD = settings.get("upsfold", "1") != "0"
 
     def run(settings, steps, profile):
         apply(settings)

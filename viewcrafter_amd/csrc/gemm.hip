@@ -560,8 +560,10 @@ static int validate(const vcx_gemm_desc* d, bool ptrs) {
                     "vcx_gemm_f16: conv needs cin %% 8 == 0 and K == kh*kw*cin + tail (cin=%d kh=%d kw=%d K=%d tail=%d+%d)", d->cin,
                     d->kh, d->kw, d->K, d->tail_k0, d->tail_k1);
         VCX_REQUIRE(d->out_h > 0 && d->out_w > 0 && d->in_h > 0 && d->in_w > 0 && d->stride > 0 &&
-                        (d->ups == 0 || d->ups == 1) && d->M % (d->out_h * d->out_w) == 0,
+                        (d->ups == 0 || d->ups == 1 || d->ups == 2) && d->M % (d->out_h * d->out_w) == 0,
                     "vcx_gemm_f16: bad conv geometry");
+        VCX_REQUIRE(d->ups != 2 || (d->kh == 2 && d->kw == 2 && d->stride == 1 && d->out_h == 2 * d->in_h && d->out_w == 2 * d->in_w && d->tail_k0 + d->tail_k1 == 0),
+                    "vcx_gemm_f16: ups = 2 (folded nearest-2x + 3x3) is four 2x2 weight sets on the source grid: kh = kw = 2, stride 1, out = 2 x in, no K tail");
     }
     const int tail = conv ? d->tail_k0 + d->tail_k1 : 0;
     VCX_REQUIRE(conv || (d->tail_k0 == 0 && d->tail_k1 == 0), "vcx_gemm_f16: a K tail (tail_k0 / tail_k1) belongs to a convolution (mode 1)");
@@ -610,6 +612,7 @@ static Knobs read_knobs(int unit_rows) {
 struct GemmRoute {
     int kind;                    // VCX_ROUTE_* (include/vcx.h)
     int epi;                     // TILED / UNITS_GROUPED: the epilogue kind plan_tiles chooses configurations by
+    bool ups_folded;             // TILED: the folded upsample convolution (ups = 2) - its four parity classes as units of the plan
     unsigned long long a_bytes, w_bytes, c_bytes, r_bytes, a2_bytes, a3_bytes;      // operand / output extents (w_bytes: of ONE unit's weights)
     char why[384];               // REFUSED: the text for vcx_last_error
 };
@@ -627,6 +630,7 @@ static GemmRoute& refuse(GemmRoute& r, const char* fmt, ...) {
 static GemmRoute gemm_route(const vcx_gemm_desc& d, int unit_rows, const Knobs& k) {
     GemmRoute r;
     r.why[0] = 0;
+    r.ups_folded = false;
     const int flags = d.flags;
     const bool conv = d.mode == 1, geglu = flags & VCX_GEMM_GEGLU, f32 = flags & VCX_GEMM_OUT_F32;
     const int lnf = (flags & VCX_GEMM_LNFOLD) ? 1 : (flags & VCX_GEMM_LNFOLD_T) ? 2 : 0;
@@ -670,6 +674,22 @@ static GemmRoute gemm_route(const vcx_gemm_desc& d, int unit_rows, const Knobs& 
     }
 
     // ---- vcx_gemm_f16
+    // Folded nearest-2x + 3x3 convolution (ups = 2; gemm_dma.hip UPSF): the four parity classes as four units of the tiled engine.  What
+    // its gather, store and moment arithmetic rest on: whole 16-row fragments inside a source row, whole 64-row strips inside an image,
+    // block-uniform taps in slab-major order, the plain bias epilogue (column moments at most), a 128- or 256-row configuration.  Any
+    // other shape is refused: the caller keeps the nine-tap weights and runs ups = 1.
+    if (conv && d.ups == 2) {
+        const long long hw = (long long)d.in_h * d.in_w;
+        if (dma_ok && d.in_w % 16 == 0 && hw % 64 == 0 && d.cin % 64 == 0 && d.N % 8 == 0 && (flags & VCX_GEMM_CONV_SLABK) &&
+            !(flags & ~(VCX_GEMM_CONV_SLABK | VCX_GEMM_BIAS_N | VCX_GEMM_COLSTATS)) && d.alpha == 1.0f && k.cfg <= 3 && 4ull * r.w_bytes < lim &&
+            (unsigned long long)d.N * d.ldw * 2ull * 3ull + r.w_bytes < lim) {
+            r.ups_folded = true;
+            r.epi = EPI_PLAIN_ONLY128;      // no 64-row tail configuration has the folded form
+            return take(r, VCX_ROUTE_TILED);
+        }
+        return refuse(r, "vcx_gemm_f16: the folded upsample convolution (ups = 2) needs in_w %% 16 == 0, in_h in_w %% 64 == 0, cin %% 64 == 0, N %% 8 == 0, slab-major K, "
+                         "a bias / column-moment epilogue, extents < 4 GiB, and GEMM_CFG <= 3; in %dx%d cin=%d N=%d flags=0x%x", d.in_h, d.in_w, d.cin, d.N, flags);
+    }
     if ((k2 || k3) && !dma_ok)
         return refuse(r, "vcx_gemm_f16: a K tail needs the DMA kernel (cin %% 64 == 0, K %% 64 == 0, N %% 8 == 0, extents < 4 GiB); cin=%d K=%d N=%d", d.cin, d.K, d.N);
     // Weight-stationary kernel (gemm_ws.hip) for the memory-bound K = 320 linear layers of level 0 (N = 320, 640, 960): the weight stays
@@ -811,6 +831,13 @@ static int run(const vcx_gemm_desc& d, const GemmRoute& r, const Knobs& k, int u
     case VCX_ROUTE_WS320: return launch_ws320(a, s);
     case VCX_ROUTE_UNITS_WS320: return launch_ws320_units(a, s);
     case VCX_ROUTE_TILED:
+        if (r.ups_folded) {
+            // the four parity classes as units of M / 4 = n in_h in_w rows on the source grid, class c's weights at W + c N ldw
+            a.unit_rows = d.M / 4; a.units = 4; a.w_unit_stride = (int64_t)d.N * d.ldw; a.bias_unit_stride = 0;
+            a.out_h = d.in_h; a.out_w = d.in_w; a.ups = 0;
+            return run_plan(a, tile_plan(d, r, k.cfg, a.unit_rows), conv, s);
+        }
+        [[fallthrough]];
     case VCX_ROUTE_UNITS_GROUPED: return run_plan(a, tile_plan(d, r, k.cfg, unit_rows), conv, s);
     default: return !geglu && d.N % 160 == 0 ? dispatch<160>(a, conv, geglu, f32, s) : dispatch<128>(a, conv, geglu, f32, s);
     }

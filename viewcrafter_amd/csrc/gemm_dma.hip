@@ -60,7 +60,14 @@ struct TileCfg {
 // A tile's unit moves the base of the W descriptor (scalar arithmetic in init_load, ahead of the tile's first DMA) and of the bias, and
 // bounds the output descriptor at the unit's end: the ragged last tile of a unit READS rows of the next unit and stores none of them.
 // Own instantiations, like TAIL.
-template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false, bool UNITS = false>
+// UPSF (round 11, convolutions, fp16 output, bias epilogue with or without column moments; include/vcx.h ups = 2): nearest-2x + 3x3 folded
+// into four 2x2 convolutions on the SOURCE grid, one per output parity class (a, b).  GEMM rows are (class, image, i, j): four units of
+// p.unit_rows = n H W rows on the per-unit machinery above - a tile's class moves the W descriptor and sets the gather's padding
+// (pad_h = 1 - a, pad_w = 1 - b: class (a, b) reads source rows i - 1 + a, i + a and columns j - 1 + b, j + b), no tile straddles two
+// classes, the ragged last tile of a class stores nothing beyond it.  p.out_h / p.out_w are the source grid here; the epilogue sends row
+// (class, img, i, j) to output pixel (img, 2i + a, 2j + b) (gemm_epilogue.h).  The K order of a row is the slab-major order of a 2x2
+// kernel whatever the tile, plan or grid.  Own instantiations again.
+template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false, bool UNITS = false, bool UPSF = false>
 __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, unsigned a_bytes, unsigned w_bytes) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (the body uses device-only types)
     constexpr int TBM = Cfg::TBM, BN = Cfg::TBN;
@@ -77,7 +84,9 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
     [[maybe_unused]] const int nk_main = (p.K - (TAIL ? p.k2 + p.k3 : 0)) / BK, nk_a2 = TAIL ? p.k2 / BK : 0;      // K-steps of the gather / of the first linear source
     [[maybe_unused]] int lrow0 = 0;                            // first output row of the tile being loaded
     [[maybe_unused]] __amdgpu_buffer_rsrc_t srd_wu = srd_w;   // UNITS: the weight set of the tile being loaded
-    [[maybe_unused]] const int tpu = UNITS ? (p.unit_rows + TBM - 1) / TBM : 1;      // UNITS: row tiles per unit
+    constexpr bool PERUNIT = UNITS || UPSF;
+    [[maybe_unused]] const int tpu = PERUNIT ? (p.unit_rows + TBM - 1) / TBM : 1;      // UNITS: row tiles per unit
+    [[maybe_unused]] const int cls0 = UPSF ? p.m_begin / p.unit_rows : 0;               // UPSF: parity class of this launch's first unit
     // UNITS: unit (relative to this launch's first one) and first row of row tile tm
     [[maybe_unused]] auto unit_of = [&](int tm, int& u, int& row0) {
         u = tm / tpu;
@@ -103,29 +112,33 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
         int tile_m, tile_n;
         tile_coords(t, ntiles, p.tiles_n, tile_m, tile_n);
         if (TAIL) lrow0 = p.m_begin + tile_m * TBM;
-        if (UNITS) {
-            int lu;
+        [[maybe_unused]] int lu = 0;
+        if (PERUNIT) {
             unit_of(tile_m, lu, lrow0);
             srd_wu = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.W + (int64_t)lu * p.w_unit_stride), 0, (int)w_bytes, 0x00020000);
         }
 #pragma unroll
         for (int i = 0; i < XROWS; ++i) {
             const int r = r0 + RSTEP * i;
-            const int m = UNITS ? lrow0 + r : p.m_begin + tile_m * TBM + r;
+            const int m = PERUNIT ? lrow0 + r : p.m_begin + tile_m * TBM + r;
             const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;   // source chunk that lands at position `chunk`
             if (CONV) {
                 const int hw = p.out_h * p.out_w;
-                const int mm = m < p.M ? m : 0;
+                // UPSF: the row inside its class (rows of the next class that a ragged last tile covers gather nothing)
+                const int ubase = UPSF ? p.m_begin + lu * p.unit_rows : 0;
+                const bool mvalid = UPSF ? m < ubase + p.unit_rows : m < p.M;
+                const int mm = mvalid ? m - ubase : 0;
                 const int img = mm / hw;
                 const int rem = mm - img * hw;
                 const int oy = rem / p.out_w;
                 const int ox = rem - oy * p.out_w;
                 // (iy0, ix0): tap (0,0) in the (possibly 2x nearest-upsampled) input grid; its source pixel is (iy0>>ups, ix0>>ups)
-                const int iy0 = oy * p.stride - p.pad_h, ix0 = ox * p.stride - p.pad_w;
+                const int pad_h = UPSF ? 1 - ((cls0 + lu) >> 1) : p.pad_h, pad_w = UPSF ? 1 - ((cls0 + lu) & 1) : p.pad_w;
+                const int iy0 = oy * p.stride - pad_h, ix0 = ox * p.stride - pad_w;
                 const long long pix0 = ((long long)img * p.in_h + (iy0 >> p.ups)) * p.in_w + (ix0 >> p.ups);   // may be negative at the border
                 xoff[i] = (unsigned)(pix0 * p.lda * 2) + csrc;                            // wraps; valid taps un-wrap it
                 unsigned mask = 0;
-                if (m < p.M) {
+                if (mvalid) {
                     const int lim_h = p.in_h << p.ups, lim_w = p.in_w << p.ups;
                     for (int ky = 0; ky < p.kh; ++ky)
                         for (int kx = 0; kx < p.kw; ++kx) {
@@ -174,7 +187,7 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(src, (lds_ptr_t)(dx + RSTEP * i * BK), 16, v, soff, 0, 0);
             }
         } else if (CONV && (parts & 1)) {
-            if (p.ups) {
+            if (!UPSF && p.ups) {
                 // source offset of tap (ky,kx) relative to tap (0,0): ((by+ky)>>1, (bx+kx)>>1) pixels, by/bx = parity of iy0/ix0
                 const unsigned cb = (unsigned)ci0 * 2u, rowb = (unsigned)(p.in_w * (int)p.lda * 2), pixb = (unsigned)((int)p.lda * 2);
                 const unsigned y0 = (unsigned)(tky >> 1) * rowb, y1 = (unsigned)((tky + 1) >> 1) * rowb;
@@ -219,7 +232,7 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
             const unsigned soffw = (unsigned)kt * (BK * 2);
 #pragma unroll
             for (int i = 0; i < WROWS; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(UNITS ? srd_wu : srd_w, (lds_ptr_t)(dw + RSTEP * i * BK), 16, woff[i], soffw, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(PERUNIT ? srd_wu : srd_w, (lds_ptr_t)(dw + RSTEP * i * BK), 16, woff[i], soffw, 0, 0);
         }
     };
 
@@ -326,6 +339,11 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
                 q.bias = p.bias + (int64_t)cu * p.bias_unit_stride;
                 q.c_bytes = (unsigned)(2ull * ((unsigned long long)(q.M - 1) * (unsigned)p.ldc + (unsigned)p.N));
                 gemm_epilogue<Cfg, false, false, 0>(q, acc, 0, tile_n, wm, wn, lane, sB);
+            } else if constexpr (UPSF) {
+                int cu, crow0;
+                unit_of(tile_m, cu, crow0);
+                gemm_epilogue<Cfg, false, false, LNF, false, true>(p, acc, tile_m, tile_n, wm, wn, lane, sB, nullptr, nullptr, nullptr, nullptr, false, cls0 + cu,
+                                                                   crow0 - (p.m_begin + cu * p.unit_rows));
             } else
             gemm_epilogue<Cfg, GEGLU, OUT_F32, LNF>(p, acc, tile_m, tile_n, wm, wn, lane, sB,
                                                     reinterpret_cast<float*>(smem_raw + Cfg::STAGES + Cfg::STRIP) + wave * WN, ln_r0, ln_r1);
@@ -350,10 +368,10 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
 #endif
 }
 
-template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false, bool UNITS = false>
+template <class Cfg, bool CONV, bool GEGLU, bool OUT_F32, int LNF = 0, bool TAIL = false, bool UNITS = false, bool UPSF = false>
 int launch(const GemmArgs& a, hipStream_t s, int grid) {
     static VcxLdsAttr lds;
-    auto kern = gemm_dma_kernel<Cfg, CONV, GEGLU, OUT_F32, LNF, TAIL, UNITS>;
+    auto kern = gemm_dma_kernel<Cfg, CONV, GEGLU, OUT_F32, LNF, TAIL, UNITS, UPSF>;
     constexpr size_t smem = LNF ? Cfg::SMEM_LNF : Cfg::SMEM;
     if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)smem, "vcx_gemm_f16(dma)")) return VCX_ELAUNCH;
     const int blocks_per_cu = Cfg::SMEM > 80 * 1024 ? 1 : 2;
@@ -364,6 +382,8 @@ int launch(const GemmArgs& a, hipStream_t s, int grid) {
 
 template <class Cfg>
 int dispatch(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_t s, int grid) {
+    if (a.unit_rows > 0 && conv)      // folded nearest-2x + 3x3 (ups = 2): four parity classes as units, bias epilogue with or without column moments (checked by gemm_route)
+        return (a.flags & VCX_GEMM_COLSTATS) ? launch<Cfg, true, false, false, 3, false, false, true>(a, s, grid) : launch<Cfg, true, false, false, 0, false, false, true>(a, s, grid);
     if (a.unit_rows > 0)       // one weight / bias set per unit of rows: linear, fp16 output, BIAS_N at most (checked by vcx_gemm_units_f16)
         return launch<Cfg, false, false, false, 0, false, true>(a, s, grid);
     if (a.k2 + a.k3 > 0)       // K tail: convolutions with fp16 output, plain or column-moment epilogue (checked by vcx_gemm_f16)
@@ -412,6 +432,10 @@ int dispatch_tail(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_
     const bool cs = a.flags & VCX_GEMM_COLSTATS;
     if (f32 || (a.flags & VCX_GEMM_LNFOLD_T)) {
         vcx_set_error("vcx_gemm_f16(dma): the 64-row tile configurations have no fp32-output / LNFOLD_T epilogue");
+        return VCX_EINVAL;
+    }
+    if (a.unit_rows > 0 && conv) {
+        vcx_set_error("vcx_gemm_f16(dma): the 64-row tile configurations have no folded-upsample form");
         return VCX_EINVAL;
     }
     if constexpr (Cfg::NF % 4 == 0) {       // the GEGLU configuration

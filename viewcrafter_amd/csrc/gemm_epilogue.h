@@ -45,12 +45,19 @@ __device__ __forceinline__ void gemm_epilogue_fetch_residual(const GemmArgs& p, 
 // LNF (folded LayerNorm, include/vcx.h VCX_GEMM_LNFOLD*): the accumulator holds x W'^T of the UN-normalised rows;
 //   LNF = 1  out = alpha rstd_m (acc - mean_m colsum_n) + bias'_n  = fma(acc, rb, fma(qb, colsum_n, bias'_n)),  rb = alpha rstd_m, qb = -rb mean_m
 //   LNF = 2  out = alpha rstd_n (acc - mean_n colsum_m) + bias'_m  = fma(acc, cs_n, fma(cq_n, colsum_m, bias'_m)), cs / cq in the two strips
-template <class Cfg, bool GEGLU, bool OUT_F32, int LNF = 0, bool RPRE = false>
+// UPSF (gemm_dma.hip, folded nearest-2x + 3x3 convolution; plain and LNF 3 epilogues, no residual / row addend): the tile's rows are rows
+// ups_q0 ... of parity class ups_cls = 2a + b on the SOURCE grid p.out_h x p.out_w; row (img, i, j) is stored at output pixel
+// (img, 2i + a, 2j + b).  p.out_w % 16 == 0: a 16-row fragment lies inside one source row, so its base is scalar arithmetic and the
+// lane step 2 ldc; fragments at or beyond p.unit_rows (the class's end) store nothing.  Column moments: p.out_h p.out_w % 64 == 0, a
+// 64-row strip belongs to one image and takes slot img (4 H W / 64) + class (H W / 64) + strip inside the image, so that an image's
+// strips stay contiguous (vcx_groupnorm_stats_from_colstats_f32 merges strips per image in any order).
+template <class Cfg, bool GEGLU, bool OUT_F32, int LNF = 0, bool RPRE = false, bool UPSF = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f4 (&acc)[Cfg::NF][Cfg::MF], int tile_m, int tile_n, int wm, int wn,
                                               int lane, float* sB, [[maybe_unused]] float* sS = nullptr,
                                               [[maybe_unused]] const float* ln_r0 = nullptr, [[maybe_unused]] const float* ln_r1 = nullptr,
                                               [[maybe_unused]] const epi_u4v* rpre = nullptr,      // RPRE: gemm_epilogue_fetch_residual's pieces
-                                              bool strip_ready = false) {      // the strip(s) still hold THIS column tile's addends (a caller that walks rows only)
+                                              bool strip_ready = false,      // the strip(s) still hold THIS column tile's addends (a caller that walks rows only)
+                                              [[maybe_unused]] int ups_cls = 0, [[maybe_unused]] int ups_q0 = 0) {
     // ln_r0 / ln_r1 [MFRAG]: per-lane row terms fetched by the caller ahead of the last K-step - LNF 1: (mean, rstd) of row
     // mbase + 16 b, LNF 2: (colsum, bias') of it
     constexpr int TBM = Cfg::TBM, BN = Cfg::TBN, NFRAG = Cfg::NF, MFRAG = Cfg::MF;
@@ -285,14 +292,25 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f4 (&acc)[Cfg::
         };
 #pragma unroll
         for (int b = 0; b < MFRAG; ++b) {
-            const unsigned crow = coff0 + (unsigned)b * cstep;
+            unsigned crow = coff0 + (unsigned)b * cstep;
+            [[maybe_unused]] bool fvalid = true;
+            if constexpr (UPSF) {
+                const int qf = ups_q0 + wm * WM + b * 16;      // the fragment's first row inside its class (wave-uniform)
+                const int hw = p.out_h * p.out_w;
+                fvalid = qf < p.unit_rows;
+                const int qc = fvalid ? qf : 0;
+                const int img = qc / hw, rem = qc - img * hw;
+                const int i = rem / p.out_w, j0 = rem - i * p.out_w;
+                const unsigned pix = ((unsigned)img * 2u * (unsigned)p.out_h + 2u * (unsigned)i + (unsigned)(ups_cls >> 1)) * 2u * (unsigned)p.out_w + 2u * (unsigned)j0 + (unsigned)(ups_cls & 1);
+                crow = ((pix + 2u * (unsigned)lr) * (unsigned)p.ldc + (unsigned)nstrip) * ES;
+            }
             asm volatile("" : "+v"(bopaque));
 #pragma unroll
             for (int u = 0; u < UNITS; ++u) {
                 const int i = b * UNITS + u;
                 const bool wide = u < NPAIRF;
                 const int a = wide ? 2 * u : 2 * NPAIRF + (u - NPAIRF);
-                const unsigned voff = nstrip + unit_col(u) < p.N ? crow + (unsigned)unit_col(u) * ES : OOB;
+                const unsigned voff = (nstrip + unit_col(u) < p.N && (!UPSF || fvalid)) ? crow + (unsigned)unit_col(u) * ES : OOB;
                 float v0[4], v1[4] = {0.f, 0.f, 0.f, 0.f};
                 finish(a, b, v0);
                 if (wide) finish(a + 1, b, v1);
@@ -368,7 +386,16 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f4 (&acc)[Cfg::
                 return x;
             };
             // one (mean, M2) pair per 64-row strip and column: colstats[strip][ldcs][2], strip = first row of the wave's rows / 64
-            const int strip = (p.m_begin + tile_m * TBM + wm * WM) >> 6;
+            int strip = (p.m_begin + tile_m * TBM + wm * WM) >> 6;
+            [[maybe_unused]] bool svalid = true;
+            if constexpr (UPSF) {
+                static_assert(!UPSF || WM == 64, "UPSF column moments: one strip per 64 rows of a wave");
+                const int qs = ups_q0 + wm * WM, s64 = (p.out_h * p.out_w) >> 6;      // strips per image and class
+                svalid = qs < p.unit_rows;
+                const int qq = svalid ? qs >> 6 : 0;
+                const int img = qq / s64;
+                strip = img * 4 * s64 + ups_cls * s64 + (qq - img * s64);
+            }
             float* dst = p.colstats + ((size_t)strip * (size_t)p.ldcs + nstrip) * 2;
 #pragma unroll
             for (int u = 0; u < UNITS; ++u) {
@@ -379,7 +406,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f4 (&acc)[Cfg::
                     mo[e] = gk[u][e >> 2] + s1 * (1.0f / 64.0f);
                     qo[e] = __builtin_fmaf(-s1 * (1.0f / 64.0f), s1, s2);
                 }
-                if (lr == 0 && strip * 64 < p.M) {     // (a tile's last strips may lie beyond M: M is a multiple of 64, not of the tile height)
+                if (lr == 0 && (UPSF ? svalid : strip * 64 < p.M)) {     // (a tile's last strips may lie beyond M: M is a multiple of 64, not of the tile height)
                     const bool wide = u < NPAIRF;
                     const int c0 = wide ? (2 * u) * 16 + lg * 4 : (2 * NPAIRF + (u - NPAIRF)) * 16 + lg * 4;
                     if (nstrip + c0 < p.N) {

@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from .... import ops
-from ....packing import pack_conv
+from ....packing import pack_conv, pack_conv_ups_folded
 from ..attention import PackedModule, SpatialTransformer, TemporalTransformer, _f16, _f32
 from ..flow import CAT_SPLIT, GN_EPILOGUE_STATS, GN_STATS_LEVEL, CatTarget, Flow, out_kwargs as _out_kwargs
 
@@ -140,8 +140,10 @@ class Downsample(PackedModule):
 
 
 class Upsample(PackedModule):
-    """Reference openaimodel3d.py:80-106: nearest 2x then Conv2d 3x3 (`.conv`); the interpolation is folded into the
-    convolution's gather (VCX mode-1 `ups`)."""
+    """Reference openaimodel3d.py:80-106: nearest 2x then Conv2d 3x3 (`.conv`).  On the GPU, where the library takes the shape
+    (ops.conv2d_ups_folded_ok), the layer runs as four 2x2 convolutions on the source grid whose weights are sums of the nine taps
+    (packing.pack_conv_ups_folded: 4/9 of the multiply-adds, one more rounding of a constant); elsewhere the interpolation is fused into
+    the nine-tap convolution's gather (VCX mode-1 `ups`)."""
 
     def __init__(self, channels, use_conv, dims=2, out_channels=None, padding=1):
         super().__init__()
@@ -154,7 +156,10 @@ class Upsample(PackedModule):
             self.conv = nn.Conv2d(self.channels, self.out_channels, 3, padding=padding)
 
     def _pack(self):
-        return dict(w=_f16(pack_conv(self.conv.weight.detach())), b=_f32(self.conv.bias)) if self.use_conv else {}
+        if not self.use_conv:
+            return {}
+        w = self.conv.weight.detach()
+        return dict(w=_f16(pack_conv(w)), wf=_f16(pack_conv_ups_folded(w, dtype=None)), b=_f32(self.conv.bias))
 
     def forward(self, x, want_colstats=False, target=None):
         if not self.use_conv:      # conv_resample: false (reference openaimodel3d.py:98-103): the nearest 2x alone
@@ -162,6 +167,8 @@ class Upsample(PackedModule):
         pk = self.packed()
         n, H, W, cin = x.shape
         kw, cs = _out_kwargs(target, want_colstats, n * 4 * H * W, 4 * H * W, cin, self.out_channels, x.device, in_rows=n * H * W)
+        if x.is_cuda and ops.conv2d_ups_folded_ok(n, H, W, cin, self.out_channels, lda=x.stride(2), ldc=kw.get("ldc"), colstats="colstats" in kw):
+            return ops.conv2d_ups_folded(x, pk["wf"], pk["b"], **kw), cs
         return ops.conv2d(x, pk["w"], pk["b"], kh=3, kw=3, ups=1, **kw), cs
 
 

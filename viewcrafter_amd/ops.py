@@ -265,6 +265,39 @@ def conv2d(x, w, bias, *, kh, kw, stride=1, pad_h=None, pad_w=None, ups=0, out_h
     return out.view(n, Ho, Wo, -1)
 
 
+# Upsample convolutions in their folded form (ups = 2, include/vcx.h; round 11).  VCX_UPS_FOLD=0: the nine-tap ups = 1 call everywhere (A/B runs)
+UPS_FOLD = os.environ.get("VCX_UPS_FOLD", "1") != "0"
+
+
+def _ups_folded_desc(n, H, W, cin, cout, lda, ldc, colstats):
+    geom = dict(in_h=H, in_w=W, out_h=2 * H, out_w=2 * W, cin=cin, kh=2, kw=2, stride=1, pad_h=1, pad_w=1, ups=2)
+    return dict(M=n * 4 * H * W, N=cout, K=4 * cin, lda=lda, ldc=ldc, conv=geom, flags=GEMM_BIAS_N | (GEMM_COLSTATS if colstats else 0))
+
+
+def conv2d_ups_folded_ok(n, H, W, cin, cout, *, lda=None, ldc=None, colstats=False):
+    """Does the library run nearest-2x + 3x3 on an [n, H, W, cin] source in its folded form (four 2x2 weight sets, conv2d_ups_folded)?
+    The dispatcher's answer (vcx_gemm_route) for the descriptor that call would send; False also under VCX_UPS_FOLD=0.  Where it says
+    no the caller runs conv2d(..., ups=1) on the nine-tap weights."""
+    if not UPS_FOLD:
+        return False
+    d = _ups_folded_desc(n, H, W, cin, cout, cin if lda is None else lda, cout if ldc is None else ldc, colstats)
+    return _takes(d.pop("M"), d.pop("N"), d.pop("K"), d.pop("lda"), d.pop("ldc"), **d)
+
+
+def conv2d_ups_folded(x, wf, bias, *, out=None, ldc=None, colstats=None, colstats_ld=None, colstats_col=0):
+    """F.interpolate(x, 2, 'nearest') + 3x3 / padding 1 as four 2x2 convolutions on the source grid: x [n, H, W, Cin] channels-last fp16,
+    wf [4, Cout, 4*Cin] as packed by packing.pack_conv_ups_folded.  Returns [n, 2H, 2W, Cout]; out / ldc / colstats* as in gemm.  Shapes:
+    conv2d_ups_folded_ok - a shape the folded kernel does not take is an error here, not a fall-back."""
+    n, H, W, cin = x.shape
+    cout = wf.shape[1]
+    if wf.dim() != 3 or wf.shape[0] != 4 or wf.shape[2] != 4 * cin or not wf.is_contiguous():
+        raise VcxError(f"conv2d_ups_folded: weights must be contiguous [4, Cout, 4 * {cin}], got {tuple(wf.shape)}")
+    geom = _ups_folded_desc(n, H, W, cin, cout, 0, 0, False)["conv"]
+    res = gemm(x, wf, M=n * 4 * H * W, N=cout, K=4 * cin, lda=x.stride(2), bias=bias, conv=geom, out=out, ldc=ldc, colstats=colstats,
+               colstats_ld=colstats_ld, colstats_col=colstats_col)
+    return res.view(n, 2 * H, 2 * W, -1)
+
+
 def _rows_geom(M, in_rows, cin, taps):
     """Convolution geometry for a route query that knows row counts only: ONE image of in_rows pixels and M outputs, taps x 1 taps."""
     return dict(in_h=1, in_w=M if in_rows is None else in_rows, out_h=1, out_w=M, cin=cin, kh=taps, kw=1, stride=1, pad_h=0, pad_w=0)

@@ -26,6 +26,22 @@ def pack_conv(w):
     return wk.permute(0, 2, 1).reshape(cout, -1).contiguous()
 
 
+def pack_conv_ups_folded(w, dtype=torch.float16):
+    """Nearest-2x followed by a 3x3 / padding-1 convolution (reference openaimodel3d.py Upsample) as four 2x2 convolutions on the SOURCE
+    grid, one per parity class (a, b) of the output pixel (2i + a, 2j + b): its tap rows -1, 0, +1 read source rows (i-1, i, i) for
+    a = 0 and (i, i, i+1) for a = 1, so the 2x2 kernel of class a over source rows (i - 1 + a, i + a) has row weights
+    (w[0], w[1] + w[2]) or (w[0] + w[1], w[2]); columns alike with b.  The zero padding of the upsampled image is the zero padding of
+    the source, so the border needs nothing.  [Cout, Cin, 3, 3] -> [4, Cout, 4*Cin], class order 2a + b, each class packed as pack_conv
+    packs a 2x2 kernel (VCX ups = 2, include/vcx.h).  The sums are made in fp64 and rounded ONCE to `dtype` (None: left in fp64)."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"pack_conv_ups_folded: need a [Cout, Cin, 3, 3] weight, got {tuple(w.shape)}")
+    w64 = w.detach().double()
+    fold = w64.new_tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]])      # [parity][tap of the 2x2 kernel][tap of the 3x3 kernel]
+    classes = [pack_conv(torch.einsum("ky,oiyx,lx->oikl", fold[a], w64, fold[b])) for a in (0, 1) for b in (0, 1)]
+    out = torch.stack(classes)
+    return out if dtype is None else out.to(dtype)
+
+
 def pad_cin(w, cin_to):
     """Zero-pad the input-channel dim of a conv weight (e.g. the VAE's 4-channel conv_in to 8)."""
     if w.shape[1] == cin_to:
