@@ -39,8 +39,9 @@ extern "C" {
  * vcx_gemm_units_f16, vcx_attn_flash_d512_f16.  8: vcx_gemm_desc grows rowstats / rowstats_eps (VCX_GEMM_ROWSTATS) and
  * tail_a0 / tail_a1 (K tail of a convolution from linear sources); vcx_groupnorm_apply2_f16.  10: vcx_gemm_route.  11: MXFP8 operands - vcx_quant_mxfp8_f16,
  * vcx_layernorm_mxfp8_f16, vcx_gemm_mxfp8, vcx_gemm_mxfp8_ok; VCX_GEMM_MXFP8_OUT.  12: ups = 2 (nearest-2x + 3x3 convolution folded into
- * four 2x2 weight sets on the tiled engine). */
-#define VCX_ABI_VERSION 12
+ * four 2x2 weight sets on the tiled engine).  13: MXFP8 temporal convolutions - vcx_groupnorm_apply_mxfp8_f16, vcx_conv_t3_mxfp8,
+ * vcx_conv_t3_mxfp8_ok. */
+#define VCX_ABI_VERSION 13
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -247,7 +248,8 @@ int vcx_layernorm_f16(const void* x, void* y, const float* gamma, const float* b
 
 /* ------------------------------------------------------------------------------------
  * MXFP8 operands (ABI 11): OCP MX with e4m3fn elements and e8m0 scales, for the block-scaled matrix instruction
- * v_mfma_scale_f32_16x16x128_f8f6f4.  Opt-in (the GEGLU feed-forward under VCX_FF_MXFP8=1); nothing else uses it.
+ * v_mfma_scale_f32_16x16x128_f8f6f4.  Opt-in (the GEGLU feed-forward under VCX_FF_MXFP8=1, the TemporalConvBlock convolutions under
+ * VCX_TCONV_MXFP8=1); nothing else uses it.
  *
  * A matrix [rows][K] (K % 32 == 0) is two dense arrays, ONE layout for every producer and consumer:
  *   elements  uint8 [rows][Kp]        Kp = K rounded up to a multiple of 128; row pitch Kp bytes
@@ -286,6 +288,30 @@ int vcx_gemm_mxfp8(const void* a, const void* a_scales, const void* w, const voi
  * words above, K % 32 == 0, N % 8 == 0 (GEGLU: N % 64 == 0, i.e. N / 2 % 32 == 0), every operand, output and residual extent below
  * 4 GiB (32-bit buffer offsets, as in the fp16 DMA engine).  Touches no device; callers ask it instead of restating the rules. */
 int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags);
+/* ABI 13.  quant(vcx_groupnorm_apply_f16(x)) byte for byte in one pass: that kernel's thread map and arithmetic, every value rounded to fp16
+ * as it would store it, then quantised per block of 32 channels; the fp16 tensor is never written.  x fp16 [n_outer][pixels][C] dense,
+ * C % 32 == 0; q [n_outer pixels][Kp(C)], scales [n_outer pixels][Kp(C) / 32], padding (element bytes 0x00, scale bytes 127) included;
+ * stats [n_outer][groups][2] = (mean, biased variance) as for vcx_groupnorm_apply_f16. */
+int vcx_groupnorm_apply_mxfp8_f16(const void* x, void* q, void* scales, const float* stats, const float* gamma, const float* beta, int n_outer,
+                                  int64_t pixels, int C, int groups, float eps, int silu, void* stream);
+/* ABI 13.  Conv3d (3,1,1), padding (1,0,0), on MXFP8 operands - a gathered mode of vcx_gemm_mxfp8's kernel:
+ *   out[(b,t,p), n] = bias[n] + sum_{tau=0..2} sum_c A[(b, t + tau - 1, p), c] W[n, tau, c]  (+ residual[(b,t,p) ldr + n])
+ * frames outside [0, T) of the row's own video contribute zero; fp32 accumulation, fp16 output [B T P][ldc] (ldc >= N: a concat buffer).
+ *   a / a_scales   [B T P][Kp(Cin)] / [B T P][Kp(Cin) / 32], as vcx_groupnorm_apply_mxfp8_f16 or vcx_quant_mxfp8_f16 write them
+ *   w / w_scales   [N][3][Kp(Cin)] / [N][3][Kp(Cin) / 32]: tap-major, every tap quantised and padded on its own (no block mixes taps;
+ *                  packing.pack_conv_t3_mxfp8)
+ * flags: VCX_GEMM_BIAS_N (required), optionally | VCX_GEMM_RESIDUAL, | VCX_GEMM_COLSTATS (colstats points at the first of this call's N
+ * columns inside a [B T P / 64][ldcs][2] buffer, as for vcx_gemm_f16).  One tile shape and one K order (tap 0, 1, 2): a row's bits depend
+ * neither on B, nor on the number of rows, nor on the tile or the grid.  Shapes: vcx_conv_t3_mxfp8_ok. */
+int vcx_conv_t3_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, const float* bias, const void* residual,
+                      float* colstats, int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int flags,
+                      void* stream);
+/* 1 if vcx_conv_t3_mxfp8 takes the call, else 0 with the reason in vcx_last_error(): the flag words above, Cin % 32 == 0, N % 8 == 0,
+ * ldc / ldr >= N and % 8 == 0, COLSTATS: B T P % 64 == 0, ldcs >= colstats_col + N, ldcs and colstats_col even; 32-bit buffer offsets:
+ * (B T P + 127 + P) Kp(Cin) (a tile reaches 127 rows past the last one, a tap P rows further), the weight and its scales, output and
+ * residual below 4 GiB.  ldr / ldcs / colstats_col are ignored without their flag.  Touches no device. */
+int vcx_conv_t3_mxfp8_ok(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
+                         int flags);
 
 /* ------------------------------------------------------------------------------------
  * Flash attention, head dim 64, no mask:  O = softmax(scale * Q K^T) V

@@ -1,6 +1,8 @@
 """rel-L2 / PSNR against the fp32 oracle at the config-1 latent (16 x 40 x 64, inference_pvd_512.yaml, synthetic weights) with the MXFP8
-feed-forward switch off and on: one UNet forward, and a 10-step DDIM trajectory (eta 0, CFG 7.5, guidance rescale 0.7) of the product
-sampler against the oracle sampler on the oracle UNet.  Figures for profiles/mxfp8_ff.md.      python tools/mxfp8_accuracy.py [--steps 10]"""
+switches - VCX_FF_MXFP8 (feed-forward) and VCX_TCONV_MXFP8 (temporal convolutions) - off, each alone, and together: one UNet forward,
+and a 10-step DDIM trajectory (eta 0, CFG 7.5, guidance rescale 0.7) of the product sampler against the oracle sampler on the oracle
+UNet.  The skip lists are as the environment sets them; --all-widths empties both.  Figures for profiles/mxfp8_ff.md and
+profiles/mxfp8_tconv.md.      python tools/mxfp8_accuracy.py [--steps 10] [--all-widths] [--only-tconv]"""
 import argparse
 import os
 import sys
@@ -26,12 +28,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--yaml", default="inference_pvd_512.yaml")
+    ap.add_argument("--all-widths", action="store_true", help="empty FF_MXFP8_SKIP_DIMS and TCONV_MXFP8_SKIP_DIMS")
+    ap.add_argument("--only-tconv", action="store_true", help="skip the feed-forward-only run (recorded in profiles/mxfp8_ff.md)")
     a = ap.parse_args()
     from oracle import lvdm_oracle as O
     from viewcrafter_amd.builder import build_diffusion_model, randomize_parameters
     from viewcrafter_amd.config import load_yaml
     from viewcrafter_amd.lvdm.models.samplers.ddim import DDIMSampler
     from viewcrafter_amd.lvdm.modules import attention as A
+    from viewcrafter_amd.lvdm.modules.networks import openaimodel3d as U
     path = os.path.join(ROOT, "configs", a.yaml)
     model = build_diffusion_model(path, device=DEV, conditioners="identity")
     randomize_parameters(model, seed=0)
@@ -54,23 +59,28 @@ def main():
     def apply_oracle(xx, t, c):
         return O.unet_forward(sd, hp, torch.cat([xx, c["c_concat"][0]], dim=1), t.to(DEV), c["c_crossattn"][0], fs)
 
-    was = A.FF_MXFP8
+    was = A.FF_MXFP8, U.TCONV_MXFP8, A.FF_MXFP8_SKIP_DIMS, U.TCONV_MXFP8_SKIP_DIMS
+    if a.all_widths:
+        A.FF_MXFP8_SKIP_DIMS = U.TCONV_MXFP8_SKIP_DIMS = frozenset()
+    print(f"skip lists: feed-forward {sorted(A.FF_MXFP8_SKIP_DIMS)}, temporal convolutions {sorted(U.TCONV_MXFP8_SKIP_DIMS)}", flush=True)
     try:
         with torch.no_grad():
             ref_fwd = O.unet_forward(sd, hp, x, ts, ctx, fs)
             ref_traj, _ = O.ddim_sample(apply_oracle, tables, scale_arr, x_T, cond, uc, steps=a.steps, eta=0.0, cfg_scale=7.5, guidance_rescale=0.7,
                                         spacing="uniform_trailing", parameterization="v")
-            for flag in (False, True):
-                A.FF_MXFP8 = flag
+            for ff, tconv in ((False, False), (True, False), (False, True), (True, True)):
+                if a.only_tconv and ff and not tconv:
+                    continue
+                A.FF_MXFP8, U.TCONV_MXFP8 = ff, tconv
                 y = unet._forward(x, ts, context=ctx, fs=fs)
                 ours, _ = DDIMSampler(model).sample(S=a.steps, conditioning=cond, batch_size=1, shape=[4, T, h, w], verbose=False,
                                                     unconditional_guidance_scale=7.5, unconditional_conditioning=uc, eta=0.0, cfg_img=None, mask=None,
                                                     x0=None, fs=fs, timestep_spacing="uniform_trailing", guidance_rescale=0.7, x_T=x_T,
                                                     log_every_t=a.steps, unconditional_conditioning_img_nonetext=None)
-                print(f"VCX_FF_MXFP8={int(flag)}: UNet forward vs fp32 oracle rel-L2 {rel_l2(y, ref_fwd):.3e} PSNR {psnr(y, ref_fwd):.2f} dB | "
+                print(f"VCX_FF_MXFP8={int(ff)} VCX_TCONV_MXFP8={int(tconv)}: UNet forward vs fp32 oracle rel-L2 {rel_l2(y, ref_fwd):.3e} PSNR {psnr(y, ref_fwd):.2f} dB | "
                       f"{a.steps}-step trajectory, final latent rel-L2 {rel_l2(ours, ref_traj):.3e} PSNR {psnr(ours, ref_traj):.2f} dB", flush=True)
     finally:
-        A.FF_MXFP8 = was
+        A.FF_MXFP8, U.TCONV_MXFP8, A.FF_MXFP8_SKIP_DIMS, U.TCONV_MXFP8_SKIP_DIMS = was
 
 
 if __name__ == "__main__":

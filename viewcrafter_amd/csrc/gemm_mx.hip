@@ -19,6 +19,15 @@
 // ONE tile shape (128 x 128, 2 x 2 waves, 64 x 64 per wave) and one K order: a row's result does not depend on M, on the tile it falls
 // into or on the grid.  A wave's 64 packed GEGLU columns are 32 output columns - one MX block of the next layer's K axis - so the
 // quantising epilogue takes a block's maximum inside the wave, across the four lane groups, with two lane swaps.  No atomics.
+//
+// vcx_conv_t3_mxfp8 (T3 = true): the (3,1,1) temporal convolution as a GATHERED mode of the same kernel.  K is three taps of Kp(Cin) each
+// (weights [N][3][Kp], tap-major, every tap padded on its own: no MX block and no K-step straddles two taps); K-step kt belongs to tap
+// kt / (Kp / 128), and the activation DMA and the scale-dword DMA of that step read row m + (tap - 1) P of the activation [B T P][Kp].
+// Whether that row exists is decided per row from t = (m / P) % T when a tile's offsets are set up (three bits per row in one register;
+// the offsets of a tap are one add and one select per DMA instruction, recomputed at issue: no second and third set of row offsets): where
+// frame t + tap - 1 of the row's OWN video does not exist the offset is forced out of range, the descriptor zero-fills element and scale
+// bytes and the products are 0 - a row at t = 0 of video b > 0 never reads video b - 1, and m - P < 0 never wraps.  The weight side stays
+// linear in K.
 #include "gemm_epilogue.h"
 #include "mx_format.h"
 
@@ -46,6 +55,10 @@ struct MxArgs {
     int ldc, ldr, flags;
     int tiles_m, tiles_n;
     unsigned a_bytes, as_bytes, w_bytes, ws_bytes, c_bytes, cs_bytes, r_bytes;
+    // vcx_conv_t3_mxfp8: frames per video, pixels per frame (kp = one tap's K extent, the activation's row pitch; the weight's is 3 kp)
+    int T, P;
+    float* colstats;                  // VCX_GEMM_COLSTATS: (mean, M2) per 64-row strip and output column (gemm_epilogue.h, LNF = 3)
+    int64_t ldcs;
 };
 
 template <int TBM_, int TBN_, int NWM_, int NWN_>
@@ -131,8 +144,9 @@ __device__ __forceinline__ void mx_geglu_epilogue(const MxArgs& p, f4 (&acc)[Cfg
     }
 }
 
-// EPI: 0 = bias / residual, fp16 out (gemm_epilogue.h, the fp16 engine's epilogue); 1 = GEGLU, fp16 out; 2 = GEGLU, MXFP8 out
-template <class Cfg, int EPI>
+// EPI: 0 = bias / residual, fp16 out (gemm_epilogue.h, the fp16 engine's epilogue); 1 = GEGLU, fp16 out; 2 = GEGLU, MXFP8 out;
+// 3 = EPI 0 + column moments of the output (VCX_GEMM_COLSTATS).  T3: the gathered temporal convolution (file header).
+template <class Cfg, int EPI, bool T3 = false>
 __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int TBM = Cfg::TBM, TBN = Cfg::TBN, NFRAG = Cfg::NF, MFRAG = Cfg::MF;
@@ -157,6 +171,16 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
     const bool scale_is_a = wave < TBM / 64;      // wave-uniform: this wave's scale dwords belong to activation rows
 
     unsigned xoff[XROWS], woff[WROWS], soff_v;
+    // T3: bit 3 i + tap = the source row of tap `tap` exists for this thread's DMA row i (i = XROWS: its scale row); xoff / soff_v then hold
+    // the offsets of the centre tap whether or not the row is below M
+    [[maybe_unused]] unsigned vbits = 0;
+    [[maybe_unused]] const unsigned tap_step = T3 ? (unsigned)p.P * (unsigned)p.kp : 0u;      // bytes between a row and the same pixel one frame on
+    [[maybe_unused]] const int nk_tap = p.kp / KSTEP;
+    [[maybe_unused]] auto tap_bits = [&](int m) -> unsigned {
+        if (m >= p.M) return 0u;
+        const unsigned t = ((unsigned)m / (unsigned)p.P) % (unsigned)p.T;
+        return 2u | (t > 0u ? 1u : 0u) | (t + 1u < (unsigned)p.T ? 4u : 0u);
+    };
     auto init_load = [&](int t) {
         int tile_m, tile_n;
         tile_coords(t, ntiles, p.tiles_n, tile_m, tile_n);
@@ -165,38 +189,62 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             const int r = r0 + RSTEP * i;
             const int m = tile_m * TBM + r;
             const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;   // source chunk that lands at position `chunk`
-            xoff[i] = m < p.M ? (unsigned)m * (unsigned)p.kp + csrc : OOB;
+            if constexpr (T3) {
+                xoff[i] = (unsigned)m * (unsigned)p.kp + csrc;
+                vbits = i == 0 ? tap_bits(m) : vbits | (tap_bits(m) << (3 * i));
+            } else {
+                xoff[i] = m < p.M ? (unsigned)m * (unsigned)p.kp + csrc : OOB;
+            }
         }
 #pragma unroll
         for (int i = 0; i < WROWS; ++i) {
             const int r = r0 + RSTEP * i;
             const int n = tile_n * TBN + r;
             const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;
-            woff[i] = n < p.N ? (unsigned)n * (unsigned)p.kp + csrc : OOB;
+            woff[i] = n < p.N ? (unsigned)n * (unsigned)(T3 ? 3 * p.kp : p.kp) + csrc : OOB;
         }
         const unsigned spitch = (unsigned)(p.kp >> 5);
         if (scale_is_a) {
             const int m = tile_m * TBM + tid;
-            soff_v = m < p.M ? (unsigned)m * spitch : OOB;
+            if constexpr (T3) {
+                soff_v = (unsigned)m * spitch;
+                vbits |= tap_bits(m) << (3 * XROWS);
+            } else {
+                soff_v = m < p.M ? (unsigned)m * spitch : OOB;
+            }
         } else {
             const int n = tile_n * TBN + (tid - TBM);
-            soff_v = n < p.N ? (unsigned)n * spitch : OOB;
+            soff_v = n < p.N ? (unsigned)n * (T3 ? 3u * spitch : spitch) : OOB;
         }
     };
-    // issue the DMA of K-step kt of the load tile into LDS stage `buf`
-    auto load_tile = [&](int kt, int buf) {
+    // issue the DMA of K-step kt of the load tile into LDS stage `buf` (T3: kt is K-step kk of tap `tap`, kt = tap nk_tap + kk)
+    auto load_tile = [&](int kt, int buf, [[maybe_unused]] int tap = 0, [[maybe_unused]] int kk = 0) {
         unsigned char* dx = sT + buf * Cfg::TILE + wave * 8 * KSTEP;
         unsigned char* dw = sT + buf * Cfg::TILE + TBM * KSTEP + wave * 8 * KSTEP;
         const unsigned soff = (unsigned)kt * KSTEP;
+        const unsigned soff_x = T3 ? (unsigned)kk * KSTEP : soff;
+        [[maybe_unused]] const unsigned shift = (unsigned)(tap - 1) * tap_step;      // (tap - 1) P rows of kp bytes, modulo 2^32: exact for every row that exists
 #pragma unroll
-        for (int i = 0; i < XROWS; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_a, (lds_ptr_t)(dx + RSTEP * i * KSTEP), 16, xoff[i], soff, 0, 0);
+        for (int i = 0; i < XROWS; ++i) {
+            unsigned vo = xoff[i];
+            if constexpr (T3) vo = ((vbits >> (3 * i + tap)) & 1u) ? vo + shift : OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_a, (lds_ptr_t)(dx + RSTEP * i * KSTEP), 16, vo, soff_x, 0, 0);
+        }
 #pragma unroll
         for (int i = 0; i < WROWS; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_w, (lds_ptr_t)(dw + RSTEP * i * KSTEP), 16, woff[i], soff, 0, 0);
         // the K-step's four scale bytes of every tile row: one dword per thread, lane-linear behind the wave's base
         unsigned* ds = sS + buf * (TBM + TBN) + wave * 64;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(scale_is_a ? srd_as : srd_ws, (lds_ptr_t)ds, 4, soff_v, (unsigned)kt * 4u, 0, 0);
+        if constexpr (T3) {
+            if (scale_is_a) {
+                const unsigned vo = ((vbits >> (3 * XROWS + tap)) & 1u) ? soff_v + (unsigned)(tap - 1) * (tap_step >> 5) : OOB;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_as, (lds_ptr_t)ds, 4, vo, (unsigned)kk * 4u, 0, 0);
+            } else {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_ws, (lds_ptr_t)ds, 4, soff_v, (unsigned)kt * 4u, 0, 0);
+            }
+        } else {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(scale_is_a ? srd_as : srd_ws, (lds_ptr_t)ds, 4, soff_v, (unsigned)kt * 4u, 0, 0);
+        }
     };
 
     const int wm = wave % Cfg::NWM, wn = wave / Cfg::NWM;
@@ -208,7 +256,8 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #pragma unroll
         for (int b = 0; b < MFRAG; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = p.kp / KSTEP;
+    const int nk = T3 ? 3 * nk_tap : p.kp / KSTEP;
+    [[maybe_unused]] int ltap = 0, lkk = 0;      // T3: tap and K-step inside the tap of the load side's lkt
     int ltile = blockIdx.x, lkt = 0;
     int ctile = blockIdx.x, ckt = 0;
     int tile_m, tile_n;
@@ -223,9 +272,15 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             lkt = 0;
             ltile += G;
             if (ltile < ntiles) init_load(ltile);
+            if constexpr (T3) ltap = lkk = 0;
+        } else if constexpr (T3) {
+            if (++lkk == nk_tap) {
+                lkk = 0;
+                ++ltap;
+            }
         }
         const bool more = ltile < ntiles;
-        if (more) load_tile(lkt, cur ^ 1);        // async: lands in the other stage while this one is consumed
+        if (more) load_tile(lkt, cur ^ 1, ltap, lkk);        // async: lands in the other stage while this one is consumed
         const unsigned char* cx = sT + cur * Cfg::TILE;
         const unsigned char* cw = cx + TBM * KSTEP;
         const unsigned* csx = sS + cur * (TBM + TBN);
@@ -262,7 +317,7 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             }
         }
         if (ckt == nk - 1) {
-            if constexpr (EPI == 0) {
+            if constexpr (EPI == 0 || EPI == 3) {
                 GemmArgs q{};
                 q.C = p.C;
                 q.bias = p.bias;
@@ -276,8 +331,10 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
                 q.rowadd_div = 1;
                 q.c_bytes = p.c_bytes;
                 q.r_bytes = p.r_bytes;
+                q.colstats = p.colstats;
+                q.ldcs = p.ldcs;
                 float* sB = reinterpret_cast<float*>(smem_raw + Cfg::STAGES) + wave * WN;   // the wave's private strip of column addends
-                gemm_epilogue<Cfg, false, false, 0>(q, acc, tile_m, tile_n, wm, wn, lane, sB);
+                gemm_epilogue<Cfg, false, false, EPI == 3 ? 3 : 0>(q, acc, tile_m, tile_n, wm, wn, lane, sB);
             } else {
                 mx_geglu_epilogue<Cfg, EPI == 2>(p, acc, tile_m, tile_n, wm, wn, lane);
             }
@@ -300,14 +357,15 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #endif
 }
 
-template <class Cfg, int EPI>
+template <class Cfg, int EPI, bool T3 = false>
 int launch_mx(const MxArgs& a, hipStream_t s) {
     static VcxLdsAttr lds;
-    auto kern = gemm_mx_kernel<Cfg, EPI>;
-    if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)Cfg::SMEM, "vcx_gemm_mxfp8")) return VCX_ELAUNCH;
+    auto kern = gemm_mx_kernel<Cfg, EPI, T3>;
+    const char* name = T3 ? "vcx_conv_t3_mxfp8" : "vcx_gemm_mxfp8";
+    if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)Cfg::SMEM, name)) return VCX_ELAUNCH;
     const int nb = persistent_grid(a.tiles_m * a.tiles_n, 2);
     hipLaunchKernelGGL(kern, dim3(nb), dim3(Cfg::THREADS), Cfg::SMEM, s, a);
-    return vcx_check_launch("vcx_gemm_mxfp8");
+    return vcx_check_launch(name);
 }
 
 using Cfg128 = MxCfg<128, 128, 2, 2>;
@@ -341,7 +399,89 @@ bool mx_takes(int64_t M, int64_t N, int64_t K, int flags, int64_t ldc, int64_t l
     return true;
 }
 
+// vcx_conv_t3_mxfp8: shape, flag, pitch and extent rules; `why` gets the reason of a refusal.  cs_col = first column of the moments inside
+// their [strips][ldcs] buffer (the caller's pointer already points there: only its alignment is this function's business).
+bool t3_takes(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int flags, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t cs_col, const char** why) {
+    *why = "flags: BIAS_N, optionally with RESIDUAL and / or COLSTATS";
+    if (!(flags & VCX_GEMM_BIAS_N) || (flags & ~(VCX_GEMM_BIAS_N | VCX_GEMM_RESIDUAL | VCX_GEMM_COLSTATS))) return false;
+    *why = "need B, T, P, Cin, N > 0, Cin % 32 == 0, N % 8 == 0";
+    if (B <= 0 || T <= 0 || P <= 0 || Cin <= 0 || N <= 0 || Cin % MX_BLOCK != 0 || N % 8 != 0) return false;
+    *why = "a dimension of 2^31 or more";
+    constexpr int64_t I31 = 1ll << 31;
+    if (B >= I31 || T >= I31 || P >= I31 || Cin >= I31 || N >= I31 || ldc >= I31 || ldr >= I31 || ldcs >= I31) return false;
+    if (B * T >= I31 || B * T * P >= I31) return false;
+    const unsigned long long M = (unsigned long long)(B * T * P), kp = (unsigned long long)mx_kp(Cin);
+    *why = "row pitches: ldc >= N, ldc % 8 == 0; with RESIDUAL ldr >= N, ldr % 8 == 0";
+    if (ldc < N || ldc % 8 != 0) return false;
+    if ((flags & VCX_GEMM_RESIDUAL) && (ldr < N || ldr % 8 != 0)) return false;
+    *why = "COLSTATS: B T P % 64 == 0, ldcs >= first column + N, ldcs and the first column even (16-byte aligned moment pairs)";
+    if ((flags & VCX_GEMM_COLSTATS) && (M % 64 != 0 || cs_col < 0 || ldcs < cs_col + N || ldcs % 2 != 0 || cs_col % 2 != 0)) return false;
+    // 32-bit buffer offsets.  The tile grid reaches up to 127 rows past M and a tap up to P rows further: (M + 127 + P) Kp must not wrap
+    // for the activation (its scale array is 1/32 of it); the weight rows are 3 Kp long and reach 127 rows past N.
+    *why = "an operand, output or residual extent of 4 GiB or more (32-bit buffer offsets; activations: (M + 127 + P) Kp)";
+    if ((M + 127 + (unsigned long long)P) * kp >= LIM || ((unsigned long long)N + 127) * 3 * kp >= LIM) return false;
+    const unsigned long long mt = (M + 127) / 128 * 128;
+    if (mt * (unsigned long long)ldc * 2 >= LIM) return false;
+    if ((flags & VCX_GEMM_RESIDUAL) && mt * (unsigned long long)ldr * 2 >= LIM) return false;
+    return true;
+}
+
 }  // namespace
+
+extern "C" int vcx_conv_t3_mxfp8_ok(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
+                                    int flags) {
+    const char* why;
+    if (t3_takes(B, T, P, Cin, N, flags, ldc, ldr, ldcs, colstats_col, &why)) return 1;
+    vcx_set_error("vcx_conv_t3_mxfp8_ok(B=%lld, T=%lld, P=%lld, Cin=%lld, N=%lld, ldc=%lld, ldr=%lld, ldcs=%lld, col=%lld, flags=0x%x): %s", (long long)B,
+                  (long long)T, (long long)P, (long long)Cin, (long long)N, (long long)ldc, (long long)ldr, (long long)ldcs, (long long)colstats_col, flags, why);
+    return 0;
+}
+
+extern "C" int vcx_conv_t3_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, const float* bias,
+                                 const void* residual, float* colstats, int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr,
+                                 int64_t ldcs, int flags, void* stream) {
+    VCX_REQUIRE(a && a_scales && w && w_scales && out && bias, "vcx_conv_t3_mxfp8: null pointer");
+    VCX_REQUIRE(!(flags & VCX_GEMM_RESIDUAL) || residual, "vcx_conv_t3_mxfp8: VCX_GEMM_RESIDUAL needs a residual");
+    VCX_REQUIRE(!(flags & VCX_GEMM_COLSTATS) || colstats, "vcx_conv_t3_mxfp8: VCX_GEMM_COLSTATS needs a colstats buffer");
+    const char* why;
+    // (the moments' first column is in the pointer: its parity shows in the pointer's alignment, checked below)
+    VCX_REQUIRE(t3_takes(B, T, P, Cin, N, flags, ldc, ldr, ldcs, 0, &why), "vcx_conv_t3_mxfp8(B=%lld, T=%lld, P=%lld, Cin=%lld, N=%lld, flags=0x%x, ldc=%lld, ldr=%lld, ldcs=%lld): %s",
+                (long long)B, (long long)T, (long long)P, (long long)Cin, (long long)N, flags, (long long)ldc, (long long)ldr, (long long)ldcs, why);
+    VCX_REQUIRE((((uintptr_t)a | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)colstats) & 15) == 0
+                    && (((uintptr_t)a_scales | (uintptr_t)w_scales) & 3) == 0,
+                "vcx_conv_t3_mxfp8: operands, output, bias, residual and colstats must be 16-byte aligned, scale arrays 4-byte aligned");
+    const int64_t M = B * T * P;
+    MxArgs p{};
+    p.A = (const unsigned char*)a;
+    p.As = (const unsigned char*)a_scales;
+    p.W = (const unsigned char*)w;
+    p.Ws = (const unsigned char*)w_scales;
+    p.C = out;
+    p.bias = bias;
+    p.R = (const half_t*)residual;
+    p.M = (int)M;
+    p.N = (int)N;
+    p.kp = (int)mx_kp(Cin);
+    p.T = (int)T;
+    p.P = (int)P;
+    p.ldc = (int)ldc;
+    p.ldr = (int)ldr;
+    p.flags = flags;
+    p.colstats = colstats;
+    p.ldcs = ldcs;
+    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
+    p.tiles_n = (int)((N + Cfg128::TBN - 1) / Cfg128::TBN);
+    p.a_bytes = (unsigned)(M * p.kp);
+    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
+    p.w_bytes = (unsigned)(N * 3 * p.kp);
+    p.ws_bytes = (unsigned)(N * 3 * (p.kp / MX_BLOCK));
+    p.c_bytes = (unsigned)(2 * ((M - 1) * ldc + N));
+    p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + N)) : 0u;
+    hipStream_t s = (hipStream_t)stream;
+    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * 3.0 * Cin, (double)(M + 3 * N) * p.kp + 2.0 * M * N);
+    if (flags & VCX_GEMM_COLSTATS) return launch_mx<Cfg128, 3, true>(p, s);
+    return launch_mx<Cfg128, 0, true>(p, s);
+}
 
 extern "C" int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags) {
     const char* why;

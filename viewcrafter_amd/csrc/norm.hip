@@ -245,6 +245,68 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ x, const half_t* __re
     }
 }
 
+// GroupNorm apply + MXFP8 quantiser in one pass (vcx_groupnorm_apply_mxfp8_f16): gn_apply_kernel's thread map and arithmetic - every value
+// rounded to fp16 as that kernel stores it - then the 32-channel blocks of those fp16 values are quantised (mx_format.h):
+// quant(vcx_groupnorm_apply_f16(x)) byte for byte, without the fp16 tensor in memory (1 + 1/32 bytes written per element instead of 2).
+// C % 32 == 0: cw = C / 8 is a multiple of four, so the four 8-channel chunks of an MX block are the four lanes of a DPP quad, all in the
+// same pixel lane - they walk the pixel loop together and the block maximum is a quad exchange, no LDS.  The thread that owns chunk c8
+// also writes the padding chunks cw + c8, 2 cw + c8, ... of its row up to kp (element bytes 0x00, scale bytes 127).
+__global__ void gn_apply_mx_kernel(const half_t* __restrict__ x, unsigned char* __restrict__ qo, unsigned char* __restrict__ so,
+                                   const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta, int64_t pixels,
+                                   int C, int kp, int groups, float eps, int silu, int64_t pix_per_block, int cw, int pl) {
+    using namespace vcxmx;
+    const int tid = threadIdx.x;
+    const int n = blockIdx.y;
+    const int cpg = C / groups;
+    const int c8 = tid % cw, plane = tid / cw;
+    float sc[8], mn[8], bt[8];      // (x - mean) * sc + beta, as in gn_apply_kernel
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int c = c8 * 8 + e;
+        const int g = c / cpg;
+        const float mean = stats[((int64_t)n * groups + g) * 2 + 0];
+        const float var = stats[((int64_t)n * groups + g) * 2 + 1];
+        const float a = rsqrtf(var + eps) * gamma[c];
+        sc[e] = a;
+        mn[e] = mean;
+        bt[e] = beta[c];
+    }
+    const int64_t p0 = (int64_t)blockIdx.x * pix_per_block;
+    const int64_t p1 = (p0 + pix_per_block < pixels) ? p0 + pix_per_block : pixels;
+    const half_t* xp = x + ((int64_t)n * pixels) * C + c8 * 8;
+    const int kc = kp >> 3, ks = kp >> 5;       // chunks and scale bytes of a padded row
+    auto emit = [&](h8 v, int64_t pix) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float f = __builtin_fmaf((float)v[e] - mn[e], sc[e], bt[e]);
+            if (silu) f = vcx_silu(f);
+            v[e] = (half_t)f;
+        }
+        const unsigned hmax = mx_quad_max(mx_absmax_bits(v));
+        float mul;
+        const unsigned sb = mx_scale_byte(hmax, mul);
+        const int64_t row = (int64_t)n * pixels + pix;
+        unsigned char* qr = qo + row * kp;
+        unsigned char* sr = so + row * ks;
+        *reinterpret_cast<uint2*>(qr + c8 * 8) = mx_quant8(v, sb, mul);
+        if ((c8 & 3) == 0) sr[c8 >> 2] = (unsigned char)sb;
+        for (int c = cw + c8; c < kc; c += cw) {
+            *reinterpret_cast<uint2*>(qr + c * 8) = make_uint2(0u, 0u);
+            if ((c & 3) == 0) sr[c >> 2] = (unsigned char)MX_SCALE_ONE;
+        }
+    };
+    const int64_t step = pl;
+    int64_t pix = p0 + plane;
+    for (; pix + 3 * step < p1; pix += 4 * step) {
+        h8 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const h8*>(xp + (pix + u * step) * C);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) emit(v[u], pix + u * step);
+    }
+    for (; pix < p1; pix += step) emit(*reinterpret_cast<const h8*>(xp + pix * C), pix);
+}
+
 // ---------------------------------------------------------------------------------------
 // LayerNorm: LPR lanes per row (8..64, chosen so a lane holds <= 4 chunks of 8 channels), the row stays in registers:
 // one HBM read, mean then centred variance from the registers (as torch computes them), one HBM write.
@@ -683,6 +745,26 @@ extern "C" int vcx_groupnorm_apply2_f16(const void* x1, int c1, const void* x2, 
                                         int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
     VCX_REQUIRE(x2 && c1 > 0 && c1 < C && c1 % 8 == 0 && ((uintptr_t)x2 & 15) == 0, "vcx_groupnorm_apply2_f16: need 0 < c1 < C, c1 %% 8 == 0, x2 16-byte aligned (c1=%d C=%d)", c1, C);
     return gn_apply_launch(x1, x2, c1, y, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
+}
+
+extern "C" int vcx_groupnorm_apply_mxfp8_f16(const void* x, void* q, void* scales, const float* stats, const float* gamma, const float* beta,
+                                             int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
+    VCX_REQUIRE(x && q && scales && stats && gamma && beta, "vcx_groupnorm_apply_mxfp8_f16: null pointer");
+    VCX_REQUIRE(n_outer > 0 && pixels > 0 && C > 0 && C <= MAXC && groups > 0 && C % groups == 0 && C % 32 == 0,
+                "vcx_groupnorm_apply_mxfp8_f16: need C %% 32 == 0, C %% groups == 0, C <= %d (C=%d groups=%d)", MAXC, C, groups);
+    VCX_REQUIRE((((uintptr_t)x | (uintptr_t)q) & 15) == 0 && ((uintptr_t)scales & 3) == 0,
+                "vcx_groupnorm_apply_mxfp8_f16: x and q must be 16-byte aligned, scales 4-byte aligned");
+    VCX_REQUIRE(n_outer <= 65535, "vcx_groupnorm_apply_mxfp8_f16: n_outer too large");
+    hipStream_t s = (hipStream_t)stream;
+    const int kp = (int)vcxmx::mx_kp(C);
+    VcxProfScope prof(VCX_FAM_GN, s, 0.0, n_outer * (double)pixels * (2.0 * C + kp + kp / 32.0));
+    const int64_t ppb = C <= 640 ? 32 : 16;      // gn_apply_launch's block size
+    dim3 grid((unsigned)((pixels + ppb - 1) / ppb), n_outer);
+    int cw, pl;
+    gn_geometry(C, cw, pl);
+    hipLaunchKernelGGL(gn_apply_mx_kernel, grid, dim3(cw * pl), 0, s, (const half_t*)x, (unsigned char*)q, (unsigned char*)scales, stats, gamma, beta,
+                       pixels, C, kp, groups, eps, silu, ppb, cw, pl);
+    return vcx_check_launch("vcx_groupnorm_apply_mxfp8_f16");
 }
 
 extern "C" int vcx_groupnorm_fold_linear_f16(const float* W, const float* bias, const float* gamma, const float* beta, const float* stats,

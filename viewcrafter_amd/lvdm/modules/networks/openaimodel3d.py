@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from .... import ops
-from ....packing import pack_conv, pack_conv_ups_folded
+from ....packing import pack_conv, pack_conv_t3_mxfp8, pack_conv_ups_folded
 from ..attention import PackedModule, SpatialTransformer, TemporalTransformer, _f16, _f32
 from ..flow import CAT_SPLIT, GN_EPILOGUE_STATS, GN_STATS_LEVEL, CatTarget, Flow, out_kwargs as _out_kwargs
 
@@ -28,6 +28,15 @@ from ..flow import CAT_SPLIT, GN_EPILOGUE_STATS, GN_STATS_LEVEL, CatTarget, Flow
 SKIP_FOLD = os.environ.get("VCX_SKIP_FOLD", "1") != "0"
 # emb_layers of all ResBlocks as ONE projection per forward (round 6); VCX_EMB_BATCHED=0: one launch per block
 EMB_BATCHED = os.environ.get("VCX_EMB_BATCHED", "1") != "0"
+# Opt-in (VCX_TCONV_MXFP8=1, default off): the four (3,1,1) convolutions of a TemporalConvBlock on the block-scaled MXFP8 matrix pipe
+# (include/vcx.h vcx_conv_t3_mxfp8, csrc/gemm_mx.hip) - each GroupNorm + SiLU apply pass writes MXFP8 bytes + block scales instead of fp16
+# (vcx_groupnorm_apply_mxfp8_f16) and the convolution gathers its three taps from them.  Independent of VCX_FF_MXFP8.  Accuracy with a
+# real checkpoint is unmeasured; what was measured is in profiles/mxfp8_tconv.md.  Off: no new launch, no new allocation, every output
+# bit as before.
+TCONV_MXFP8 = os.environ.get("VCX_TCONV_MXFP8", "0") == "1"
+# Block widths that stay on the fp16 route although the switch is on: those whose MX block was measured no faster than its fp16 block
+# (profiles/mxfp8_tconv.md).  VCX_TCONV_MXFP8_SKIP_DIMS="" puts every width on MX.
+TCONV_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_TCONV_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
 
 class TimestepBlock(nn.Module):
     """Marker: modules whose forward takes the timestep embedding (reference openaimodel3d.py:19-28)."""
@@ -192,6 +201,7 @@ class TemporalConvBlock(PackedModule):
                                    nn.Conv3d(out_channels, in_channels, k, padding=p))
         nn.init.zeros_(self.conv4[-1].weight)
         nn.init.zeros_(self.conv4[-1].bias)
+        self._mx = None            # MXFP8 weight pairs of the four convolutions (TCONV_MXFP8): built at the first use of that route
 
     def _pack(self):
         out = []
@@ -200,12 +210,68 @@ class TemporalConvBlock(PackedModule):
             out.append((_f32(gn.weight), _f32(gn.bias), gn.eps, _f16(pack_conv(conv.weight.detach())), _f32(conv.bias)))
         return out
 
+    def _drop_packed(self):
+        super()._drop_packed()
+        self._mx = None
+
+    def _apply(self, fn, recurse=True):
+        self._mx = None
+        return super()._apply(fn, recurse)
+
+    def _mx_plan(self, B, T, P, want_colstats, target):
+        """TCONV_MXFP8: the keywords each of the four convolutions would pass to ops.temporal_conv3_mxfp8 (`colstats`: True where a buffer
+        is to be allocated), or None - the block stays on the fp16 route - at a skipped width or where the library's predicate refuses
+        any of the four.  The predicate is asked about ONE video (a row's route must not depend on the batch it runs in) and about the
+        call itself (only the 32-bit extents depend on B).  Moments are asked for where the host graph's rule allows them: whole 64-row
+        strips per statistics unit (T P rows for the inner norms, P for the per-frame norm behind the block)."""
+        convs = [seq[-1] for seq in (self.conv1, self.conv2, self.conv3, self.conv4)]
+        if any(c.in_channels in TCONV_MXFP8_SKIP_DIMS or c.out_channels in TCONV_MXFP8_SKIP_DIMS or c.bias is None for c in convs):
+            return None
+        plan = []
+        for i, conv in enumerate(convs):
+            last = i == len(convs) - 1
+            if last and target is not None:
+                kw = target.kwargs(conv.in_channels, B * T * P)
+            else:
+                wanted = GN_EPILOGUE_STATS and (want_colstats if last else True)
+                kw = dict(colstats=True) if wanted and (P if last else T * P) % 64 == 0 else {}
+            query = dict(residual=last, ldc=kw.get("ldc"), colstats="colstats" in kw, colstats_ld=kw.get("colstats_ld"), colstats_col=kw.get("colstats_col", 0))
+            if not all(ops.temporal_conv3_mxfp8_ok(b, T, P, conv.in_channels, conv.out_channels, **query) for b in sorted({1, B})):
+                return None
+            plan.append(kw)
+        return plan
+
+    def _forward_mx(self, x, colstats, plan):
+        """The block on the MX route: per stage one quantising GroupNorm + SiLU apply and one gathered convolution; statistics, moments,
+        concat target and the residual of the last stage as on the fp16 route."""
+        B, T, P, C = x.shape
+        stages = self.packed()
+        if self._mx is None:
+            with torch.no_grad():
+                self._mx = [tuple(t.to(x.device) for t in pack_conv_t3_mxfp8(seq[-1].weight.detach())) for seq in (self.conv1, self.conv2, self.conv3, self.conv4)]
+        y = x
+        for i, ((gw, gb, eps, w, b), wmx, kw) in enumerate(zip(stages, self._mx, plan)):
+            cy = y.shape[-1]
+            stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, B, T * P, cy)
+            a = ops.group_norm_mxfp8(y.reshape(B, T * P, cy), gw, gb, eps, True, stats=stats)
+            last = i == len(stages) - 1
+            kw = dict(kw)
+            if kw.get("colstats") is True:
+                kw["colstats"] = ops.colstats_buffer(B * T * P, w.shape[0], x.device)
+            colstats = kw.get("colstats")
+            y = ops.temporal_conv3_mxfp8(a, wmx, b, B=B, T=T, P=P, cin=cy, residual=x.reshape(B * T * P, C) if last else None, **kw)
+        return y, colstats
+
     def forward(self, x, colstats=None, want_colstats=False, target=None):
         """x [B, T, P, C] fp16.  `colstats`: column moments of x written by the layer that produced it (ops.gemm colstats=):
         the first norm then needs no statistics pass; the three inner norms get theirs from this block's own convolutions.
         want_colstats: also produce the moments of the OUTPUT (for the per-frame GroupNorm behind this block); target: write the
         output (and its moments) into a concat buffer.  -> (y, moments of y or None)"""
         B, T, P, C = x.shape
+        if TCONV_MXFP8:
+            plan = self._mx_plan(B, T, P, want_colstats, target)
+            if plan is not None:
+                return self._forward_mx(x, colstats, plan)
         y = x
         stages = self.packed()
         for i, (gw, gb, eps, w, b) in enumerate(stages):

@@ -433,7 +433,8 @@ def layer_norm(x, gamma, beta, eps=1e-5):
 
 
 # ------------------------------------------------------------------------------------------
-# MXFP8 operands (include/vcx.h "MXFP8 operands"; opt-in: the GEGLU feed-forward under VCX_FF_MXFP8=1)
+# MXFP8 operands (include/vcx.h "MXFP8 operands"; opt-in: the GEGLU feed-forward under VCX_FF_MXFP8=1, the TemporalConvBlock convolutions
+# under VCX_TCONV_MXFP8=1)
 # ------------------------------------------------------------------------------------------
 _u8 = torch.uint8
 
@@ -513,6 +514,82 @@ def linear_mxfp8(a, w, bias, *, K, residual=None, geglu=False, mx_out=False):
                                n_out, residual.stride(0) if residual is not None else 0, _mx_flags(residual is not None, geglu, mx_out), _stream()),
           "gemm_mxfp8")
     return out
+
+
+def group_norm_mxfp8(x, gamma, beta, eps, silu, groups=32, stats=None):
+    """quant_mxfp8(group_norm(x, ...).view(rows, C)), byte for byte, in one pass: the normalised fp16 tensor is never written.
+    x [n_outer, pixels, C] fp16 (contiguous, C % 32 == 0); statistics computed here or handed in, as for group_norm.
+    -> (element bytes [n_outer * pixels, Kp], scale bytes [n_outer * pixels, Kp / 32])."""
+    n_outer, pixels, C = x.shape
+    _dev16(x)
+    _dev32(gamma, beta)
+    if not x.is_contiguous():
+        raise VcxError("group_norm_mxfp8: a contiguous [n_outer, pixels, C] tensor needed")
+    L = lib()
+    s = _stream()
+    if stats is None:
+        stats = torch.empty((n_outer, groups, 2), dtype=_f32, device=x.device)
+        ws = torch.empty((L.vcx_groupnorm_ws_bytes(n_outer, pixels, groups),), dtype=torch.uint8, device=x.device)
+        check(L.vcx_groupnorm_stats_f16(x.data_ptr(), stats.data_ptr(), ws.data_ptr(), n_outer, pixels, C, groups, s), "groupnorm_stats")
+    else:
+        _dev32(stats)
+    q, sc = _mx_buffers(n_outer * pixels, C, x.device)
+    check(L.vcx_groupnorm_apply_mxfp8_f16(x.data_ptr(), q.data_ptr(), sc.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                          n_outer, pixels, C, groups, eps, 1 if silu else 0, s), "groupnorm_apply_mxfp8")
+    return q, sc
+
+
+def _t3_flags(residual, colstats):
+    return GEMM_BIAS_N | (GEMM_RESIDUAL if residual else 0) | (GEMM_COLSTATS if colstats else 0)
+
+
+def temporal_conv3_mxfp8_ok(B, T, P, cin, cout, *, residual=False, ldc=None, ldr=None, colstats=False, colstats_ld=None, colstats_col=0):
+    """Does vcx_conv_t3_mxfp8 take a (3,1,1) convolution of B videos x T frames x P pixels x cin channels onto cout channels with these
+    keywords (those of temporal_conv3_mxfp8: `residual` / `colstats` as booleans, pitches as that call would pass them)?  The library's
+    answer - shape, flags, alignment, 32-bit extents; the reason of a refusal is in vcx_last_error()."""
+    ldc = cout if ldc is None else ldc
+    ldr = (cout if ldr is None else ldr) if residual else 0
+    ldcs = (cout if colstats_ld is None else colstats_ld) if colstats else 0
+    return lib().vcx_conv_t3_mxfp8_ok(B, T, P, cin, cout, ldc, ldr, ldcs, colstats_col if colstats else 0, _t3_flags(residual, colstats)) == 1
+
+
+def temporal_conv3_mxfp8(a, w, bias, *, B, T, P, cin, residual=None, ldr=None, out=None, ldc=None, colstats=None, colstats_ld=None, colstats_col=0):
+    """(3,1,1) convolution along T with zero padding on MXFP8 operands: a = (element bytes, scale bytes) of the activation
+    [B * T * P, cin] (group_norm_mxfp8 / quant_mxfp8), w = the pair packing.pack_conv_t3_mxfp8 made of the Conv3d weight.  Returns fp16
+    [B, T, P, cout] (or [.., ldc] when written into `out`); residual / out / ldc / colstats* as in gemm.  Shapes: temporal_conv3_mxfp8_ok -
+    a call the kernel does not take is an error here, not a fall-back."""
+    M = B * T * P
+    kp = mx_kp(cin)
+    cout = w[0].shape[0]
+    _dev_mx(a, M, cin, "temporal_conv3_mxfp8 a")
+    for t, shape in ((w[0], (cout, 3 * kp)), (w[1], (cout, 3 * kp // 32))):
+        if t.dtype is not _u8 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
+            raise VcxError(f"temporal_conv3_mxfp8 w: expected contiguous GPU uint8 {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    _dev32(bias)
+    _dev16(residual, out)
+    if bias is None or bias.numel() != cout or not bias.is_contiguous():
+        raise VcxError(f"temporal_conv3_mxfp8: a contiguous fp32 bias [N = {cout}] is required")
+    if residual is not None:
+        if tuple(residual.shape) != (M, cout) or residual.stride(1) != 1:
+            raise VcxError(f"temporal_conv3_mxfp8: residual must be [{M}, {cout}] with unit column stride, got {tuple(residual.shape)}")
+        ldr = residual.stride(0) if ldr is None else ldr
+    if out is None:
+        out = torch.empty((M, cout), dtype=_f16, device=a[0].device)
+        ldc = cout
+    elif ldc is None:
+        ldc = out.stride(0)
+    if out.numel() < (M - 1) * ldc + cout:
+        raise VcxError(f"temporal_conv3_mxfp8: out holds {out.numel()} elements, [{M}] rows of pitch {ldc} need {(M - 1) * ldc + cout}")
+    cs_ptr, cld = None, 0
+    if colstats is not None:
+        _dev32(colstats)
+        cld = cout if colstats_ld is None else int(colstats_ld)
+        if colstats.numel() != (M // 64) * cld * 2 or colstats_col < 0 or colstats_col + cout > cld:
+            raise VcxError(f"colstats must hold [M / 64, {cld}, 2] floats (M={M}, N={cout}, first column {colstats_col}), got {tuple(colstats.shape)}")
+        cs_ptr = colstats.data_ptr() + 8 * int(colstats_col)
+    check(lib().vcx_conv_t3_mxfp8(a[0].data_ptr(), a[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(), out.data_ptr(), bias.data_ptr(), _ptr(residual), cs_ptr,
+                                  B, T, P, cin, cout, ldc, ldr or 0, cld, _t3_flags(residual is not None, colstats is not None), _stream()), "conv_t3_mxfp8")
+    return out.view(B, T, P, -1)
 
 
 # ------------------------------------------------------------------------------------------

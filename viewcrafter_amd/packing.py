@@ -103,3 +103,17 @@ def pack_mxfp8(w):
     s = torch.full((rows, kp // 32), 127, dtype=torch.uint8)
     s[:, :K // 32] = scale.to(torch.uint8)
     return q.to(w.device), s.to(w.device)
+
+
+def pack_conv_t3_mxfp8(weight):
+    """Conv3d weight [Cout, Cin, 3, 1, 1] (Cin % 32 == 0) -> (element bytes uint8 [Cout, 3 * Kp], scale bytes uint8 [Cout, 3 * Kp / 32]),
+    Kp = Cin rounded up to 128: the weight operand of vcx_conv_t3_mxfp8 (include/vcx.h).  Tap-major - columns [tau Kp, tau Kp + Cin) are
+    weight[:, :, tau] - and every tap is quantised and padded on its own with pack_mxfp8's rule (per 32-channel block inside the tap), so
+    that no MX block and no 128-element K-step of the kernel straddles two taps.  The weight is rounded to fp16 first, as the fp16 route's
+    pack_conv copy is."""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 1, 1) or weight.shape[1] % 32 != 0:
+        raise ValueError(f"pack_conv_t3_mxfp8: need a Conv3d weight [Cout, Cin, 3, 1, 1] with Cin % 32 == 0, got {tuple(weight.shape)}")
+    cout, cin = weight.shape[:2]
+    taps = weight.detach().reshape(cout, cin, 3).permute(0, 2, 1).to(torch.float16).contiguous()      # [Cout, 3, Cin]
+    q, s = pack_mxfp8(taps.view(cout * 3, cin))
+    return q.view(cout, -1).contiguous(), s.view(cout, -1).contiguous()
