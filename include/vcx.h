@@ -40,8 +40,8 @@ extern "C" {
  * tail_a0 / tail_a1 (K tail of a convolution from linear sources); vcx_groupnorm_apply2_f16.  10: vcx_gemm_route.  11: MXFP8 operands - vcx_quant_mxfp8_f16,
  * vcx_layernorm_mxfp8_f16, vcx_gemm_mxfp8, vcx_gemm_mxfp8_ok; VCX_GEMM_MXFP8_OUT.  12: ups = 2 (nearest-2x + 3x3 convolution folded into
  * four 2x2 weight sets on the tiled engine).  13: MXFP8 temporal convolutions - vcx_groupnorm_apply_mxfp8_f16, vcx_conv_t3_mxfp8,
- * vcx_conv_t3_mxfp8_ok. */
-#define VCX_ABI_VERSION 13
+ * vcx_conv_t3_mxfp8_ok.  14: MXFP8 ResBlock 3x3 convolutions - vcx_conv3x3_mxfp8, vcx_conv3x3_mxfp8_ok, vcx_groupnorm_apply2_mxfp8_f16. */
+#define VCX_ABI_VERSION 14
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -249,7 +249,7 @@ int vcx_layernorm_f16(const void* x, void* y, const float* gamma, const float* b
 /* ------------------------------------------------------------------------------------
  * MXFP8 operands (ABI 11): OCP MX with e4m3fn elements and e8m0 scales, for the block-scaled matrix instruction
  * v_mfma_scale_f32_16x16x128_f8f6f4.  Opt-in (the GEGLU feed-forward under VCX_FF_MXFP8=1, the TemporalConvBlock convolutions under
- * VCX_TCONV_MXFP8=1); nothing else uses it.
+ * VCX_TCONV_MXFP8=1, the ResBlock 3x3 convolutions under VCX_RESCONV_MXFP8=1); nothing else uses it.
  *
  * A matrix [rows][K] (K % 32 == 0) is two dense arrays, ONE layout for every producer and consumer:
  *   elements  uint8 [rows][Kp]        Kp = K rounded up to a multiple of 128; row pitch Kp bytes
@@ -312,6 +312,33 @@ int vcx_conv_t3_mxfp8(const void* a, const void* a_scales, const void* w, const 
  * residual below 4 GiB.  ldr / ldcs / colstats_col are ignored without their flag.  Touches no device. */
 int vcx_conv_t3_mxfp8_ok(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
                          int flags);
+/* ABI 14.  vcx_groupnorm_apply_mxfp8_f16 over a channel concat [x1 | x2] that is never materialised (x1 [n_outer][pixels][c1],
+ * x2 [n_outer][pixels][C - c1], as vcx_groupnorm_apply2_f16 reads them): quant(vcx_groupnorm_apply2_f16(...)) byte for byte.  c1 % 8 == 0,
+ * C % 32 == 0; an MX block may straddle the two halves. */
+int vcx_groupnorm_apply2_mxfp8_f16(const void* x1, int c1, const void* x2, void* q, void* scales, const float* stats, const float* gamma,
+                                   const float* beta, int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream);
+/* ABI 14.  Conv2d 3x3, padding 1, on MXFP8 operands - the second gathered mode of vcx_gemm_mxfp8's kernel (the ResBlock convolutions):
+ *   out[(f,y,x), o] = bias[o] + sum_{ky,kx=0..2} sum_c A[(f, y + ky - 1, x + kx - 1), c] W[o, c, ky, kx]
+ *                     (+ rowadd[((f,y,x) / rowadd_div) rowadd_ld + o]) (+ residual[(f,y,x) ldr + o])
+ * pixels outside the row's own frame contribute zero; fp32 accumulation, fp16 output [n H W][ldc] (ldc >= N: a concat buffer).
+ *   a / a_scales   [n H W][Kp(Cin)] / [n H W][Kp(Cin) / 32], as vcx_groupnorm_apply(2)_mxfp8_f16 or vcx_quant_mxfp8_f16 write them
+ *   w / w_scales   [N][Kp / 128][9][128] / [N][Kp / 128][9][4]: slab-major - the K-step of 128 elements at index 9 s + 3 ky + kx holds
+ *                  channels 128 s .. 128 s + 127 of tap (ky, kx) - every tap quantised per 32-channel block and padded to Kp on its own
+ *                  (no block and no K-step mixes taps; packing.pack_conv3x3_mxfp8)
+ *   rowadd         fp32 [.][rowadd_ld], one row per rowadd_div output rows (the timestep embedding: rowadd_div = frames per video * H W)
+ * flags: VCX_GEMM_BIAS_N (required), optionally | VCX_GEMM_ROWADD, | VCX_GEMM_RESIDUAL, | VCX_GEMM_COLSTATS (colstats points at the first of
+ * this call's N columns inside a [n H W / 64][ldcs][2] buffer, as for vcx_gemm_f16).  One tile shape and one K order: a row's bits depend
+ * neither on n, nor on the number of rows, nor on the tile or the grid.  Shapes: vcx_conv3x3_mxfp8_ok. */
+int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, const float* bias, const float* rowadd,
+                      const void* residual, float* colstats, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr,
+                      int64_t ldcs, int64_t rowadd_ld, int64_t rowadd_div, int flags, void* stream);
+/* 1 if vcx_conv3x3_mxfp8 takes the call, else 0 with the reason in vcx_last_error(): the flag words above, Cin % 32 == 0, N % 8 == 0,
+ * ldc / ldr >= N and % 8 == 0, COLSTATS: n H W % 64 == 0, ldcs >= colstats_col + N, ldcs and colstats_col even, ROWADD: rowadd_div > 0, every
+ * dimension below 2^31; 32-bit buffer offsets: (n H W + 127 + W + 1) Kp(Cin) (a tile reaches 127 rows past the last one, the farthest tap
+ * W + 1 rows further), (N + 127) 9 Kp, output and residual below 4 GiB.  ldr / ldcs / colstats_col / rowadd_div are ignored without
+ * their flag.  Touches no device. */
+int vcx_conv3x3_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
+                         int64_t rowadd_div, int flags);
 
 /* ------------------------------------------------------------------------------------
  * Flash attention, head dim 64, no mask:  O = softmax(scale * Q K^T) V

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libvcx.so")
 SYMBOLS = [
     "vcx_abi_version", "vcx_last_error", "vcx_device_arch", "vcx_gemm_f16", "vcx_gemm_units_f16", "vcx_gemm_route", "vcx_quant_mxfp8_f16", "vcx_layernorm_mxfp8_f16", "vcx_gemm_mxfp8", "vcx_gemm_mxfp8_ok",
     "vcx_groupnorm_apply_mxfp8_f16", "vcx_conv_t3_mxfp8", "vcx_conv_t3_mxfp8_ok",
+    "vcx_groupnorm_apply2_mxfp8_f16", "vcx_conv3x3_mxfp8", "vcx_conv3x3_mxfp8_ok",
     "vcx_groupnorm_ws_bytes", "vcx_groupnorm_stats_f16", "vcx_groupnorm_apply_f16", "vcx_groupnorm_apply2_f16", "vcx_groupnorm_stats_from_colstats_f32", "vcx_groupnorm_fold_linear_f16", "vcx_layernorm_f16", "vcx_rowstats_f16",
     "vcx_attn_flash_d64_f16", "vcx_attn_flash_d512_f16", "vcx_attn_flash_dual_d64_f16", "vcx_attn_temporal_d64_f16", "vcx_attn_temporal_d64_masked_f16", "vcx_attn_temporal_d64_rel_f16", "vcx_softmax_rows_f16",
     "vcx_silu_f32", "vcx_gelu_f16", "vcx_clip_preprocess_f32", "vcx_add_nchw_f32_to_nhwc_f16", "vcx_timestep_embedding_f32", "vcx_cast_f32_to_f16", "vcx_cast_f16_to_f32",
@@ -22,7 +23,7 @@ SYMBOLS = [
     "vcx_profile_begin", "vcx_profile_end", "vcx_tune_set", "vcx_tune_get",
 ]
 
-ABI_VERSION = 13         # include/vcx.h VCX_ABI_VERSION
+ABI_VERSION = 14         # include/vcx.h VCX_ABI_VERSION
 # experiment knobs (include/vcx.h VCX_TUNE_*): name -> (index, default)
 TUNE = {"GEMM_CFG": (0, -1), "GEMM_DMA": (1, 1), "FLASH_QB": (2, 0), "XATTN_RESIDENT": (3, 1), "FLASH_IMPL": (4, 0), "EXP0": (5, 0),
         "EXP1": (6, 0), "GEMM_WS": (7, 1)}
@@ -90,6 +91,11 @@ def lib():
     L.vcx_conv_t3_mxfp8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
                                     c_int64, c_int64, c_int64, c_int, c_void_p]
     L.vcx_conv_t3_mxfp8_ok.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int]
+    L.vcx_groupnorm_apply2_mxfp8_f16.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_float,
+                                                 c_int, c_void_p]
+    L.vcx_conv3x3_mxfp8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                    c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]
+    L.vcx_conv3x3_mxfp8_ok.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int]
     L.vcx_groupnorm_ws_bytes.argtypes = [c_int, c_int64, c_int]
     L.vcx_groupnorm_stats_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]
     L.vcx_groupnorm_apply_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,

@@ -28,6 +28,15 @@
 // frame t + tap - 1 of the row's OWN video does not exist the offset is forced out of range, the descriptor zero-fills element and scale
 // bytes and the products are 0 - a row at t = 0 of video b > 0 never reads video b - 1, and m - P < 0 never wraps.  The weight side stays
 // linear in K.
+//
+// vcx_conv3x3_mxfp8 (GM = 2): the 3x3 / padding-1 convolution of a ResBlock, the second gathered mode.  The activation is [n][H][W][Kp], row
+// m = (f H + y) W + x; K is SLAB-major, for the reason packing.conv_slab_major gives for the fp16 engine: K-step kt belongs to the
+// 128-channel slab kt / 9 and to tap kt % 9 = 3 ky + kx (weights [N][Kp / 128][9][128], every tap quantised and padded on its own), so the
+// nine re-reads of a tile's input rows are consecutive K-steps.  Tap (ky, kx) reads row m + (ky - 1) W + (kx - 1), which exists iff
+// 0 <= y + ky - 1 < H and 0 <= x + kx - 1 < W inside the row's OWN frame: six bits per DMA row (three for ky, three for kx, from
+// (m / W) % H and m % W when a tile's offsets are set up; 5 rows x 6 bits in the register T3 uses 15 bits of), a tap is valid iff both of
+// its bits are set, and its offset is one add and one select at issue.  A missing source row gets an out-of-range offset: no read of the
+// neighbouring frame, no wrap to the previous image row at x = 0 or the next one at x = W - 1, no negative offset at m < W + 1.
 #include "gemm_epilogue.h"
 #include "mx_format.h"
 
@@ -57,6 +66,10 @@ struct MxArgs {
     unsigned a_bytes, as_bytes, w_bytes, ws_bytes, c_bytes, cs_bytes, r_bytes;
     // vcx_conv_t3_mxfp8: frames per video, pixels per frame (kp = one tap's K extent, the activation's row pitch; the weight's is 3 kp)
     int T, P;
+    // vcx_conv3x3_mxfp8: the frame's grid (the weight's row pitch is 9 kp) and the row-indexed addend of VCX_GEMM_ROWADD (gemm_epilogue.h)
+    int GH, GW;
+    const float* rowadd;
+    int rowadd_ld, rowadd_div;
     float* colstats;                  // VCX_GEMM_COLSTATS: (mean, M2) per 64-row strip and output column (gemm_epilogue.h, LNF = 3)
     int64_t ldcs;
 };
@@ -145,10 +158,13 @@ __device__ __forceinline__ void mx_geglu_epilogue(const MxArgs& p, f4 (&acc)[Cfg
 }
 
 // EPI: 0 = bias / residual, fp16 out (gemm_epilogue.h, the fp16 engine's epilogue); 1 = GEGLU, fp16 out; 2 = GEGLU, MXFP8 out;
-// 3 = EPI 0 + column moments of the output (VCX_GEMM_COLSTATS).  T3: the gathered temporal convolution (file header).
-template <class Cfg, int EPI, bool T3 = false>
+// 3 = EPI 0 + column moments of the output (VCX_GEMM_COLSTATS).  GM, the gather mode of the activation operand: 0 = linear, 1 = the temporal
+// 3-tap convolution, 2 = the spatial 3x3 convolution (file header).
+template <class Cfg, int EPI, int GM = 0>
 __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool T3 = GM == 1, C9 = GM == 2, GATHER = GM != 0;
+    constexpr int VB = C9 ? 6 : 3;      // validity bits per DMA row
     constexpr int TBM = Cfg::TBM, TBN = Cfg::TBN, NFRAG = Cfg::NF, MFRAG = Cfg::MF;
     constexpr int XROWS = Cfg::XROWS, WROWS = Cfg::WROWS, RSTEP = Cfg::RSTEP;
     constexpr int WM = TBM / Cfg::NWM, WN = TBN / Cfg::NWN;
@@ -172,15 +188,22 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 
     unsigned xoff[XROWS], woff[WROWS], soff_v;
     // T3: bit 3 i + tap = the source row of tap `tap` exists for this thread's DMA row i (i = XROWS: its scale row); xoff / soff_v then hold
-    // the offsets of the centre tap whether or not the row is below M
+    // the offsets of the centre tap whether or not the row is below M.  C9: bits 6 i + ky and 6 i + 3 + kx, tap (ky, kx) exists iff both are set
     [[maybe_unused]] unsigned vbits = 0;
     [[maybe_unused]] const unsigned tap_step = T3 ? (unsigned)p.P * (unsigned)p.kp : 0u;      // bytes between a row and the same pixel one frame on
-    [[maybe_unused]] const int nk_tap = p.kp / KSTEP;
+    [[maybe_unused]] const int nk_tap = p.kp / KSTEP;      // K-steps of a tap (T3) = channel slabs (C9)
     [[maybe_unused]] auto tap_bits = [&](int m) -> unsigned {
         if (m >= p.M) return 0u;
-        const unsigned t = ((unsigned)m / (unsigned)p.P) % (unsigned)p.T;
-        return 2u | (t > 0u ? 1u : 0u) | (t + 1u < (unsigned)p.T ? 4u : 0u);
+        if constexpr (C9) {
+            const unsigned q = (unsigned)m / (unsigned)p.GW;
+            const unsigned x = (unsigned)m - q * (unsigned)p.GW, y = q % (unsigned)p.GH;
+            return 2u | (y > 0u ? 1u : 0u) | (y + 1u < (unsigned)p.GH ? 4u : 0u) | 16u | (x > 0u ? 8u : 0u) | (x + 1u < (unsigned)p.GW ? 32u : 0u);
+        } else {
+            const unsigned t = ((unsigned)m / (unsigned)p.P) % (unsigned)p.T;
+            return 2u | (t > 0u ? 1u : 0u) | (t + 1u < (unsigned)p.T ? 4u : 0u);
+        }
     };
+    const unsigned wpitch = (unsigned)(C9 ? 9 * p.kp : T3 ? 3 * p.kp : p.kp);      // bytes of a weight row
     auto init_load = [&](int t) {
         int tile_m, tile_n;
         tile_coords(t, ntiles, p.tiles_n, tile_m, tile_n);
@@ -189,9 +212,9 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             const int r = r0 + RSTEP * i;
             const int m = tile_m * TBM + r;
             const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;   // source chunk that lands at position `chunk`
-            if constexpr (T3) {
+            if constexpr (GATHER) {
                 xoff[i] = (unsigned)m * (unsigned)p.kp + csrc;
-                vbits = i == 0 ? tap_bits(m) : vbits | (tap_bits(m) << (3 * i));
+                vbits = i == 0 ? tap_bits(m) : vbits | (tap_bits(m) << (VB * i));
             } else {
                 xoff[i] = m < p.M ? (unsigned)m * (unsigned)p.kp + csrc : OOB;
             }
@@ -201,33 +224,42 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             const int r = r0 + RSTEP * i;
             const int n = tile_n * TBN + r;
             const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;
-            woff[i] = n < p.N ? (unsigned)n * (unsigned)(T3 ? 3 * p.kp : p.kp) + csrc : OOB;
+            woff[i] = n < p.N ? (unsigned)n * wpitch + csrc : OOB;
         }
         const unsigned spitch = (unsigned)(p.kp >> 5);
         if (scale_is_a) {
             const int m = tile_m * TBM + tid;
-            if constexpr (T3) {
+            if constexpr (GATHER) {
                 soff_v = (unsigned)m * spitch;
-                vbits |= tap_bits(m) << (3 * XROWS);
+                vbits |= tap_bits(m) << (VB * XROWS);
             } else {
                 soff_v = m < p.M ? (unsigned)m * spitch : OOB;
             }
         } else {
             const int n = tile_n * TBN + (tid - TBM);
-            soff_v = n < p.N ? (unsigned)n * (T3 ? 3u * spitch : spitch) : OOB;
+            soff_v = n < p.N ? (unsigned)n * (wpitch >> 5) : OOB;
         }
     };
-    // issue the DMA of K-step kt of the load tile into LDS stage `buf` (T3: kt is K-step kk of tap `tap`, kt = tap nk_tap + kk)
+    // issue the DMA of K-step kt of the load tile into LDS stage `buf` (T3: kt is K-step kk of tap `tap`, kt = tap nk_tap + kk; C9: kt is
+    // tap `tap` of slab kk, kt = 9 kk + tap)
     auto load_tile = [&](int kt, int buf, [[maybe_unused]] int tap = 0, [[maybe_unused]] int kk = 0) {
         unsigned char* dx = sT + buf * Cfg::TILE + wave * 8 * KSTEP;
         unsigned char* dw = sT + buf * Cfg::TILE + TBM * KSTEP + wave * 8 * KSTEP;
         const unsigned soff = (unsigned)kt * KSTEP;
-        const unsigned soff_x = T3 ? (unsigned)kk * KSTEP : soff;
-        [[maybe_unused]] const unsigned shift = (unsigned)(tap - 1) * tap_step;      // (tap - 1) P rows of kp bytes, modulo 2^32: exact for every row that exists
+        const unsigned soff_x = GATHER ? (unsigned)kk * KSTEP : soff;
+        // the tap's distance in rows, times kp bytes (kp / 32 scale bytes), modulo 2^32: exact for every row that exists
+        [[maybe_unused]] const int ky = C9 ? tap / 3 : 0, kx = C9 ? tap - 3 * ky : 0;
+        [[maybe_unused]] const unsigned drow = C9 ? (unsigned)((ky - 1) * p.GW + (kx - 1)) : 0u;
+        [[maybe_unused]] const unsigned shift = C9 ? drow * (unsigned)p.kp : (unsigned)(tap - 1) * tap_step;
+        [[maybe_unused]] const unsigned sshift = C9 ? drow * (unsigned)(p.kp >> 5) : (unsigned)(tap - 1) * (tap_step >> 5);
+        [[maybe_unused]] auto valid = [&](int i) -> bool {      // the source row of this tap exists for DMA row i
+            if constexpr (C9) return ((vbits >> (VB * i + ky)) & (vbits >> (VB * i + 3 + kx)) & 1u) != 0u;
+            else return ((vbits >> (VB * i + tap)) & 1u) != 0u;
+        };
 #pragma unroll
         for (int i = 0; i < XROWS; ++i) {
             unsigned vo = xoff[i];
-            if constexpr (T3) vo = ((vbits >> (3 * i + tap)) & 1u) ? vo + shift : OOB;
+            if constexpr (GATHER) vo = valid(i) ? vo + shift : OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_a, (lds_ptr_t)(dx + RSTEP * i * KSTEP), 16, vo, soff_x, 0, 0);
         }
 #pragma unroll
@@ -235,9 +267,9 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_w, (lds_ptr_t)(dw + RSTEP * i * KSTEP), 16, woff[i], soff, 0, 0);
         // the K-step's four scale bytes of every tile row: one dword per thread, lane-linear behind the wave's base
         unsigned* ds = sS + buf * (TBM + TBN) + wave * 64;
-        if constexpr (T3) {
+        if constexpr (GATHER) {
             if (scale_is_a) {
-                const unsigned vo = ((vbits >> (3 * XROWS + tap)) & 1u) ? soff_v + (unsigned)(tap - 1) * (tap_step >> 5) : OOB;
+                const unsigned vo = valid(XROWS) ? soff_v + sshift : OOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_as, (lds_ptr_t)ds, 4, vo, (unsigned)kk * 4u, 0, 0);
             } else {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_ws, (lds_ptr_t)ds, 4, soff_v, (unsigned)kt * 4u, 0, 0);
@@ -256,14 +288,14 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #pragma unroll
         for (int b = 0; b < MFRAG; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = T3 ? 3 * nk_tap : p.kp / KSTEP;
-    [[maybe_unused]] int ltap = 0, lkk = 0;      // T3: tap and K-step inside the tap of the load side's lkt
+    const int nk = C9 ? 9 * nk_tap : T3 ? 3 * nk_tap : p.kp / KSTEP;
+    [[maybe_unused]] int ltap = 0, lkk = 0;      // T3: tap and K-step inside the tap of the load side's lkt; C9: tap and slab
     int ltile = blockIdx.x, lkt = 0;
     int ctile = blockIdx.x, ckt = 0;
     int tile_m, tile_n;
     tile_coords(ctile, ntiles, p.tiles_n, tile_m, tile_n);
     init_load(ltile);
-    load_tile(0, 0);
+    load_tile(0, 0, 0, 0);
     __builtin_amdgcn_s_waitcnt(0x0f70 | 0);   // vmcnt(0): first K-step landed in LDS
     __syncthreads();
     int cur = 0;
@@ -272,11 +304,16 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             lkt = 0;
             ltile += G;
             if (ltile < ntiles) init_load(ltile);
-            if constexpr (T3) ltap = lkk = 0;
+            if constexpr (GATHER) ltap = lkk = 0;
         } else if constexpr (T3) {
             if (++lkk == nk_tap) {
                 lkk = 0;
                 ++ltap;
+            }
+        } else if constexpr (C9) {
+            if (++ltap == 9) {
+                ltap = 0;
+                ++lkk;
             }
         }
         const bool more = ltile < ntiles;
@@ -329,6 +366,11 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
                 q.flags = p.flags;
                 q.alpha = 1.0f;
                 q.rowadd_div = 1;
+                if constexpr (C9) {
+                    q.rowadd = p.rowadd;
+                    q.rowadd_ld = p.rowadd_ld;
+                    q.rowadd_div = p.rowadd_div;
+                }
                 q.c_bytes = p.c_bytes;
                 q.r_bytes = p.r_bytes;
                 q.colstats = p.colstats;
@@ -357,11 +399,11 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #endif
 }
 
-template <class Cfg, int EPI, bool T3 = false>
+template <class Cfg, int EPI, int GM = 0>
 int launch_mx(const MxArgs& a, hipStream_t s) {
     static VcxLdsAttr lds;
-    auto kern = gemm_mx_kernel<Cfg, EPI, T3>;
-    const char* name = T3 ? "vcx_conv_t3_mxfp8" : "vcx_gemm_mxfp8";
+    auto kern = gemm_mx_kernel<Cfg, EPI, GM>;
+    const char* name = GM == 2 ? "vcx_conv3x3_mxfp8" : GM == 1 ? "vcx_conv_t3_mxfp8" : "vcx_gemm_mxfp8";
     if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)Cfg::SMEM, name)) return VCX_ELAUNCH;
     const int nb = persistent_grid(a.tiles_m * a.tiles_n, 2);
     hipLaunchKernelGGL(kern, dim3(nb), dim3(Cfg::THREADS), Cfg::SMEM, s, a);
@@ -426,7 +468,99 @@ bool t3_takes(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int flags
     return true;
 }
 
+// vcx_conv3x3_mxfp8: shape, flag, pitch and extent rules; `why` gets the reason of a refusal (cs_col as in t3_takes)
+bool c9_takes(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int flags, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t cs_col, int64_t rowadd_div,
+              const char** why) {
+    *why = "flags: BIAS_N, optionally with ROWADD, RESIDUAL and / or COLSTATS";
+    if (!(flags & VCX_GEMM_BIAS_N) || (flags & ~(VCX_GEMM_BIAS_N | VCX_GEMM_ROWADD | VCX_GEMM_RESIDUAL | VCX_GEMM_COLSTATS))) return false;
+    *why = "need n, H, W, Cin, N > 0, Cin % 32 == 0, N % 8 == 0";
+    if (n <= 0 || H <= 0 || W <= 0 || Cin <= 0 || N <= 0 || Cin % MX_BLOCK != 0 || N % 8 != 0) return false;
+    *why = "a dimension of 2^31 or more";
+    constexpr int64_t I31 = 1ll << 31;
+    if (n >= I31 || H >= I31 || W >= I31 || Cin >= I31 || N >= I31 || ldc >= I31 || ldr >= I31 || ldcs >= I31 || rowadd_div >= I31) return false;
+    if (n * H >= I31 || n * H * W >= I31) return false;
+    const unsigned long long M = (unsigned long long)(n * H * W), kp = (unsigned long long)mx_kp(Cin);
+    *why = "row pitches: ldc >= N, ldc % 8 == 0; with RESIDUAL ldr >= N, ldr % 8 == 0";
+    if (ldc < N || ldc % 8 != 0) return false;
+    if ((flags & VCX_GEMM_RESIDUAL) && (ldr < N || ldr % 8 != 0)) return false;
+    *why = "COLSTATS: n H W % 64 == 0, ldcs >= first column + N, ldcs and the first column even (16-byte aligned moment pairs)";
+    if ((flags & VCX_GEMM_COLSTATS) && (M % 64 != 0 || cs_col < 0 || ldcs < cs_col + N || ldcs % 2 != 0 || cs_col % 2 != 0)) return false;
+    *why = "ROWADD: rowadd_div > 0 (output rows per row of the addend)";
+    if ((flags & VCX_GEMM_ROWADD) && rowadd_div <= 0) return false;
+    // 32-bit buffer offsets.  The tile grid reaches up to 127 rows past M and the farthest tap W + 1 rows further: (M + 127 + W + 1) Kp must
+    // not wrap for the activation (its scale array is 1/32 of it); the weight rows are 9 Kp long and reach 127 rows past N.
+    *why = "an operand, output or residual extent of 4 GiB or more (32-bit buffer offsets; activations: (M + 127 + W + 1) Kp)";
+    if ((M + 127 + (unsigned long long)W + 1) * kp >= LIM || ((unsigned long long)N + 127) * 9 * kp >= LIM) return false;
+    const unsigned long long mt = (M + 127) / 128 * 128;
+    if (mt * (unsigned long long)ldc * 2 >= LIM) return false;
+    if ((flags & VCX_GEMM_RESIDUAL) && mt * (unsigned long long)ldr * 2 >= LIM) return false;
+    return true;
+}
+
 }  // namespace
+
+extern "C" int vcx_conv3x3_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
+                                    int64_t rowadd_div, int flags) {
+    const char* why;
+    if (c9_takes(n, H, W, Cin, N, flags, ldc, ldr, ldcs, colstats_col, rowadd_div, &why)) return 1;
+    vcx_set_error("vcx_conv3x3_mxfp8_ok(n=%lld, H=%lld, W=%lld, Cin=%lld, N=%lld, ldc=%lld, ldr=%lld, ldcs=%lld, col=%lld, rowadd_div=%lld, flags=0x%x): %s",
+                  (long long)n, (long long)H, (long long)W, (long long)Cin, (long long)N, (long long)ldc, (long long)ldr, (long long)ldcs, (long long)colstats_col,
+                  (long long)rowadd_div, flags, why);
+    return 0;
+}
+
+extern "C" int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, const float* bias, const float* rowadd,
+                                 const void* residual, float* colstats, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr,
+                                 int64_t ldcs, int64_t rowadd_ld, int64_t rowadd_div, int flags, void* stream) {
+    VCX_REQUIRE(a && a_scales && w && w_scales && out && bias, "vcx_conv3x3_mxfp8: null pointer");
+    VCX_REQUIRE(!(flags & VCX_GEMM_ROWADD) || rowadd, "vcx_conv3x3_mxfp8: VCX_GEMM_ROWADD needs a rowadd");
+    VCX_REQUIRE(!(flags & VCX_GEMM_RESIDUAL) || residual, "vcx_conv3x3_mxfp8: VCX_GEMM_RESIDUAL needs a residual");
+    VCX_REQUIRE(!(flags & VCX_GEMM_COLSTATS) || colstats, "vcx_conv3x3_mxfp8: VCX_GEMM_COLSTATS needs a colstats buffer");
+    const char* why;
+    // (the moments' first column is in the pointer: its parity shows in the pointer's alignment, checked below)
+    VCX_REQUIRE(c9_takes(n, H, W, Cin, N, flags, ldc, ldr, ldcs, 0, rowadd_div, &why),
+                "vcx_conv3x3_mxfp8(n=%lld, H=%lld, W=%lld, Cin=%lld, N=%lld, flags=0x%x, ldc=%lld, ldr=%lld, ldcs=%lld, rowadd_div=%lld): %s", (long long)n,
+                (long long)H, (long long)W, (long long)Cin, (long long)N, flags, (long long)ldc, (long long)ldr, (long long)ldcs, (long long)rowadd_div, why);
+    VCX_REQUIRE(!(flags & VCX_GEMM_ROWADD) || (rowadd_ld >= N && rowadd_ld % 4 == 0 && rowadd_ld < (1ll << 31)),
+                "vcx_conv3x3_mxfp8: VCX_GEMM_ROWADD needs rowadd_ld >= N, rowadd_ld %% 4 == 0 (rowadd_ld=%lld)", (long long)rowadd_ld);
+    VCX_REQUIRE((((uintptr_t)a | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)rowadd | (uintptr_t)residual | (uintptr_t)colstats) & 15) == 0
+                    && (((uintptr_t)a_scales | (uintptr_t)w_scales) & 3) == 0,
+                "vcx_conv3x3_mxfp8: operands, output, bias, rowadd, residual and colstats must be 16-byte aligned, scale arrays 4-byte aligned");
+    const int64_t M = n * H * W;
+    MxArgs p{};
+    p.A = (const unsigned char*)a;
+    p.As = (const unsigned char*)a_scales;
+    p.W = (const unsigned char*)w;
+    p.Ws = (const unsigned char*)w_scales;
+    p.C = out;
+    p.bias = bias;
+    p.R = (const half_t*)residual;
+    p.M = (int)M;
+    p.N = (int)N;
+    p.kp = (int)mx_kp(Cin);
+    p.GH = (int)H;
+    p.GW = (int)W;
+    p.rowadd = (flags & VCX_GEMM_ROWADD) ? rowadd : nullptr;
+    p.rowadd_ld = (flags & VCX_GEMM_ROWADD) ? (int)rowadd_ld : 0;
+    p.rowadd_div = (flags & VCX_GEMM_ROWADD) ? (int)rowadd_div : 1;
+    p.ldc = (int)ldc;
+    p.ldr = (int)ldr;
+    p.flags = flags;
+    p.colstats = colstats;
+    p.ldcs = ldcs;
+    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
+    p.tiles_n = (int)((N + Cfg128::TBN - 1) / Cfg128::TBN);
+    p.a_bytes = (unsigned)(M * p.kp);
+    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
+    p.w_bytes = (unsigned)(N * 9 * p.kp);
+    p.ws_bytes = (unsigned)(N * 9 * (p.kp / MX_BLOCK));
+    p.c_bytes = (unsigned)(2 * ((M - 1) * ldc + N));
+    p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + N)) : 0u;
+    hipStream_t s = (hipStream_t)stream;
+    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * 9.0 * Cin, (double)(M + 9 * N) * p.kp + 2.0 * M * N);
+    if (flags & VCX_GEMM_COLSTATS) return launch_mx<Cfg128, 3, 2>(p, s);
+    return launch_mx<Cfg128, 0, 2>(p, s);
+}
 
 extern "C" int vcx_conv_t3_mxfp8_ok(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
                                     int flags) {
@@ -479,8 +613,8 @@ extern "C" int vcx_conv_t3_mxfp8(const void* a, const void* a_scales, const void
     p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + N)) : 0u;
     hipStream_t s = (hipStream_t)stream;
     VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * 3.0 * Cin, (double)(M + 3 * N) * p.kp + 2.0 * M * N);
-    if (flags & VCX_GEMM_COLSTATS) return launch_mx<Cfg128, 3, true>(p, s);
-    return launch_mx<Cfg128, 0, true>(p, s);
+    if (flags & VCX_GEMM_COLSTATS) return launch_mx<Cfg128, 3, 1>(p, s);
+    return launch_mx<Cfg128, 0, 1>(p, s);
 }
 
 extern "C" int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags) {

@@ -251,7 +251,10 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ x, const half_t* __re
 // C % 32 == 0: cw = C / 8 is a multiple of four, so the four 8-channel chunks of an MX block are the four lanes of a DPP quad, all in the
 // same pixel lane - they walk the pixel loop together and the block maximum is a quad exchange, no LDS.  The thread that owns chunk c8
 // also writes the padding chunks cw + c8, 2 cw + c8, ... of its row up to kp (element bytes 0x00, scale bytes 127).
-__global__ void gn_apply_mx_kernel(const half_t* __restrict__ x, unsigned char* __restrict__ qo, unsigned char* __restrict__ so,
+// x2 != nullptr (vcx_groupnorm_apply2_mxfp8_f16): gn_apply_kernel's two-source addressing of a channel concat [x | x2] that is never
+// materialised (c1 % 8 == 0: a thread's chunk lies in one half; an MX block may straddle the halves - the quad maximum does not care
+// where its four chunks were read).
+__global__ void gn_apply_mx_kernel(const half_t* __restrict__ x, const half_t* __restrict__ x2, int c1, unsigned char* __restrict__ qo, unsigned char* __restrict__ so,
                                    const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta, int64_t pixels,
                                    int C, int kp, int groups, float eps, int silu, int64_t pix_per_block, int cw, int pl) {
     using namespace vcxmx;
@@ -273,7 +276,13 @@ __global__ void gn_apply_mx_kernel(const half_t* __restrict__ x, unsigned char* 
     }
     const int64_t p0 = (int64_t)blockIdx.x * pix_per_block;
     const int64_t p1 = (p0 + pix_per_block < pixels) ? p0 + pix_per_block : pixels;
+    int64_t Cx = C;                  // row stride of this thread's source
     const half_t* xp = x + ((int64_t)n * pixels) * C + c8 * 8;
+    if (x2) {
+        const bool right = c8 * 8 >= c1;
+        Cx = right ? C - c1 : c1;
+        xp = (right ? x2 - c1 : x) + ((int64_t)n * pixels) * Cx + c8 * 8;
+    }
     const int kc = kp >> 3, ks = kp >> 5;       // chunks and scale bytes of a padded row
     auto emit = [&](h8 v, int64_t pix) {
 #pragma unroll
@@ -300,11 +309,11 @@ __global__ void gn_apply_mx_kernel(const half_t* __restrict__ x, unsigned char* 
     for (; pix + 3 * step < p1; pix += 4 * step) {
         h8 v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const h8*>(xp + (pix + u * step) * C);
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const h8*>(xp + (pix + u * step) * Cx);
 #pragma unroll
         for (int u = 0; u < 4; ++u) emit(v[u], pix + u * step);
     }
-    for (; pix < p1; pix += step) emit(*reinterpret_cast<const h8*>(xp + pix * C), pix);
+    for (; pix < p1; pix += step) emit(*reinterpret_cast<const h8*>(xp + pix * Cx), pix);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -747,8 +756,8 @@ extern "C" int vcx_groupnorm_apply2_f16(const void* x1, int c1, const void* x2, 
     return gn_apply_launch(x1, x2, c1, y, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
 }
 
-extern "C" int vcx_groupnorm_apply_mxfp8_f16(const void* x, void* q, void* scales, const float* stats, const float* gamma, const float* beta,
-                                             int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
+static int gn_apply_mx_launch(const void* x, const void* x2, int c1, void* q, void* scales, const float* stats, const float* gamma, const float* beta,
+                              int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
     VCX_REQUIRE(x && q && scales && stats && gamma && beta, "vcx_groupnorm_apply_mxfp8_f16: null pointer");
     VCX_REQUIRE(n_outer > 0 && pixels > 0 && C > 0 && C <= MAXC && groups > 0 && C % groups == 0 && C % 32 == 0,
                 "vcx_groupnorm_apply_mxfp8_f16: need C %% 32 == 0, C %% groups == 0, C <= %d (C=%d groups=%d)", MAXC, C, groups);
@@ -762,9 +771,21 @@ extern "C" int vcx_groupnorm_apply_mxfp8_f16(const void* x, void* q, void* scale
     dim3 grid((unsigned)((pixels + ppb - 1) / ppb), n_outer);
     int cw, pl;
     gn_geometry(C, cw, pl);
-    hipLaunchKernelGGL(gn_apply_mx_kernel, grid, dim3(cw * pl), 0, s, (const half_t*)x, (unsigned char*)q, (unsigned char*)scales, stats, gamma, beta,
+    hipLaunchKernelGGL(gn_apply_mx_kernel, grid, dim3(cw * pl), 0, s, (const half_t*)x, (const half_t*)x2, c1, (unsigned char*)q, (unsigned char*)scales, stats, gamma, beta,
                        pixels, C, kp, groups, eps, silu, ppb, cw, pl);
     return vcx_check_launch("vcx_groupnorm_apply_mxfp8_f16");
+}
+
+extern "C" int vcx_groupnorm_apply_mxfp8_f16(const void* x, void* q, void* scales, const float* stats, const float* gamma, const float* beta,
+                                             int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
+    return gn_apply_mx_launch(x, nullptr, 0, q, scales, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
+}
+
+extern "C" int vcx_groupnorm_apply2_mxfp8_f16(const void* x1, int c1, const void* x2, void* q, void* scales, const float* stats, const float* gamma,
+                                              const float* beta, int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
+    VCX_REQUIRE(x2 && c1 > 0 && c1 < C && c1 % 8 == 0 && ((uintptr_t)x2 & 15) == 0,
+                "vcx_groupnorm_apply2_mxfp8_f16: need 0 < c1 < C, c1 %% 8 == 0, x2 16-byte aligned (c1=%d C=%d)", c1, C);
+    return gn_apply_mx_launch(x1, x2, c1, q, scales, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
 }
 
 extern "C" int vcx_groupnorm_fold_linear_f16(const float* W, const float* bias, const float* gamma, const float* beta, const float* stats,

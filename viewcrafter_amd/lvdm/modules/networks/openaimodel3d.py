@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from .... import ops
-from ....packing import pack_conv, pack_conv_t3_mxfp8, pack_conv_ups_folded
+from ....packing import pack_conv, pack_conv3x3_mxfp8, pack_conv_t3_mxfp8, pack_conv_ups_folded
 from ..attention import PackedModule, SpatialTransformer, TemporalTransformer, _f16, _f32
 from ..flow import CAT_SPLIT, GN_EPILOGUE_STATS, GN_STATS_LEVEL, CatTarget, Flow, out_kwargs as _out_kwargs
 
@@ -37,6 +37,19 @@ TCONV_MXFP8 = os.environ.get("VCX_TCONV_MXFP8", "0") == "1"
 # Block widths that stay on the fp16 route although the switch is on: those whose MX block was measured no faster than its fp16 block
 # (profiles/mxfp8_tconv.md).  VCX_TCONV_MXFP8_SKIP_DIMS="" puts every width on MX.
 TCONV_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_TCONV_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+# Opt-in (VCX_RESCONV_MXFP8=1, default off): the two 3x3 convolutions of a ResBlock on the block-scaled MXFP8 matrix pipe (include/vcx.h
+# vcx_conv3x3_mxfp8, the second gathered mode of csrc/gemm_mx.hip) - the GroupNorm + SiLU apply pass in front of an MX convolution writes
+# MXFP8 bytes + block scales (vcx_groupnorm_apply_mxfp8_f16 / apply2 over a split concat).  Independent of VCX_FF_MXFP8 and
+# VCX_TCONV_MXFP8.  Accuracy with a real checkpoint is unmeasured; what was measured is in profiles/mxfp8_resconv.md.  Off: no new
+# launch, no new allocation, every output bit as before.
+RESCONV_MXFP8 = os.environ.get("VCX_RESCONV_MXFP8", "0") == "1"
+# Block widths (out_channels) that stay on the fp16 route although the switch is on: those whose MX block was measured no faster than its
+# fp16 block - none (profiles/mxfp8_resconv.md: 1.04x at the least), so the default list is empty.
+RESCONV_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_RESCONV_MXFP8_SKIP_DIMS", "").split(",") if v.strip())
+# A block with a 1x1 skip convolution: 1 = its second convolution stays on the fp16 engine with the skip folded in as a K tail and only the
+# first one is MX; 0 (default: the faster one in the isolated A/B, 1.22x / 1.29x against 1.06x / 1.11x, profiles/mxfp8_resconv.md) = the
+# second one is MX too and takes the separate fp16 skip convolution's result as its residual.
+RESCONV_MXFP8_KEEP_FOLD = os.environ.get("VCX_RESCONV_MXFP8_KEEP_FOLD", "0") == "1"
 
 class TimestepBlock(nn.Module):
     """Marker: modules whose forward takes the timestep embedding (reference openaimodel3d.py:19-28)."""
@@ -325,6 +338,102 @@ class ResBlock(PackedModule, TimestepBlock):
             self.temopral_conv = TemporalConvBlock(self.out_channels, self.out_channels, dropout=0.1,
                                                    spatial_aware=tempspatial_aware)
         self._emb_all = None       # set by UNetModel._forward for the length of one forward: this block's columns of the batched emb projection
+        self._mx = {}              # MXFP8 weight pairs of the 3x3 convolutions (RESCONV_MXFP8), by name: built at the first use of that route
+
+    def _drop_packed(self):
+        super()._drop_packed()
+        self._mx = {}
+
+    def _apply(self, fn, recurse=True):
+        self._mx = {}
+        return super()._apply(fn, recurse)
+
+    def _mx_weight(self, name, conv, device):
+        if name not in self._mx:
+            with torch.no_grad():
+                self._mx[name] = tuple(t.to(device) for t in pack_conv3x3_mxfp8(conv.weight.detach()))
+        return self._mx[name]
+
+    def _forward_mx(self, x, emb, batch_size, want_colstats, colstats, target, x2):
+        """RESCONV_MXFP8: the block with one or both 3x3 convolutions on the MX route, or None - the block stays on the fp16 route,
+        nothing launched - where the library's predicate takes neither.  Each convolution is decided on its own, asked about ONE
+        video's frames (a row's route must not depend on the batch it runs in) and about the call's (only the 32-bit extents depend on
+        n); the GroupNorm + SiLU apply in front of a convolution is the quantising one iff that convolution is MX.  Moments are asked
+        for where the host graph's rule allows them: whole 64-row strips per statistics unit.  A block with a skip convolution keeps
+        its second convolution on the fp16 engine with the folded K tail under RESCONV_MXFP8_KEEP_FOLD, and wherever the skip's input
+        is a split concat read in place (the K tail takes two sources, a separate skip convolution does not); otherwise the second
+        convolution is MX with the fp16 skip convolution's result as its residual."""
+        n, H, W, c1 = x.shape
+        cin = c1 + (0 if x2 is None else x2.shape[-1])
+        cout = self.out_channels
+        if cin % 32 != 0 or not x.is_contiguous():      # (the quantising apply reads dense rows; a strided view stays on the fp16 route)
+            return None
+        pk = self.packed()
+        has_skip = "ws" in pk
+        B = emb.shape[0]
+        M, fpv = n * H * W, n // B
+        fold_skip = SKIP_FOLD and has_skip and ops.conv_tail_ok(M, cout, cout, 9, [cin] if x2 is None else [c1, cin - c1])
+        inplace = x2 is not None and fold_skip and colstats is not None and c1 % 8 == 0 and x2.is_contiguous()
+        if x2 is not None and not inplace:
+            fold_skip = SKIP_FOLD and has_skip and ops.conv_tail_ok(M, cout, cout, 9, [cin])
+        frames = sorted({fpv, n})
+        cs1_mx = GN_EPILOGUE_STATS and (H * W) % 64 == 0
+        mx1 = all(ops.conv3x3_mxfp8_ok(f, H, W, cin, cout, rowadd=True, rowadd_div=fpv * H * W, colstats=cs1_mx) for f in frames)
+        temporal = self.use_temporal_conv and batch_size
+        if temporal:
+            kw2 = dict(colstats=True) if GN_EPILOGUE_STATS and ((n // batch_size) * H * W) % 64 == 0 else {}
+        elif target is not None:
+            kw2 = target.kwargs(cout, M)
+        else:
+            kw2 = dict(colstats=True) if GN_EPILOGUE_STATS and want_colstats and (H * W) % 64 == 0 else {}
+        mx2 = (not has_skip or (not RESCONV_MXFP8_KEEP_FOLD and not inplace)) and all(
+            ops.conv3x3_mxfp8_ok(f, H, W, cout, cout, residual=True, ldr=cout, ldc=kw2.get("ldc"), colstats="colstats" in kw2,
+                                 colstats_ld=kw2.get("colstats_ld"), colstats_col=kw2.get("colstats_col", 0)) for f in frames)
+        if not (mx1 or mx2):
+            return None
+        if x2 is not None and not inplace:
+            x, x2 = ops.concat_channels(x.reshape(M, c1), x2.reshape(M, cin - c1)).view(n, H, W, -1), None      # the materialised concat
+        stats_in = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, H * W, cin)
+        xin, x2in = x.view(n, H * W, -1), None if x2 is None else x2.view(n, H * W, -1)
+        a = (ops.group_norm_mxfp8 if mx1 else ops.group_norm)(xin, *pk["g1"], True, stats=stats_in, x2=x2in)
+        emb_out = self._emb_all[:B] if self._emb_all is not None else ops.linear(emb, pk["we"], pk["be"], out_f32=True)
+        if mx1:
+            cs1 = ops.colstats_buffer(M, cout, x.device) if cs1_mx else None
+            h = ops.conv3x3_mxfp8(a, self._mx_weight("w1", self.in_layers[2], x.device), pk["b1"], n=n, H=H, W=W, cin=cin, rowadd=emb_out,
+                                  rowadd_div=fpv * H * W, colstats=cs1)
+        else:
+            cs1 = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and ops.colstats_ok(M, H * W, cin, cout, in_rows=M)) else None
+            h = ops.conv2d(a.view(n, H, W, cin), pk["w1"], pk["b1"], kh=3, kw=3, rowadd=emb_out, rowadd_div=fpv * H * W, colstats=cs1)
+        stats = None if cs1 is None else ops.group_norm_stats_from_colstats(cs1, n, H * W, cout)
+        if mx2:
+            a = ops.group_norm_mxfp8(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
+            residual = ops.conv2d(x, pk["ws"], pk["bs"], kh=1, kw=1).view(M, cout) if has_skip else x.reshape(M, cout)
+            kw2 = dict(kw2)
+            if kw2.get("colstats") is True:
+                kw2["colstats"] = ops.colstats_buffer(M, cout, x.device)
+            cs_out = kw2.get("colstats")
+            h = ops.conv3x3_mxfp8(a, self._mx_weight("w2", self.out_layers[3], x.device), pk["b2"], n=n, H=H, W=W, cin=cout, residual=residual, **kw2)
+        else:
+            a = ops.group_norm(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
+            if fold_skip:
+                w2, b2 = pk["w2s"], pk["b2s"]
+                skip_kw = dict(tail=[x.reshape(M, -1)] + ([] if x2 is None else [x2.reshape(M, -1)]))
+            else:
+                w2, b2 = pk["w2"], pk["b2"]
+                skip_kw = dict(residual=ops.conv2d(x, pk["ws"], pk["bs"], kh=1, kw=1).view(M, cout) if has_skip else x.reshape(M, cout))
+            if temporal:
+                cs_out = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and ops.colstats_ok(M, (n // batch_size) * H * W, cout, cout)) else None
+                kw2 = {} if cs_out is None else dict(colstats=cs_out)
+            elif target is not None:
+                cs_out = target.moments
+            else:
+                cs_out = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and want_colstats and ops.colstats_ok(M, H * W, cout, cout)) else None
+                kw2 = {} if cs_out is None else dict(colstats=cs_out)
+            h = ops.conv2d(a.view(n, H, W, cout), w2, b2, kh=3, kw=3, **skip_kw, **kw2)
+        if temporal:
+            h, cs_out = self.temopral_conv(h.view(batch_size, n // batch_size, H * W, cout), colstats=cs_out, want_colstats=want_colstats, target=target)
+            return h.view(n, H, W, -1), cs_out
+        return h, cs_out
 
     def _pack(self):
         gn1, c1 = self.in_layers[0], self.in_layers[2]
@@ -350,6 +459,10 @@ class ResBlock(PackedModule, TimestepBlock):
         needs no statistics pass); want_colstats: produce the moments of the output for a per-frame GroupNorm behind this block
         (SpatialTransformer.norm, the next block's in_layers); target: write output and moments into a concat buffer.
         -> (h, moments of h or None)"""
+        if RESCONV_MXFP8 and not self.updown and not self.use_scale_shift_norm and self.out_channels not in RESCONV_MXFP8_SKIP_DIMS:
+            routed = self._forward_mx(x, emb, batch_size, want_colstats, colstats, target, x2)
+            if routed is not None:
+                return routed
         n, H, W, cin = x.shape
         pk = self.packed()
         cout = self.out_channels

@@ -434,7 +434,7 @@ def layer_norm(x, gamma, beta, eps=1e-5):
 
 # ------------------------------------------------------------------------------------------
 # MXFP8 operands (include/vcx.h "MXFP8 operands"; opt-in: the GEGLU feed-forward under VCX_FF_MXFP8=1, the TemporalConvBlock convolutions
-# under VCX_TCONV_MXFP8=1)
+# under VCX_TCONV_MXFP8=1, the ResBlock 3x3 convolutions under VCX_RESCONV_MXFP8=1)
 # ------------------------------------------------------------------------------------------
 _u8 = torch.uint8
 
@@ -516,10 +516,14 @@ def linear_mxfp8(a, w, bias, *, K, residual=None, geglu=False, mx_out=False):
     return out
 
 
-def group_norm_mxfp8(x, gamma, beta, eps, silu, groups=32, stats=None):
+def group_norm_mxfp8(x, gamma, beta, eps, silu, groups=32, stats=None, x2=None):
     """quant_mxfp8(group_norm(x, ...).view(rows, C)), byte for byte, in one pass: the normalised fp16 tensor is never written.
-    x [n_outer, pixels, C] fp16 (contiguous, C % 32 == 0); statistics computed here or handed in, as for group_norm.
+    x [n_outer, pixels, C] fp16 (contiguous, C % 32 == 0); statistics computed here or handed in, as for group_norm.  x2
+    [n_outer, pixels, C2]: the norm runs over the channel concat [x | x2] without materialising it (vcx_groupnorm_apply2_mxfp8_f16;
+    `stats` required, as for group_norm).
     -> (element bytes [n_outer * pixels, Kp], scale bytes [n_outer * pixels, Kp / 32])."""
+    if x2 is not None:
+        return _group_norm2_mxfp8(x, x2, gamma, beta, eps, silu, groups, stats)
     n_outer, pixels, C = x.shape
     _dev16(x)
     _dev32(gamma, beta)
@@ -536,6 +540,21 @@ def group_norm_mxfp8(x, gamma, beta, eps, silu, groups=32, stats=None):
     q, sc = _mx_buffers(n_outer * pixels, C, x.device)
     check(L.vcx_groupnorm_apply_mxfp8_f16(x.data_ptr(), q.data_ptr(), sc.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                                           n_outer, pixels, C, groups, eps, 1 if silu else 0, s), "groupnorm_apply_mxfp8")
+    return q, sc
+
+
+def _group_norm2_mxfp8(x1, x2, gamma, beta, eps, silu, groups, stats):
+    n_outer, pixels, c1 = x1.shape
+    C = c1 + x2.shape[2]
+    _dev16(x1, x2)
+    _dev32(gamma, beta, stats)
+    if (stats is None or tuple(x2.shape[:2]) != (n_outer, pixels) or c1 % 8 != 0 or C % 32 != 0 or not x1.is_contiguous()
+            or not x2.is_contiguous()):
+        raise VcxError(f"group_norm_mxfp8 over a split concat needs statistics, contiguous halves, c1 % 8 == 0 and C % 32 == 0 "
+                       f"(x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)})")
+    q, sc = _mx_buffers(n_outer * pixels, C, x1.device)
+    check(lib().vcx_groupnorm_apply2_mxfp8_f16(x1.data_ptr(), c1, x2.data_ptr(), q.data_ptr(), sc.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
+                                               beta.data_ptr(), n_outer, pixels, C, groups, eps, 1 if silu else 0, _stream()), "groupnorm_apply2_mxfp8")
     return q, sc
 
 
@@ -590,6 +609,69 @@ def temporal_conv3_mxfp8(a, w, bias, *, B, T, P, cin, residual=None, ldr=None, o
     check(lib().vcx_conv_t3_mxfp8(a[0].data_ptr(), a[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(), out.data_ptr(), bias.data_ptr(), _ptr(residual), cs_ptr,
                                   B, T, P, cin, cout, ldc, ldr or 0, cld, _t3_flags(residual is not None, colstats is not None), _stream()), "conv_t3_mxfp8")
     return out.view(B, T, P, -1)
+
+
+def _c9_flags(rowadd, residual, colstats):
+    return GEMM_BIAS_N | (GEMM_ROWADD if rowadd else 0) | (GEMM_RESIDUAL if residual else 0) | (GEMM_COLSTATS if colstats else 0)
+
+
+def conv3x3_mxfp8_ok(n, H, W, cin, cout, *, rowadd=False, rowadd_div=0, residual=False, ldc=None, ldr=None, colstats=False, colstats_ld=None,
+                     colstats_col=0):
+    """Does vcx_conv3x3_mxfp8 take a 3x3 / padding-1 convolution of n frames x H x W pixels x cin channels onto cout channels with these
+    keywords (those of conv3x3_mxfp8: `rowadd` / `residual` / `colstats` as booleans, pitches as that call would pass them)?  The
+    library's answer - shape, flags, alignment, 32-bit extents; the reason of a refusal is in vcx_last_error()."""
+    ldc = cout if ldc is None else ldc
+    ldr = (cout if ldr is None else ldr) if residual else 0
+    ldcs = (cout if colstats_ld is None else colstats_ld) if colstats else 0
+    return lib().vcx_conv3x3_mxfp8_ok(n, H, W, cin, cout, ldc, ldr, ldcs, colstats_col if colstats else 0, rowadd_div if rowadd else 0,
+                                      _c9_flags(rowadd, residual, colstats)) == 1
+
+
+def conv3x3_mxfp8(a, w, bias, *, n, H, W, cin, rowadd=None, rowadd_div=0, residual=None, ldr=None, out=None, ldc=None, colstats=None,
+                  colstats_ld=None, colstats_col=0):
+    """3x3 convolution with zero padding 1 on MXFP8 operands: a = (element bytes, scale bytes) of the channels-last activation
+    [n * H * W, cin] (group_norm_mxfp8 / quant_mxfp8), w = the pair packing.pack_conv3x3_mxfp8 made of the Conv2d weight.  Returns fp16
+    [n, H, W, cout] (or [.., ldc] when written into `out`); rowadd / rowadd_div / residual / out / ldc / colstats* as in gemm.  Shapes:
+    conv3x3_mxfp8_ok - a call the kernel does not take is an error here, not a fall-back."""
+    M = n * H * W
+    kp = mx_kp(cin)
+    cout = w[0].shape[0]
+    _dev_mx(a, M, cin, "conv3x3_mxfp8 a")
+    for t, shape in ((w[0], (cout, 9 * kp)), (w[1], (cout, 9 * kp // 32))):
+        if t.dtype is not _u8 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
+            raise VcxError(f"conv3x3_mxfp8 w: expected contiguous GPU uint8 {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    _dev32(bias, rowadd)
+    _dev16(residual, out)
+    if bias is None or bias.numel() != cout or not bias.is_contiguous():
+        raise VcxError(f"conv3x3_mxfp8: a contiguous fp32 bias [N = {cout}] is required")
+    rld = 0
+    if rowadd is not None:
+        if rowadd.dim() != 2 or rowadd.stride(1) != 1 or rowadd.shape[1] != cout or rowadd_div <= 0 or rowadd.shape[0] * rowadd_div < M:
+            raise VcxError(f"conv3x3_mxfp8: rowadd must be [>= M / rowadd_div rows, N = {cout}] fp32 with unit column stride and rowadd_div > 0, "
+                           f"got {tuple(rowadd.shape)}, rowadd_div={rowadd_div}, M={M}")
+        rld = rowadd.stride(0) if rowadd.shape[0] > 1 else cout
+    if residual is not None:
+        if tuple(residual.shape) != (M, cout) or residual.stride(1) != 1:
+            raise VcxError(f"conv3x3_mxfp8: residual must be [{M}, {cout}] with unit column stride, got {tuple(residual.shape)}")
+        ldr = residual.stride(0) if ldr is None else ldr
+    if out is None:
+        out = torch.empty((M, cout), dtype=_f16, device=a[0].device)
+        ldc = cout
+    elif ldc is None:
+        ldc = out.stride(0)
+    if out.numel() < (M - 1) * ldc + cout:
+        raise VcxError(f"conv3x3_mxfp8: out holds {out.numel()} elements, [{M}] rows of pitch {ldc} need {(M - 1) * ldc + cout}")
+    cs_ptr, cld = None, 0
+    if colstats is not None:
+        _dev32(colstats)
+        cld = cout if colstats_ld is None else int(colstats_ld)
+        if colstats.numel() != (M // 64) * cld * 2 or colstats_col < 0 or colstats_col + cout > cld:
+            raise VcxError(f"colstats must hold [M / 64, {cld}, 2] floats (M={M}, N={cout}, first column {colstats_col}), got {tuple(colstats.shape)}")
+        cs_ptr = colstats.data_ptr() + 8 * int(colstats_col)
+    check(lib().vcx_conv3x3_mxfp8(a[0].data_ptr(), a[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(), out.data_ptr(), bias.data_ptr(), _ptr(rowadd),
+                                  _ptr(residual), cs_ptr, n, H, W, cin, cout, ldc, ldr or 0, cld, rld, rowadd_div if rowadd is not None else 0,
+                                  _c9_flags(rowadd is not None, residual is not None, colstats is not None), _stream()), "conv3x3_mxfp8")
+    return out.view(n, H, W, -1)
 
 
 # ------------------------------------------------------------------------------------------

@@ -2,8 +2,8 @@
 
 Reference layouts (binding because checkpoints are loaded with strict=True):
 conv weights [Cout, Cin, kh, kw] / [Cout, Cin, 3, 1, 1] / [Cout, Cin, 1], linear [out, in].
-Kernel layouts: fp16 [N_out][K] with K ordered (tap, cin); GEGLU rows interleaved in blocks of 32; MXFP8 (opt-in feed-forward):
-element bytes [N_out][Kp] + scale bytes [N_out][Kp / 32].
+Kernel layouts: fp16 [N_out][K] with K ordered (tap, cin); GEGLU rows interleaved in blocks of 32; MXFP8 (opt-in feed-forward, temporal
+and ResBlock convolutions): element bytes [N_out][Kp] + scale bytes [N_out][Kp / 32] per tap.
 """
 import torch
 
@@ -117,3 +117,21 @@ def pack_conv_t3_mxfp8(weight):
     taps = weight.detach().reshape(cout, cin, 3).permute(0, 2, 1).to(torch.float16).contiguous()      # [Cout, 3, Cin]
     q, s = pack_mxfp8(taps.view(cout * 3, cin))
     return q.view(cout, -1).contiguous(), s.view(cout, -1).contiguous()
+
+
+def pack_conv3x3_mxfp8(weight):
+    """Conv2d weight [Cout, Cin, 3, 3] (Cin % 32 == 0) -> (element bytes uint8 [Cout, (Kp / 128) * 9 * 128], scale bytes uint8
+    [Cout, (Kp / 128) * 9 * 4]), Kp = Cin rounded up to 128: the weight operand of vcx_conv3x3_mxfp8 (include/vcx.h).  Slab-major, for the
+    reason conv_slab_major gives for the fp16 engine: the 128 columns at K-step 9 s + 3 ky + kx are channels 128 s .. 128 s + 127 of
+    weight[:, :, ky, kx], so the nine tap re-reads of a tile's input rows are consecutive K-steps.  Every tap is quantised and padded on
+    its own with pack_mxfp8's rule (per 32-channel block inside the tap): no MX block and no K-step straddles two taps.  The weight is
+    rounded to fp16 first, as the fp16 route's pack_conv copy is."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] % 32 != 0:
+        raise ValueError(f"pack_conv3x3_mxfp8: need a Conv2d weight [Cout, Cin, 3, 3] with Cin % 32 == 0, got {tuple(weight.shape)}")
+    cout, cin = weight.shape[:2]
+    taps = weight.detach().reshape(cout, cin, 9).permute(0, 2, 1).to(torch.float16).contiguous()      # [Cout, 9, Cin]
+    q, s = pack_mxfp8(taps.view(cout * 9, cin))                                                        # [Cout * 9, Kp], [Cout * 9, Kp / 32]
+    slabs = q.shape[1] // 128
+    q = q.view(cout, 9, slabs, 128).permute(0, 2, 1, 3).reshape(cout, -1).contiguous()
+    s = s.view(cout, 9, slabs, 4).permute(0, 2, 1, 3).reshape(cout, -1).contiguous()
+    return q, s
