@@ -151,7 +151,11 @@ typedef struct vcx_gemm_desc {
      * (fp16 [M][tail_lda*], row-for-row like a linear layer).  A ResBlock's 1x1 skip convolution folded into its second 3x3
      * convolution - `return self.skip_connection(x) + h`, openaimodel3d.py:228-235 - with x in one piece or, on the up path, as the
      * two halves of `torch.cat([h, hs.pop()], dim=1)` (:596) that are then never concatenated.  tail_k* % 64 == 0, DMA kernel only
-     * (cin % 64 == 0, 32-bit extents), fp16 output, no GEGLU.  0 / null: none. */
+     * (cin % 64 == 0, 32-bit extents), fp16 output, no GEGLU.  0 / null: none.
+     * Linear layers (mode 0, round 12) take the same tail: K = main K + tail_k0 + tail_k1, A holds the main K columns only - one GEMM
+     * over the row-aligned sources [A | tail_a0 | tail_a1] without a concatenated copy (two linear layers with nothing between them
+     * folded into one: the transformers' ff.net[2] + proj_out).  Tiled engine only, main K % 64 == 0, plain and COLSTATS epilogues;
+     * with GEGLU / LNFOLD / ROWSTATS / fp32 output, per-unit weights or off the DMA kernel the call is VCX_ROUTE_REFUSED. */
     const void* tail_a0;
     const void* tail_a1;
     int64_t tail_lda0;

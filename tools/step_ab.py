@@ -11,6 +11,8 @@ A variant is  name:key=value,key=value  with keys
     ws       1 | 0   weight-stationary K = 320 kernel (knob GEMM_WS)
     lnrs     1 | 0   LayerNorm statistics from the producing layer's epilogue (VCX_GEMM_ROWSTATS; ops.LN_ROWSTATS)
     upsfold  1 | 0   Upsample convolutions as four 2x2 weight sets on the source grid (ops.UPS_FOLD; 0 = the nine-tap ups = 1 call)
+    ffout    1 | 0   a transformer's ff.net[2] + proj_out as one GEMM with a K tail (attention.FF_OUT_FOLD)
+    ffskip   widths joined by '+' that keep two calls (attention.FF_OUT_FOLD_SKIP_DIMS), e.g. ffskip=1280 or ffskip=640+1280
 e.g.   base:gnfold=0,xattn=2  gnfold:gnfold=1,xattn=2  xattn2:gnfold=0,xattn=1  all:gnfold=1,xattn=1
 --lib runs everything on another build of the library of the SAME ABI (e.g. tools/_abl/libvcx_gelu_select.so, built by
 tools/build_abl.sh): a library-level change is then compared across two invocations on the same box."""
@@ -66,6 +68,8 @@ def main():
         name, _, kv = v.partition(":")
         variants.append((name, dict(item.split("=") for item in kv.split(",") if item)))
 
+    default_ffskip = attention.FF_OUT_FOLD_SKIP_DIMS
+
     def apply(settings):
         attention.GN_FOLD = settings.get("gnfold", "1") != "0"
         attention.GN_FOLD_SPATIAL = {"0": 0, "2": 2}.get(settings.get("gnspatial", "1"), 1)
@@ -79,6 +83,11 @@ def main():
         ops.tune_set("GEMM_WS", int(settings.get("ws", "1")))
         ops.LN_ROWSTATS = settings.get("lnrs", "1") != "0"
         ops.UPS_FOLD = settings.get("upsfold", "1") != "0"
+        attention.FF_OUT_FOLD = settings.get("ffout", "1") != "0"
+        if "ffskip" in settings:
+            attention.FF_OUT_FOLD_SKIP_DIMS = frozenset(int(v) for v in settings["ffskip"].split("+") if v)
+        else:
+            attention.FF_OUT_FOLD_SKIP_DIMS = default_ffskip
 
     def run(settings, steps, profile):
         apply(settings)

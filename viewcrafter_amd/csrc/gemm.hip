@@ -565,13 +565,15 @@ static int validate(const vcx_gemm_desc* d, bool ptrs) {
         VCX_REQUIRE(d->ups != 2 || (d->kh == 2 && d->kw == 2 && d->stride == 1 && d->out_h == 2 * d->in_h && d->out_w == 2 * d->in_w && d->tail_k0 + d->tail_k1 == 0),
                     "vcx_gemm_f16: ups = 2 (folded nearest-2x + 3x3) is four 2x2 weight sets on the source grid: kh = kw = 2, stride 1, out = 2 x in, no K tail");
     }
-    const int tail = conv ? d->tail_k0 + d->tail_k1 : 0;
-    VCX_REQUIRE(conv || (d->tail_k0 == 0 && d->tail_k1 == 0), "vcx_gemm_f16: a K tail (tail_k0 / tail_k1) belongs to a convolution (mode 1)");
+    // linear mode: K = main K + tail_k0 + tail_k1, the main K columns from A (whether a kernel takes the tailed call is gemm_route's answer)
+    VCX_REQUIRE(conv || (d->tail_k0 >= 0 && d->tail_k1 >= 0 && d->tail_k0 + d->tail_k1 < d->K),
+                "vcx_gemm_f16: a linear K tail needs tail_k >= 0 and K > tail_k0 + tail_k1 (K counts the tail; K=%d tail=%d+%d)", d->K, d->tail_k0, d->tail_k1);
+    const int tail = d->tail_k0 + d->tail_k1;
     if (tail) {
         VCX_REQUIRE(d->tail_k0 % 64 == 0 && d->tail_k1 % 64 == 0 && (d->tail_k0 == 0 || ((!ptrs || d->tail_a0) && d->tail_lda0 >= d->tail_k0 && d->tail_lda0 % 8 == 0)) &&
                         (d->tail_k1 == 0 || ((!ptrs || d->tail_a1) && d->tail_lda1 >= d->tail_k1 && d->tail_lda1 % 8 == 0)) && !(d->tail_k0 == 0 && d->tail_k1 != 0),
                     "vcx_gemm_f16: K tail: tail_k %% 64 == 0, sources with tail_lda >= tail_k, tail_lda %% 8 == 0, tail_a0 first (tail=%d+%d)", d->tail_k0, d->tail_k1);
-        VCX_REQUIRE((!ptrs || (((uintptr_t)d->tail_a0 | (uintptr_t)d->tail_a1) & 15) == 0) && !geglu && !f32 && !lnf, "vcx_gemm_f16: K tail: 16-byte aligned sources, fp16 output, no GEGLU / LNFOLD");
+        VCX_REQUIRE((!ptrs || (((uintptr_t)d->tail_a0 | (uintptr_t)d->tail_a1) & 15) == 0) && (!conv || (!geglu && !f32 && !lnf)), "vcx_gemm_f16: K tail: 16-byte aligned sources, fp16 output, no GEGLU / LNFOLD");
     }
     // vector epilogue alignment
     if (!geglu) {
@@ -634,12 +636,12 @@ static GemmRoute gemm_route(const vcx_gemm_desc& d, int unit_rows, const Knobs& 
     const int flags = d.flags;
     const bool conv = d.mode == 1, geglu = flags & VCX_GEMM_GEGLU, f32 = flags & VCX_GEMM_OUT_F32;
     const int lnf = (flags & VCX_GEMM_LNFOLD) ? 1 : (flags & VCX_GEMM_LNFOLD_T) ? 2 : 0;
-    const int k2 = conv ? d.tail_k0 : 0, k3 = conv ? d.tail_k1 : 0;
+    const int k2 = d.tail_k0, k3 = d.tail_k1;
     r.epi = geglu ? (conv ? EPI_GEGLU_ONLY128 : EPI_GEGLU) : ((f32 || lnf == 2) ? EPI_PLAIN_ONLY128 : EPI_PLAIN);
     // DMA kernel (gemm_dma.hip) whenever its addressing assumptions hold; the register-staged kernel otherwise.
     const unsigned long long lim = 0xFFFF0000ull;
     r.a_bytes = conv ? 2ull * (unsigned long long)(d.M / (d.out_h * d.out_w)) * d.in_h * d.in_w * d.lda
-                     : 2ull * ((unsigned long long)(d.M - 1) * d.lda + d.K);
+                     : 2ull * ((unsigned long long)(d.M - 1) * d.lda + (d.K - k2 - k3));      // (a linear K tail is not part of A)
     r.w_bytes = 2ull * ((unsigned long long)(d.N - 1) * d.ldw + d.K);
     // output / residual: 32-bit byte offsets up to 256 rows past the end must not wrap (rows >= M are dropped by the
     // descriptor's range check, which only works if their offset is still >= the extent)
@@ -658,6 +660,7 @@ static GemmRoute gemm_route(const vcx_gemm_desc& d, int unit_rows, const Knobs& 
     // the tiled engine gives the bits of the unit-by-unit loop; units that vcx_gemm_f16 would give to its weight-stationary kernel stay
     // on the loop, so that the bits stay those of the loop whatever that kernel does.  ONE unit is vcx_gemm_f16's call, with ROWSTATS too.
     const int units = unit_rows > 0 ? d.M / unit_rows : 1;
+    if (unit_rows > 0 && (k2 || k3)) return refuse(r, "vcx_gemm_units_f16: no K tail (tail_k0 / tail_k1) with per-unit weights");
     if (units > 1) {
         if (d.K == 320 && d.N == 320 && unit_rows % 32 == 0 && unit_rows >= 1024 && d.M >= 8192 && r.a_bytes < lim && c_ok && units <= 65535 &&
             k.dma != 0 && k.ws != 0 && force_cfg_unset)
@@ -692,6 +695,15 @@ static GemmRoute gemm_route(const vcx_gemm_desc& d, int unit_rows, const Knobs& 
     }
     if ((k2 || k3) && !dma_ok)
         return refuse(r, "vcx_gemm_f16: a K tail needs the DMA kernel (cin %% 64 == 0, K %% 64 == 0, N %% 8 == 0, extents < 4 GiB); cin=%d K=%d N=%d", d.cin, d.K, d.N);
+    // A linear layer with a K tail (round 12: ff.net[2] + proj_out of a transformer as one GEMM): the tiled engine's plain and column-moment
+    // epilogues (bias, residual, ldc > N) only.  K % 64 == 0 (dma_ok) and tail_k % 64 == 0 (validate) make the main K whole K-steps too.
+    // Never a weight-stationary kernel - they walk one source - so the bits of a tailed call are the tiled engine's for every M.
+    if (!conv && (k2 || k3)) {
+        if (geglu || f32 || lnf || (flags & VCX_GEMM_ROWSTATS))
+            return refuse(r, "vcx_gemm_f16: a linear K tail takes the plain and COLSTATS epilogues only: no GEGLU / LNFOLD / ROWSTATS / fp32 output; flags=0x%x", flags);
+        if (k.cfg > 5) return refuse(r, "vcx_gemm_f16: tile configuration %d (knob GEMM_CFG) has no K tail in linear mode", k.cfg);
+        return take(r, VCX_ROUTE_TILED);
+    }
     // Weight-stationary kernel (gemm_ws.hip) for the memory-bound K = 320 linear layers of level 0 (N = 320, 640, 960): the weight stays
     // in the register file, only the activation rows stream.  From 128 tiles of 64 rows on (below that the tiled engine's small
     // configuration is as good).  Not the LayerNorm-folded projections: a lean folded epilogue was built and measured level with the
@@ -736,7 +748,6 @@ static GemmRoute gemm_route(const vcx_gemm_desc& d, int unit_rows, const Knobs& 
 
 // the kernels' argument block of a call (unit_rows = 0: one weight set); a launch of the tile plan then narrows its copy to its rows
 static GemmArgs fill_args(const vcx_gemm_desc& d, const GemmRoute& r, int unit_rows, int64_t w_unit_stride, int64_t bias_unit_stride) {
-    const bool conv = d.mode == 1;
     GemmArgs a;
     a.A = (const half_t*)d.A; a.W = (const half_t*)d.W; a.C = d.C; a.bias = d.bias; a.rowadd = d.rowadd; a.R = (const half_t*)d.residual;
     a.lda = d.lda; a.M = d.M; a.N = d.N; a.K = d.K; a.ldw = d.ldw; a.ldc = d.ldc; a.ldr = d.ldr;
@@ -752,7 +763,7 @@ static GemmArgs fill_args(const vcx_gemm_desc& d, const GemmRoute& r, int unit_r
     a.unit_rows = unit_rows; a.units = unit_rows > 0 ? d.M / unit_rows : 1; a.w_unit_stride = w_unit_stride; a.bias_unit_stride = bias_unit_stride;
     a.rowstats = d.rowstats; a.rowstats_eps = d.rowstats_eps;
     a.A2 = (const half_t*)d.tail_a0; a.A3 = (const half_t*)d.tail_a1; a.lda2 = d.tail_lda0; a.lda3 = d.tail_lda1;
-    a.k2 = conv ? d.tail_k0 : 0; a.k3 = conv ? d.tail_k1 : 0;
+    a.k2 = d.tail_k0; a.k3 = d.tail_k1;
     a.a_bytes = (unsigned)r.a_bytes; a.w_bytes = (unsigned)r.w_bytes; a.c_bytes = (unsigned)r.c_bytes; a.r_bytes = (unsigned)r.r_bytes;
     a.a2_bytes = (unsigned)r.a2_bytes; a.a3_bytes = (unsigned)r.a3_bytes;
     return a;

@@ -36,7 +36,7 @@ struct GemmArgs {
     int64_t w_unit_stride, bias_unit_stride;      // elements between consecutive units' weights / biases
     float* rowstats;          // VCX_GEMM_ROWSTATS (gemm_ws320_pipe_kernel only): (mean, rstd) of every output row
     float rowstats_eps;
-    // K tail of a convolution (gemm_dma_kernel<..., TAIL>): the last (k2 + k3) / 64 K-steps read rows of A2, then A3, linearly
+    // K tail of a convolution or a linear layer (gemm_dma_kernel<..., TAIL>): the last (k2 + k3) / 64 K-steps read rows of A2, then A3, linearly
     const half_t* A2;
     const half_t* A3;
     int64_t lda2, lda3;

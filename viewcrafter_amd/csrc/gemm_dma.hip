@@ -51,9 +51,12 @@ struct TileCfg {
 
 // LNF: 0 = plain epilogue, 1 = VCX_GEMM_LNFOLD, 2 = VCX_GEMM_LNFOLD_T (linear mode only), 3 = VCX_GEMM_COLSTATS (convolutions and, round 4, linear layers);
 // separate instantiations, so the plain kernels keep their register allocation
-// TAIL (round 6, convolutions only): the last (p.k2 + p.k3) / 64 K-steps of a tile read, for output row m, row m of p.A2 and then of p.A3
+// TAIL (round 6): the last (p.k2 + p.k3) / 64 K-steps of a tile read, for output row m, row m of p.A2 and then of p.A3
 // - linear sources - instead of an input pixel: the 1x1 skip convolution of a ResBlock rides in the K loop of its second 3x3
 // convolution (include/vcx.h tail_a0 / tail_a1).  Own instantiations: the kernels without a tail keep their listing.
+// ... and in linear mode (plain and column-moment epilogues): the K-steps before the tail walk p.A as every linear layer does (the K
+// offset in the scalar soffset, no per-lane address work), the tail's read p.A2 / p.A3; the weight side is linear over the whole K.
+// The transformers' ff.net[2] + proj_out pair as one GEMM over [g ; t] (lvdm/modules/attention.py, packing.pack_ff_out_folded).
 // UNITS (round 9, linear mode, fp16 output, bias epilogue only; vcx_gemm_units_f16): one weight / bias set per p.unit_rows consecutive
 // rows.  Row tiles are counted per unit - p.tiles_m = units x ceil(unit_rows / TBM), tile_m = unit x tiles-per-unit + tile inside the
 // unit - so no tile straddles two units and the tiles of a unit are neighbours in the XCD-aware walk (its weight set stays in one L2).
@@ -172,9 +175,9 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_dma_kernel(GemmArgs p, u
         }
         half_t* dx = sX + buf * TBM * BK + wave * 8 * BK;
         half_t* dw = sW + buf * BN * BK + wave * 8 * BK;
-        if (TAIL && CONV && (parts & 1) && kt >= nk_main) {
+        if (TAIL && (parts & 1) && kt >= nk_main) {
             // K tail: row m of a linear source (the descriptor's range check drops rows >= M and anything beyond the source); the K
-            // walker of the gather rests - it is reset by the next tile's init_load
+            // walker of a convolution's gather rests - it is reset by the next tile's init_load
             const bool first = kt - nk_main < nk_a2;
             const __amdgpu_buffer_rsrc_t src = first ? srd_a2 : srd_a3;
             const long long ld2 = (first ? p.lda2 : p.lda3) * 2;
@@ -386,8 +389,10 @@ int dispatch(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_t s, 
         return (a.flags & VCX_GEMM_COLSTATS) ? launch<Cfg, true, false, false, 3, false, false, true>(a, s, grid) : launch<Cfg, true, false, false, 0, false, false, true>(a, s, grid);
     if (a.unit_rows > 0)       // one weight / bias set per unit of rows: linear, fp16 output, BIAS_N at most (checked by vcx_gemm_units_f16)
         return launch<Cfg, false, false, false, 0, false, true>(a, s, grid);
-    if (a.k2 + a.k3 > 0)       // K tail: convolutions with fp16 output, plain or column-moment epilogue (checked by vcx_gemm_f16)
-        return (a.flags & VCX_GEMM_COLSTATS) ? launch<Cfg, true, false, false, 3, true>(a, s, grid) : launch<Cfg, true, false, false, 0, true>(a, s, grid);
+    if (a.k2 + a.k3 > 0) {     // K tail: fp16 output, plain or column-moment epilogue (checked by vcx_gemm_f16)
+        if (conv) return (a.flags & VCX_GEMM_COLSTATS) ? launch<Cfg, true, false, false, 3, true>(a, s, grid) : launch<Cfg, true, false, false, 0, true>(a, s, grid);
+        return (a.flags & VCX_GEMM_COLSTATS) ? launch<Cfg, false, false, false, 3, true>(a, s, grid) : launch<Cfg, false, false, false, 0, true>(a, s, grid);
+    }
     if (a.flags & (VCX_GEMM_LNFOLD | VCX_GEMM_LNFOLD_T)) {      // linear, fp16 output (checked by vcx_gemm_f16)
         if (a.flags & VCX_GEMM_LNFOLD_T) return launch<Cfg, false, false, false, 2>(a, s, grid);
         if (!geglu) return launch<Cfg, false, false, false, 1>(a, s, grid);
@@ -454,7 +459,10 @@ int dispatch_tail(const GemmArgs& a, bool conv, bool geglu, bool f32, hipStream_
             return VCX_EINVAL;
         }
         if (a.unit_rows > 0) return launch_tail<Cfg, false, false, 0, false, true>(a, s, grid);
-        if (a.k2 + a.k3 > 0) return cs ? launch_tail<Cfg, true, false, 3, true>(a, s, grid) : launch_tail<Cfg, true, false, 0, true>(a, s, grid);
+        if (a.k2 + a.k3 > 0) {
+            if (conv) return cs ? launch_tail<Cfg, true, false, 3, true>(a, s, grid) : launch_tail<Cfg, true, false, 0, true>(a, s, grid);
+            return cs ? launch_tail<Cfg, false, false, 3, true>(a, s, grid) : launch_tail<Cfg, false, false, 0, true>(a, s, grid);
+        }
         if (a.flags & VCX_GEMM_LNFOLD) return launch_tail<Cfg, false, false, 1>(a, s, grid);
         if (cs) return conv ? launch_tail<Cfg, true, false, 3>(a, s, grid) : launch_tail<Cfg, false, false, 3>(a, s, grid);
         return conv ? launch_tail<Cfg, true, false>(a, s, grid) : launch_tail<Cfg, false, false>(a, s, grid);

@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from ... import ops
-from ...packing import fold_layernorm, pack_geglu, pack_mxfp8
+from ...packing import fold_layernorm, pack_ff_out_folded, pack_geglu, pack_mxfp8
 from ..common import default
 from .flow import GN_STATS_LEVEL, out_kwargs
 
@@ -51,6 +51,18 @@ FF_MXFP8 = os.environ.get("VCX_FF_MXFP8", "0") == "1"
 # slower in MXFP8 than on the weight-stationary fp16 kernel (1.08 against 0.98 ms at 460800 rows; the pair 1.49 against 1.45 ms), while
 # the 640- and 1280-wide pairs are 1.25x / 1.29x faster (profiles/mxfp8_ff.md).  VCX_FF_MXFP8_SKIP_DIMS="" puts every width on MX.
 FF_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_FF_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+
+# A transformer's last two linear layers - ff.net[2] + block residual, then proj_out + transformer residual - have nothing between them
+# and the token stream between them has no other reader (depth 1; proj_out follows the last block), so they run as ONE GEMM over
+# K = 4D + D: weights [Wout W2 | Wout] combined at pack time (packing.pack_ff_out_folded), the GEGLU output g as the A operand and the
+# token stream t as its K tail (include/vcx.h tail_a0; ops.linear_tail_ok).  The write and re-read of the feed-forward's output, one
+# launch and one fp16 rounding disappear; the result agrees with the two-step form to fp16 rounding, not bit for bit.  On the GPU only
+# (CPU / meta tensors keep the two calls), fp16 feed-forward route only.  VCX_FF_OUT_FOLD=0: two calls everywhere (A/B runs,
+# tools/step_ab.py); VCX_FF_OUT_FOLD_SKIP_DIMS: widths that keep two calls.  1280 by default: isolated at the benchmark's rows the merged call
+# is 13 % / 9 % faster than the pair at D = 320 / 640, but at D = 1280 (K = 6400, compute-bound either way) its 2-5 % lies inside the pair's
+# own round-to-round spread, and the step is level with those twelve transformers folded or not (profiles/ff_out_fold.md).
+FF_OUT_FOLD = os.environ.get("VCX_FF_OUT_FOLD", "1") != "0"
+FF_OUT_FOLD_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_FF_OUT_FOLD_SKIP_DIMS", "1280").split(",") if v.strip())
 
 
 # TemporalTransformer.norm -> proj_in (reference attention.py:331-336,369-372) and SpatialTransformer.norm -> proj_in (:265-269,299):
@@ -302,6 +314,20 @@ class FeedForward(PackedModule):
                 and ops.linear_mxfp8_ok(rows, proj.out_features, self.dim, geglu=True, mx_out=True)
                 and ops.linear_mxfp8_ok(rows, out.out_features, out.in_features, residual=True))
 
+    def on_fp16_route(self, t):
+        return not (FF_MXFP8 and self._mx_ok(t))
+
+    def glu(self, t, ln_params):
+        """x * gelu(gate) of the GEGLU projection of LayerNorm(t), [rows, 4 dim]: the operand of net[2].  The fp16 route (on_fp16_route)."""
+        pk = self.packed()
+        if pk["colsum"] is not None and ops.lnfold_ok(t.shape[0], pk["w1"].shape[0], t.shape[1], lda=t.stride(0)):
+            return ops.linear(t, pk["w1"], pk["b1"], geglu=True, ln_stats=ops.row_stats(t, ln_params[2]), ln_colsum=pk["colsum"])
+        if pk["colsum"] is not None and "w1_plain" not in pk:      # folded pack, shape the folded kernel cannot take
+            proj = self.net[0].proj
+            pk["w1_plain"], pk["b1_plain"] = pack_geglu(_f16(proj.weight), _f32(proj.bias))
+        w1, b1 = (pk["w1"], pk["b1"]) if pk["colsum"] is None else (pk["w1_plain"], pk["b1_plain"])
+        return ops.linear(ops.layer_norm(t, *ln_params), w1, b1, geglu=True)
+
     def run(self, t, ln_params):
         """t + FF(LayerNorm(t)); ln_params = (gamma, beta, eps) of the LayerNorm in front (used when it is not folded into w1)."""
         pk = self.packed()
@@ -314,15 +340,7 @@ class FeedForward(PackedModule):
             a = ops.layer_norm_mxfp8(t, *ln_params)
             g = ops.linear_mxfp8(a, mx["w1"], mx["b1"], K=self.dim, geglu=True, mx_out=True)
             return ops.linear_mxfp8(g, mx["w2"], pk["b2"], K=pk["w2"].shape[1], residual=t)
-        if pk["colsum"] is not None and ops.lnfold_ok(t.shape[0], pk["w1"].shape[0], t.shape[1], lda=t.stride(0)):
-            g = ops.linear(t, pk["w1"], pk["b1"], geglu=True, ln_stats=ops.row_stats(t, ln_params[2]), ln_colsum=pk["colsum"])
-        else:
-            if pk["colsum"] is not None and "w1_plain" not in pk:      # folded pack, shape the folded kernel cannot take
-                proj = self.net[0].proj
-                pk["w1_plain"], pk["b1_plain"] = pack_geglu(_f16(proj.weight), _f32(proj.bias))
-            w1, b1 = (pk["w1"], pk["b1"]) if pk["colsum"] is None else (pk["w1_plain"], pk["b1_plain"])
-            g = ops.linear(ops.layer_norm(t, *ln_params), w1, b1, geglu=True)
-        return ops.linear(g, pk["w2"], pk["b2"], residual=t)
+        return ops.linear(self.glu(t, ln_params), pk["w2"], pk["b2"], residual=t)
 
 
 class BasicTransformerBlock(PackedModule):
@@ -362,6 +380,29 @@ class BasicTransformerBlock(PackedModule):
 
     def ln_params(self):
         return self.packed()
+
+
+def ff_proj_out(tr, t, ln_params, xin, kw, video_rows):
+    """proj_out(t + FF(LayerNorm(t))) + xin behind the last block of transformer `tr` (Spatial / Temporal), kw = out_kwargs' keywords
+    of the proj_out call.  One GEMM over [g ; t] where FF_OUT_FOLD applies (see there), ff.run + proj_out otherwise.  The two forms
+    differ in the last bits, so which one runs must not depend on the batch: the dispatcher is asked about the rows of ONE video and
+    about the call itself (only the 4 GiB extents then depend on the whole call), like ops.rowstats_ok."""
+    pk, ff = tr.packed(), tr.transformer_blocks[-1].ff
+    tokens, D = t.shape
+    C = pk["wout"].shape[0]
+    fold = (FF_OUT_FOLD and t.is_cuda and D not in FF_OUT_FOLD_SKIP_DIMS and ff.net[2].bias is not None and ff.on_fp16_route(t)
+            and all(ops.linear_tail_ok(m, C, ff.net[2].in_features, [D], ldc=kw.get("ldc"), residual=True, colstats="colstats" in kw)
+                    for m in sorted({video_rows, tokens})))
+    if not fold:
+        return ops.linear(ff.run(t, ln_params), pk["wout"], pk["bout"], residual=xin, **kw)
+    if "wcat" not in pk:
+        pk["wcat"], pk["bcat"] = pack_ff_out_folded(ff.net[2].weight, ff.net[2].bias, pk["wout"], pk["bout"])
+    return ops.linear(ff.glu(t, ln_params), pk["wcat"], pk["bcat"], tail=[t], residual=xin, **kw)
+
+
+def _last_ff_params(tr):
+    ff2 = tr.transformer_blocks[-1].ff.net[2]
+    return [ff2.weight] + ([] if ff2.bias is None else [ff2.bias])
 
 
 class ContextKV:
@@ -418,7 +459,12 @@ class SpatialTransformer(PackedModule):
         nn.init.zeros_(self.proj_out.bias)
         self.use_linear = use_linear
 
+    def _foreign_params(self):
+        return _last_ff_params(self)
+
     def _pack(self):
+        """+ wcat / bcat, built on first use by ff_proj_out: [Wout W2 | Wout] and Wout b2 + bout, DERIVED FROM transformer_blocks[-1].ff.net[2]
+        (a child's parameters: _foreign_params rebuilds the pack when they change, _drop_packed discards it with the rest)."""
         win = self.proj_in.weight.detach().reshape(self.proj_in.weight.shape[0], -1)       # ([out, in, 1, 1] of the 1x1-conv form)
         wout = self.proj_out.weight.detach().reshape(self.proj_out.weight.shape[0], -1)
         return dict(gn_w=_f32(self.norm.weight), gn_b=_f32(self.norm.bias), win=_f16(win), win32=_f32(win),
@@ -511,10 +557,11 @@ class SpatialTransformer(PackedModule):
                                kv_rows=80, kv_div=frames_per_video, ldq=D, ldk=D, ldvt=nb * 80, ldo=D, scale=blk.attn2.scale,
                                log2_logits=True)
             t = ops.linear(o2, a2["wo"], a2["bo"], residual=t)
-            # ---- feed-forward
-            t = blk.ff.run(t, ln[2])
+            # ---- feed-forward (the last block's: with proj_out, below)
+            if bi + 1 < len(self.transformer_blocks):
+                t = blk.ff.run(t, ln[2])
         kw, cs_out = out_kwargs(None, want_colstats and N == N_img, tokens, N_img, D, C, x.device)
-        out = ops.linear(t, pk["wout"], pk["bout"], residual=xin, **kw)
+        out = ff_proj_out(self, t, ln[2], xin, kw, video_rows)
         if N != N_img:
             unpadded = torch.empty((n * N_img, C), dtype=torch.float16, device=x.device)
             ops.copy2d(out, unpadded, n, N_img * C, N * C, N_img * C)
@@ -563,7 +610,12 @@ class TemporalTransformer(PackedModule):
             blk.set_kind("temporal")
         self.use_linear = use_linear
 
+    def _foreign_params(self):
+        return _last_ff_params(self)
+
     def _pack(self):
+        """+ wcat / bcat, built on first use by ff_proj_out: [Wout W2 | Wout] and Wout b2 + bout, DERIVED FROM transformer_blocks[-1].ff.net[2]
+        (a child's parameters: _foreign_params rebuilds the pack when they change, _drop_packed discards it with the rest)."""
         win = self.proj_in.weight.detach().reshape(self.proj_in.weight.shape[0], -1)
         wout = self.proj_out.weight.detach().reshape(self.proj_out.weight.shape[0], -1)
         return dict(gn_w=_f32(self.norm.weight), gn_b=_f32(self.norm.bias), win=_f16(win), win32=_f32(win), bin=_f32(self.proj_in.bias),
@@ -621,7 +673,8 @@ class TemporalTransformer(PackedModule):
                 if ai == 0 and _folded(blk.attn2.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, D, ldr=D, video_rows=rows):
                     st = ops.rowstats_buffer(tokens, x.device)
                 t = ops.linear(o, ap["wo"], ap["bo"], residual=t, rowstats=st, rowstats_eps=ln[1][2])
-            t = blk.ff.run(t, ln[2])
+            if blk is not self.transformer_blocks[-1]:      # (the last block's feed-forward: with proj_out, below)
+                t = blk.ff.run(t, ln[2])
         kw, cs_out = out_kwargs(target, want_colstats, tokens, P, D, C, x.device)
-        out = ops.linear(t, pk["wout"], pk["bout"], residual=xin, **kw)
+        out = ff_proj_out(self, t, ln[2], xin, kw, rows)
         return out.view(B, T, P, -1), cs_out

@@ -97,8 +97,10 @@ def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, res
     GroupNorm behind it (VCX_GEMM_COLSTATS); with `colstats_ld` / `colstats_col` the buffer is [M / 64, colstats_ld, 2] and this
     call fills the columns [colstats_col, colstats_col + N) - the moments of a tensor that is one part of a channel concat.
     `rowstats` (fp32 [M, 2], see rowstats_ok) makes the layer write LayerNorm's (mean, rstd) of its output rows (VCX_GEMM_ROWSTATS).
-    `tail` (convolutions): one or two fp16 tensors [M, k_j] whose rows are the last sum(k_j) K columns of the problem - K then counts
-    them (include/vcx.h tail_a0 / tail_a1; see conv_tail_ok)."""
+    `tail`: one or two fp16 tensors [M, k_j] whose rows are the last sum(k_j) K columns of the problem - K then counts them
+    (include/vcx.h tail_a0 / tail_a1).  Behind a convolution's taps (see conv_tail_ok), or - without `conv` - behind the K - sum(k_j)
+    columns of a: one GEMM over the row-aligned sources [a | tail...], bit for bit the linear layer on their concatenation wherever the
+    tiled engine takes that (see linear_tail_ok; linear() counts K itself)."""
     n_out = N // 2 if geglu else N
     _dev16(a, w, residual)
     _dev32(bias, rowadd)
@@ -107,8 +109,8 @@ def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, res
         ldc = n_out
     elif ldc is None:
         ldc = out.stride(0)
-    if tail and (conv is None or len(tail) > 2):
-        raise VcxError("gemm: a K tail belongs to a convolution and has one or two sources")
+    if tail and len(tail) > 2:
+        raise VcxError("gemm: a K tail has one or two sources")
     for j, t in enumerate(tail or ()):
         if t.dim() != 2 or t.shape[0] != M or t.stride(1) != 1:
             raise VcxError(f"gemm: tail source {j} must be [M = {M}, k] with unit column stride, got {tuple(t.shape)}")
@@ -241,9 +243,20 @@ def lnfold_ok(rows, n_out, K, *, lda=None, ldc=None, transposed=False):
 
 
 def linear(x, w, bias=None, **kw):
-    """x [rows, K] (row stride may exceed K) times w [N, K]^T."""
+    """x [rows, K] (row stride may exceed K) times w [N, K]^T.  tail=[t...]: [x | t...] times w [N, K + sum(k_j)]^T (gemm, linear_tail_ok)."""
     rows, K = x.shape
+    K += sum(t.shape[1] for t in kw.get("tail") or ())
     return gemm(x, w, M=rows, N=w.shape[0], K=K, lda=x.stride(0), bias=bias, **kw)
+
+
+def linear_tail_ok(M, N, K, tail_ks, lda=None, ldc=None, residual=False, colstats=False):
+    """Will vcx_gemm_f16 take the linear layer [a | tail...] W^T - K main columns from a, then a K tail of widths tail_ks - with a bias,
+    this residual / column-moment epilogue and these strides (tail sources dense)?  The tiled engine only: the dispatcher's answer
+    (vcx_gemm_route) for the descriptor gemm(..., tail=...) would send."""
+    if not 0 < len(tail_ks) <= 2 or any(k <= 0 for k in tail_ks):
+        return False
+    flags = GEMM_BIAS_N | (GEMM_RESIDUAL if residual else 0) | (GEMM_COLSTATS if colstats else 0)
+    return _takes(M, N, K + sum(tail_ks), K if lda is None else lda, N if ldc is None else ldc, ldr=N if residual else 0, tail=[(k, k) for k in tail_ks], flags=flags)
 
 
 def conv2d(x, w, bias, *, kh, kw, stride=1, pad_h=None, pad_w=None, ups=0, out_hw=None, **kwargs):

@@ -77,6 +77,19 @@ def fold_layernorm(w, gamma, beta, bias=None):
     return wf.contiguous(), colsum.contiguous(), bias_f.contiguous()
 
 
+def pack_ff_out_folded(w2, b2, wout, bout):
+    """A transformer's last two linear layers have nothing between them (lvdm/modules/attention.py: ff.net[2] + block residual, then
+    proj_out):  Wout (W2 g + b2 + t) + bout = [Wout W2 | Wout] [g ; t] + (Wout b2 + bout) - ONE GEMM over K = 4D + D whose last D columns
+    read the token stream t (the K tail of a linear layer, include/vcx.h).  w2 [D, 4D], b2 [D], wout [C, D], bout [C] ->
+    (wcat fp16 [C, 4D + D], bcat fp32 [C]).  The product is formed in fp64 from the fp16-ROUNDED W2 and Wout - the values the two-step
+    form multiplies by - and rounded once; the bias in fp64 from the fp32 biases.  torch ops only: runs on meta tensors."""
+    w2h, wouth = w2.detach().to(torch.float16), wout.detach().to(torch.float16)
+    w2d, woutd = w2h.double(), wouth.double()
+    wcat = torch.cat([(woutd @ w2d).to(torch.float16), wouth], dim=1).contiguous()
+    bcat = (woutd @ b2.detach().float().double() + bout.detach().float().double()).float().contiguous()
+    return wcat, bcat
+
+
 def pack_mxfp8(w):
     """fp16 [rows, K] (K % 32 == 0) -> (element bytes uint8 [rows, Kp], scale bytes uint8 [rows, Kp / 32]), Kp = K rounded up to 128: the
     MXFP8 format of include/vcx.h ("MXFP8 operands") for weights, computed once at pack time with integer arithmetic on the fp16 bit
