@@ -40,8 +40,9 @@ extern "C" {
  * tail_a0 / tail_a1 (K tail of a convolution from linear sources); vcx_groupnorm_apply2_f16.  10: vcx_gemm_route.  11: MXFP8 operands - vcx_quant_mxfp8_f16,
  * vcx_layernorm_mxfp8_f16, vcx_gemm_mxfp8, vcx_gemm_mxfp8_ok; VCX_GEMM_MXFP8_OUT.  12: ups = 2 (nearest-2x + 3x3 convolution folded into
  * four 2x2 weight sets on the tiled engine).  13: MXFP8 temporal convolutions - vcx_groupnorm_apply_mxfp8_f16, vcx_conv_t3_mxfp8,
- * vcx_conv_t3_mxfp8_ok.  14: MXFP8 ResBlock 3x3 convolutions - vcx_conv3x3_mxfp8, vcx_conv3x3_mxfp8_ok, vcx_groupnorm_apply2_mxfp8_f16. */
-#define VCX_ABI_VERSION 14
+ * vcx_conv_t3_mxfp8_ok.  14: MXFP8 ResBlock 3x3 convolutions - vcx_conv3x3_mxfp8, vcx_conv3x3_mxfp8_ok, vcx_groupnorm_apply2_mxfp8_f16.
+ * 15: MXFP8 temporal attention output - vcx_attn_temporal_d64_mxfp8, vcx_attn_temporal_d64_mxfp8_ok. */
+#define VCX_ABI_VERSION 15
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -431,6 +432,21 @@ int vcx_attn_temporal_d64_masked_f16(const void* qkv, void* o, int B, int T, int
 int vcx_attn_temporal_d64_rel_f16(const void* qkv, void* o, const void* relg, void* relp, int R, int B, int T, int64_t P,
                                   int heads, int64_t ld, int k_off, int v_off, int64_t ldo, float scale, int flags,
                                   void* stream);
+/* ABI 15.  quant(vcx_attn_temporal_d64_masked_f16(...) with ldo = D) byte for byte in one pass, D = 64 heads: that kernel's arithmetic up to the
+ * fp16 rounding of every output value, then the MXFP8 format above ("MXFP8 operands") - a head's 64 columns are two blocks of 32, so the wave that
+ * holds a (pixel, head) writes its own element bytes and scale bytes; no fp16 o and no quantiser pass in front of the to_out GEMM.
+ *   q       [(b t p)][Kp(D)] element bytes, Kp(D) = D rounded up to 128; head h at columns 64 h .. 64 h + 63
+ *   scales  [(b t p)][Kp(D) / 32] scale bytes; head h at columns 2 h, 2 h + 1
+ * With an odd head count the last 64 columns are padding: element bytes 0x00, scale bytes 127, written by this call (the buffers need no
+ * initialisation).  T <= 32; flags: VCX_ATTN_CAUSAL only (no relative-position form).  qkv / q 16-byte aligned, scales 4-byte aligned; ld,
+ * k_off, v_off multiples of 8; B T P x Kp(D) below 4 GiB (vcx_gemm_mxfp8 addresses its operand with 32 bits).  A row's bytes depend on that
+ * (b, p)'s inputs alone.  Used by the opt-in route VCX_TATTN_MXFP8=1 of the Python package (default off); accuracy with a real checkpoint and
+ * any multi-GPU number are unmeasured (profiles/mxfp8_tattn.md). */
+int vcx_attn_temporal_d64_mxfp8(const void* qkv, void* q, void* scales, int B, int T, int64_t P, int heads, int64_t ld,
+                                int k_off, int v_off, float scale, int flags, void* stream);
+/* 1 if vcx_attn_temporal_d64_mxfp8 takes the call (the rules above that need no pointer), else 0 with the reason in vcx_last_error(); touches
+ * no device. */
+int vcx_attn_temporal_d64_mxfp8_ok(int B, int T, int64_t P, int heads, int64_t ld, int flags);
 
 /* Row softmax in place on fp16 [rows][ld] over the first n columns (fp32 math): VAE AttnBlock, ae_modules.py:66-69.
  * ld % 8 == 0; when n is not a multiple of 8 the columns up to the next multiple of 8 (ld must cover them) are written as zeros. */

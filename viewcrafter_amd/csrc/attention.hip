@@ -1,6 +1,6 @@
 // Attention kernels for gfx950: flash attention (head dim 64) on MFMA 32x32x16 f16, temporal
 // attention over T <= 32 frames on the VALU, and an in-place row softmax.
-#include "vcx_common.h"
+#include "tattn_mx.h"      // (-> mx_format.h -> vcx_common.h) the MXFP8 store tail of tattn_d64_kernel
 #include "flash2.h"
 #include <stdlib.h>
 
@@ -1038,7 +1038,7 @@ struct TAttnArgs {
     // relg [(b t p)][heads][64] = q . Ek[rel] per query, relp [(b t p)][heads][64] <- the probabilities by clipped distance, R = max distance
     const half_t* relg;
     half_t* relp;
-    int R;
+    int R; vcxmx::TAttnMxOut mx;      // mx: the output of tattn_d64_kernel<.., false, MXQ = true> (tattn_mx.h), in place of o
 };
 
 // One wave per (pixel, head): S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_32x32x16_f16 (T <= 32 keys = one MFMA
@@ -1053,7 +1053,7 @@ struct TAttnArgs {
 // the two extra contractions are plain 64-wide GEMMs of the caller around this kernel: it ADDS the row relg[query][.] (= q Ek^T, one value per
 // clipped distance) to its scores before scale and softmax, and WRITES the probabilities of a query by clipped distance (all keys beyond +-R summed
 // into the end slots) to relp[query][.] - which the caller has zeroed and then multiplies with Ev.  Own instantiations.
-template <bool CAUSAL, bool REL = false>
+template <bool CAUSAL, bool REL = false, bool MXQ = false>
 __global__ void __launch_bounds__(512) tattn_d64_kernel(TAttnArgs p) {
     constexpr int VLD = 72;                                           // LDS row pitch (halfs): 144 B keeps 16-B alignment
     constexpr int WAVES = 8;
@@ -1191,8 +1191,7 @@ __global__ void __launch_bounds__(512) tattn_d64_kernel(TAttnArgs p) {
     // row is split 8 bytes / 8 bytes between lanes l and l + 32.  v_permlane32_swap on the packed words of groups k (vdst) and
     // k + 1 (src) leaves lanes 0-31 with columns 8k .. 8k+7 and lanes 32-63 with 8k+8 .. 8k+15: four 16-byte stores per lane
     // instead of eight 8-byte ones (T21 of the HIP guide; the store tail is issue-bound).
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    typedef unsigned u2v __attribute__((ext_vector_type(2))); typedef unsigned u4v __attribute__((ext_vector_type(4)));
     u2v pk[8];
 #pragma unroll
     for (int db = 0; db < 2; ++db)
@@ -1200,6 +1199,7 @@ __global__ void __launch_bounds__(512) tattn_d64_kernel(TAttnArgs p) {
         for (int gq = 0; gq < 4; ++gq)
             pk[db * 4 + gq] = __builtin_bit_cast(u2v, h4{(half_t)oacc[db][gq * 4 + 0], (half_t)oacc[db][gq * 4 + 1],
                                                         (half_t)oacc[db][gq * 4 + 2], (half_t)oacc[db][gq * 4 + 3]});
+    if constexpr (MXQ) { static_assert(!REL, "no relative-position form"); vcxmx::tattn_mx_store(pk, p.mx, ((int64_t)b * p.T + lq) * p.P + pix, h, p.heads, hi, rvalid); return; }
     half_t* dst = p.o + (((int64_t)b * p.T + lq) * p.P + pix) * p.ldo + h * 64 + hi * 8;
 #pragma unroll
     for (int k = 0; k < 8; k += 2) {
@@ -1618,6 +1618,52 @@ static int tattn_launch(const void* qkv, void* o, const void* relg, void* relp, 
     } else if (flags & VCX_ATTN_CAUSAL) hipLaunchKernelGGL(tattn_d64_kernel<true>, dim3((unsigned)nblk), dim3(512), 0, s, a);
     else hipLaunchKernelGGL(tattn_d64_kernel<false>, dim3((unsigned)nblk), dim3(512), 0, s, a);
     return vcx_check_launch("vcx_attn_temporal_d64_f16");
+}
+
+// vcx_attn_temporal_d64_mxfp8 (ABI 15): the rules that need no pointer; `why` gets the reason of a refusal
+static bool tattn_mx_takes(int B, int T, int64_t P, int heads, int64_t ld, int flags, const char** why) {
+    const char* r = nullptr;
+    if ((flags & ~VCX_ATTN_CAUSAL) != 0) r = "unknown flags (VCX_ATTN_CAUSAL is the only one; no relative-position form)";
+    else if (B <= 0 || P <= 0 || heads <= 0) r = "need B, P, heads > 0";
+    else if (T <= 0 || T > 32) r = "need 0 < T <= 32";
+    else if (ld % 8 != 0) r = "ld must be a multiple of 8";
+    else if ((double)B * (double)P * heads >= 8.0 * 2147483648.0) r = "grid too large (eight (pixel, head) pairs per block, 2^31 blocks)";
+    else if ((double)B * T * (double)P * (double)vcxmx::mx_kp(64 * (int64_t)heads) >= 4294967296.0) r = "B T P x Kp(D) must stay below 4 GiB (the GEMM behind it addresses its operand with 32 bits)";
+    if (why) *why = r;
+    return r == nullptr;
+}
+
+extern "C" int vcx_attn_temporal_d64_mxfp8_ok(int B, int T, int64_t P, int heads, int64_t ld, int flags) {
+    const char* why = nullptr;
+    if (tattn_mx_takes(B, T, P, heads, ld, flags, &why)) return 1;
+    vcx_set_error("vcx_attn_temporal_d64_mxfp8_ok(B=%d, T=%d, P=%lld, heads=%d, ld=%lld, flags=0x%x): %s", B, T, (long long)P, heads, (long long)ld, flags, why);
+    return 0;
+}
+
+extern "C" int vcx_attn_temporal_d64_mxfp8(const void* qkv, void* q, void* scales, int B, int T, int64_t P, int heads, int64_t ld,
+                                           int k_off, int v_off, float scale, int flags, void* stream) {
+    VCX_REQUIRE(qkv && q && scales, "vcx_attn_temporal_d64_mxfp8: null pointer");
+    const char* why = nullptr;
+    VCX_REQUIRE(tattn_mx_takes(B, T, P, heads, ld, flags, &why), "vcx_attn_temporal_d64_mxfp8(B=%d, T=%d, P=%lld, heads=%d, ld=%lld, flags=0x%x): %s", B, T,
+                (long long)P, heads, (long long)ld, flags, why);
+    VCX_REQUIRE(k_off >= 0 && v_off >= 0 && k_off % 8 == 0 && v_off % 8 == 0, "vcx_attn_temporal_d64_mxfp8: k_off / v_off must be non-negative multiples of 8");
+    VCX_REQUIRE((((uintptr_t)qkv | (uintptr_t)q) & 15) == 0 && ((uintptr_t)scales & 3) == 0,
+                "vcx_attn_temporal_d64_mxfp8: qkv and q must be 16-byte aligned, scales 4-byte aligned");
+    TAttnArgs a;
+    a.qkv = (const half_t*)qkv; a.o = nullptr;
+    a.B = B; a.T = T; a.heads = heads; a.P = P; a.ld = ld; a.ldo = 0;
+    a.k_off = k_off; a.v_off = v_off; a.scale = scale;
+    a.npairs = (int64_t)B * P * heads;
+    a.relg = nullptr; a.relp = nullptr; a.R = 0;
+    a.mx.q = (uint8_t*)q; a.mx.s = (uint8_t*)scales; a.mx.ldq = vcxmx::mx_kp(64 * (int64_t)heads);
+    hipStream_t s = (hipStream_t)stream;
+    // q, k, v read as fp16; one byte per output element and one scale byte per 32 of them, the row's padding included
+    VcxProfScope prof(VCX_FAM_TATTN, s, 4.0 * a.npairs * (double)T * T * 64, 2.0 * a.npairs * T * 64 * 3.0 + (double)B * T * P * a.mx.ldq * (1.0 + 1.0 / 32));
+    const int64_t nblk = (a.npairs + 7) / 8;
+    VCX_REQUIRE(nblk < (1ll << 31), "vcx_attn_temporal_d64_mxfp8: grid too large");
+    if (flags & VCX_ATTN_CAUSAL) hipLaunchKernelGGL((tattn_d64_kernel<true, false, true>), dim3((unsigned)nblk), dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((tattn_d64_kernel<false, false, true>), dim3((unsigned)nblk), dim3(512), 0, s, a);
+    return vcx_check_launch("vcx_attn_temporal_d64_mxfp8");
 }
 
 extern "C" int vcx_softmax_rows_f16(void* x, int64_t rows, int n, int64_t ld, void* stream) {

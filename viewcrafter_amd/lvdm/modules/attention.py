@@ -51,6 +51,18 @@ FF_MXFP8 = os.environ.get("VCX_FF_MXFP8", "0") == "1"
 # slower in MXFP8 than on the weight-stationary fp16 kernel (1.08 against 0.98 ms at 460800 rows; the pair 1.49 against 1.45 ms), while
 # the 640- and 1280-wide pairs are 1.25x / 1.29x faster (profiles/mxfp8_ff.md).  VCX_FF_MXFP8_SKIP_DIMS="" puts every width on MX.
 FF_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_FF_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+# Opt-in (VCX_TATTN_MXFP8=1, default off): the two self-attentions of every block of a TemporalTransformer on the MXFP8 matrix pipe -
+# LayerNorm + quantiser in one pass, the q|k|v projection reading those bytes (un-folded weights, a zero bias: the reference has none),
+# the temporal attention kernel writing MXFP8 bytes + scales itself (vcx_attn_temporal_d64_mxfp8: a head's 64 columns are two MX blocks
+# held by one wave, so no quantiser pass), to_out with bias and residual reading them.  T <= 32, no relative position; any refusal keeps
+# the fp16 calls for the whole transformer.  The spatial transformer stays fp16.  Accuracy with a real checkpoint is unmeasured; what was
+# measured is in profiles/mxfp8_tattn.md.  Off: no new launch, no new allocation, every output bit as before.
+TATTN_MXFP8 = os.environ.get("VCX_TATTN_MXFP8", "0") == "1"
+# Widths whose temporal attentions stay on the fp16 route although the switch is on: those whose isolated MX layer is not faster than
+# its fp16 layer by more than the fp16 layer's own spread on the same box.  320 by default: its MX layer is 0.80x of the fp16 one (Kp = 384
+# pads a sixth of K, N = 320 half-fills the third column tile), 640 / 1280 are 1.05x / 1.26x against a spread of 0.5 % (profiles/mxfp8_tattn.md).
+# VCX_TATTN_MXFP8_SKIP_DIMS="" puts every width on MX.
+TATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_TATTN_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
 
 # A transformer's last two linear layers - ff.net[2] + block residual, then proj_out + transformer residual - have nothing between them
 # and the token stream between them has no other reader (depth 1; proj_out follows the last block), so they run as ONE GEMM over
@@ -273,6 +285,17 @@ class CrossAttention(PackedModule):
             wv_rel[:, :ev.shape[0]] = ev.float().t()
             pk["rel_k"], pk["rel_v"], pk["rel_R"] = _f16(wk_rel), _f16(wv_rel), self.relative_position_k.max_relative_position
         return pk
+
+    def mx_packed(self):
+        """TATTN_MXFP8 (temporal self-attention): the MXFP8 pairs of the UN-folded cat(Wq, Wk, Wv) and of to_out's weight, a zero bias [3D]
+        for the projection that has none (vcx_gemm_mxfp8 wants one) and bo.  Built at first use of the route, inside the pack: dropped with it."""
+        pk = self.packed()
+        if "mx" not in pk:
+            with torch.no_grad():
+                wqkv = _f16(torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach(), self.to_v.weight.detach()], 0))
+                pk["mx"] = dict(wqkv=pack_mxfp8(wqkv), zero=torch.zeros(wqkv.shape[0], dtype=torch.float32, device=wqkv.device),
+                                wo=pack_mxfp8(pk["wo"]), bo=pk["bo"])
+        return pk["mx"]
 
     def forward(self, *args, **kwargs):
         raise RuntimeError("CrossAttention is driven by SpatialTransformer/TemporalTransformer in this package")
@@ -621,6 +644,20 @@ class TemporalTransformer(PackedModule):
         return dict(gn_w=_f32(self.norm.weight), gn_b=_f32(self.norm.bias), win=_f16(win), win32=_f32(win), bin=_f32(self.proj_in.bias),
                     wout=_f16(wout), bout=_f32(self.proj_out.bias))
 
+    def _mx_route(self, x, D):
+        """TATTN_MXFP8: do all self-attentions of this call run on the MX route?  Decided once per call, before anything runs: width not
+        skipped, T <= 32, no relative position, dense rows, and the library's three predicates - asked about ONE video (a row's route must
+        not depend on the batch it runs in) and about the call itself (only the 32-bit extents depend on B).  Any refusal keeps the fp16
+        calls for the whole transformer."""
+        B, T, P, _ = x.shape
+        if not TATTN_MXFP8 or D in TATTN_MXFP8_SKIP_DIMS or T > 32 or not x.is_contiguous():
+            return False
+        attns = [a for blk in self.transformer_blocks for a in (blk.attn1, blk.attn2)]
+        if any(a.relative_position or a.to_out[0].bias is None or a.inner_dim != D or a.query_dim != D for a in attns):
+            return False
+        return all(ops.linear_mxfp8_ok(b * T * P, 3 * D, D) and ops.linear_mxfp8_ok(b * T * P, D, D, residual=True)
+                   and ops.temporal_attn_mxfp8_ok(b, T, P, self.n_heads, 3 * D, causal=self.causal_attention) for b in sorted({1, B}))
+
     def forward(self, x, context=None, colstats=None, want_colstats=False, target=None):
         """x [B, T, P, C] fp16 channels-last (P = h*w).  colstats: column moments of x (the per-video norm then needs no statistics
         pass); want_colstats / target: proj_out writes the moments of the result / the result itself into a concat buffer
@@ -629,8 +666,9 @@ class TemporalTransformer(PackedModule):
         pk = self.packed()
         tokens = B * T * P
         xin = x.reshape(tokens, C)
-        stats = None if (colstats is None or GN_STATS_LEVEL < 2) else ops.group_norm_stats_from_colstats(colstats, B, T * P, C)
         D, heads = pk["win"].shape[0], self.n_heads
+        mx = self._mx_route(x, D)
+        stats = None if (colstats is None or GN_STATS_LEVEL < 2) else ops.group_norm_stats_from_colstats(colstats, B, T * P, C)
         rows = T * P
         if GN_FOLD and C % 64 == 0 and 2 * rows * C >= GN_FOLD_MIN_BYTES and 2 * rows * max(C, D) < 0xFFFF0000 and ops.tune_get("GEMM_DMA") != 0:
             # the norm as per-video weights / bias of proj_in; the projection reads the un-normalised rows of each video
@@ -644,7 +682,8 @@ class TemporalTransformer(PackedModule):
         # LayerNorm statistics from the producing layer (VCX_GEMM_ROWSTATS): proj_in for norm1, attn1's output projection for norm2
         blk0 = self.transformer_blocks[0]
         st = None
-        if _folded(blk0.attn1.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, C, lda=C, unit_rows=rows if fold else None, video_rows=rows):
+        # (none on the MX route: the quantising LayerNorm computes its own)
+        if not mx and _folded(blk0.attn1.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, C, lda=C, unit_rows=rows if fold else None, video_rows=rows):
             st = ops.rowstats_buffer(tokens, x.device)
         if fold:
             t = ops.gemm_units(xin, wn, bn, unit_rows=rows, rowstats=st, rowstats_eps=blk0.norm1.eps)
@@ -653,6 +692,14 @@ class TemporalTransformer(PackedModule):
         for blk in self.transformer_blocks:
             ln = blk.ln_params()
             for ai, (attn, lnp) in enumerate(((blk.attn1, ln[0]), (blk.attn2, ln[1]))):
+                if mx:
+                    am = attn.mx_packed()
+                    an = ops.layer_norm_mxfp8(t, *lnp)
+                    qkv = ops.linear_mxfp8(an, am["wqkv"], am["zero"], K=D)           # [tokens, 3D] fp16
+                    o = ops.temporal_attn_mxfp8(qkv, B=B, T=T, P=P, heads=heads, ld=3 * D, k_off=D, v_off=2 * D, scale=attn.scale,
+                                                causal=self.causal_attention)        # MXFP8 pair [tokens, Kp(D)]
+                    t = ops.linear_mxfp8(o, am["wo"], am["bo"], K=D, residual=t)
+                    continue
                 ap = attn.packed()
                 qkv = ln_linear(t, ap["qkv"], lnp, stats=st)                         # [tokens, 3D]
                 o = torch.empty((tokens, D), dtype=torch.float16, device=x.device)

@@ -737,6 +737,22 @@ def temporal_attn(qkv, out, *, B, T, P, heads, ld, k_off, v_off, ldo, scale, cau
     return out
 
 
+def temporal_attn_mxfp8_ok(B, T, P, heads, ld, causal=False):
+    """Does vcx_attn_temporal_d64_mxfp8 take B videos x T frames x P pixels x heads with qkv row pitch ld?  The library's answer."""
+    return lib().vcx_attn_temporal_d64_mxfp8_ok(B, T, P, heads, ld, ATTN_CAUSAL if causal else 0) == 1
+
+
+def temporal_attn_mxfp8(qkv, *, B, T, P, heads, ld, k_off, v_off, scale, causal=False):
+    """quant_mxfp8(temporal_attn(qkv, ...) with ldo = 64 heads), byte for byte, in one pass: the fp16 attention output is never written.
+    Returns (element bytes [B * T * P, Kp(64 heads)], scale bytes [B * T * P, Kp / 32]), the a operand of linear_mxfp8.  T <= 32, no
+    relative position (include/vcx.h)."""
+    _dev16(qkv)
+    q, s = _mx_buffers(B * T * P, 64 * heads, qkv.device)
+    check(lib().vcx_attn_temporal_d64_mxfp8(qkv.data_ptr(), q.data_ptr(), s.data_ptr(), B, T, P, heads, ld, k_off, v_off, scale,
+                                            ATTN_CAUSAL if causal else 0, _stream()), "attn_temporal_d64_mxfp8")
+    return q, s
+
+
 def temporal_attn_rel(qkv, out, relg, relp, *, R, B, T, P, heads, ld, k_off, v_off, ldo, scale, causal=False):
     """Temporal attention with relative position (reference attention.py:104-108, 120-123): relg [tokens, heads, 64] = q Ek^T is added to the
     logits, relp [tokens, heads, 64] (zeroed by the caller) receives the probabilities by clipped distance; see include/vcx.h."""
