@@ -41,8 +41,9 @@ extern "C" {
  * vcx_layernorm_mxfp8_f16, vcx_gemm_mxfp8, vcx_gemm_mxfp8_ok; VCX_GEMM_MXFP8_OUT.  12: ups = 2 (nearest-2x + 3x3 convolution folded into
  * four 2x2 weight sets on the tiled engine).  13: MXFP8 temporal convolutions - vcx_groupnorm_apply_mxfp8_f16, vcx_conv_t3_mxfp8,
  * vcx_conv_t3_mxfp8_ok.  14: MXFP8 ResBlock 3x3 convolutions - vcx_conv3x3_mxfp8, vcx_conv3x3_mxfp8_ok, vcx_groupnorm_apply2_mxfp8_f16.
- * 15: MXFP8 temporal attention output - vcx_attn_temporal_d64_mxfp8, vcx_attn_temporal_d64_mxfp8_ok. */
-#define VCX_ABI_VERSION 15
+ * 15: MXFP8 temporal attention output - vcx_attn_temporal_d64_mxfp8, vcx_attn_temporal_d64_mxfp8_ok.
+ * 16: DPM-Solver++(2M) step - vcx_dpmpp2m_step_f32. */
+#define VCX_ABI_VERSION 16
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -518,6 +519,21 @@ int vcx_ddim_step3_f32(const float* x, const float* v_cond, const float* v_uncon
                        const float* v_img, const float* noise, float* x_prev, float* pred_x0,
                        void* ws, size_t ws_bytes, int B, int64_t n, const float* coef_host,
                        void* stream);
+/* ABI 16.  DPM-Solver++(2M) step (arXiv 2211.01095, data-prediction multistep form) - no reference call site: the reference
+ * has only the DDIM update.  It is the eta = 0 DDIM step of vcx_ddim_step3_f32, formed by the same statements, plus a
+ * history term on the data prediction in true units D = x0 / s (s = the dynamic-rescale factor at this step, 1 without):
+ *   x_prev = [ sqrt(a_prev) (x0 scale_ratio) + sqrt(1 - a_prev) e_t ] + c_h (D - d_last),   d_out = D = x0 (1/s)
+ * with v, e_t, x0 as in the DDIM step (guidance combine, guidance rescale, v / eps parameterisation) and pred_x0 =
+ * x0 scale_ratio, what the DDIM step reports.  coef_host[11] =
+ *   { sqrt_acp_t, sqrt_1m_acp_t, a_prev, 0 (sigma_t: the solver is deterministic, anything else is refused), scale_ratio(prev/t),
+ *     cfg_scale, guidance_rescale, parameterization_is_v, cfg_img, 1/s, c_h }.
+ * c_h is the host's second-order coefficient (utils_diffusion.dpmpp2m_coefficients); c_h == 0 is a first-order step:
+ * d_last is not read and may be NULL, x_prev and pred_x0 equal vcx_ddim_step3_f32's with sigma_t = 0.  d_last == NULL with
+ * c_h != 0 is refused.  d_out is always written; it may be d_last itself (a thread reads its element before it writes it).
+ * v_uncond / v_img may be NULL as for vcx_ddim_step3_f32; ws / ws_bytes follow vcx_ddim_ws_bytes(B, n), checked. */
+int vcx_dpmpp2m_step_f32(const float* x, const float* v_cond, const float* v_uncond, const float* v_img,
+                         const float* d_last, float* x_prev, float* pred_x0, float* d_out, void* ws,
+                         size_t ws_bytes, int B, int64_t n, const float* coef_host, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Lightweight per-kernel-family profiling with HIP events (used by bench.py to fill

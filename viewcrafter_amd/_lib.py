@@ -21,10 +21,10 @@ SYMBOLS = [
     "vcx_attn_temporal_d64_mxfp8", "vcx_attn_temporal_d64_mxfp8_ok", "vcx_softmax_rows_f16",
     "vcx_silu_f32", "vcx_gelu_f16", "vcx_clip_preprocess_f32", "vcx_add_nchw_f32_to_nhwc_f16", "vcx_timestep_embedding_f32", "vcx_cast_f32_to_f16", "vcx_cast_f16_to_f32",
     "vcx_copy2d_f16", "vcx_avgpool2x2_f16", "vcx_upsample2x_f16", "vcx_ncthw_f32_to_nthwc_f16", "vcx_nthwc_to_ncthw_f32", "vcx_ddim_ws_bytes", "vcx_ddim_step_f32", "vcx_ddim_step3_f32",
-    "vcx_profile_begin", "vcx_profile_end", "vcx_tune_set", "vcx_tune_get",
+    "vcx_dpmpp2m_step_f32", "vcx_profile_begin", "vcx_profile_end", "vcx_tune_set", "vcx_tune_get",
 ]
 
-ABI_VERSION = 15         # include/vcx.h VCX_ABI_VERSION
+ABI_VERSION = 16         # include/vcx.h VCX_ABI_VERSION
 # experiment knobs (include/vcx.h VCX_TUNE_*): name -> (index, default)
 TUNE = {"GEMM_CFG": (0, -1), "GEMM_DMA": (1, 1), "FLASH_QB": (2, 0), "XATTN_RESIDENT": (3, 1), "FLASH_IMPL": (4, 0), "EXP0": (5, 0),
         "EXP1": (6, 0), "GEMM_WS": (7, 1)}
@@ -143,6 +143,8 @@ def lib():
                                     c_int64, POINTER(c_float), c_void_p]
     L.vcx_ddim_step3_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t,
                                      c_int, c_int64, POINTER(c_float), c_void_p]
+    L.vcx_dpmpp2m_step_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       ctypes.c_size_t, c_int, c_int64, POINTER(c_float), c_void_p]
     L.vcx_profile_begin.argtypes = [c_int]
     L.vcx_profile_end.argtypes = [POINTER(c_double)]
     L.vcx_tune_set.argtypes = [c_int, c_int]

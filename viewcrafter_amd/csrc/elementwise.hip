@@ -106,9 +106,12 @@ __global__ void __launch_bounds__(256) ddim_reduce_kernel(const float* vc, const
     }
 }
 
-__global__ void __launch_bounds__(256) ddim_update_kernel(const float* x, const float* vc, const float* vu, const float* vi,
-                                                          const float* noise, float* x_prev, float* pred_x0, const double* ws,
-                                                          int64_t n, DdimCoef k, int nparts) {
+// One body, two kernels: DPM = false is the DDIM update (ddim_update_kernel, below), DPM = true the DPM-Solver++(2M) update
+// (dpmpp2m_update_kernel).  Everything DPM adds sits behind `if constexpr`, so the DDIM instantiation is the code it was.
+template <bool DPM>
+__device__ __forceinline__ void ddim_update_body(const float* x, const float* vc, const float* vu, const float* vi, const float* noise,
+                                                 const float* d_last, float* x_prev, float* pred_x0, float* d_out, const double* ws,
+                                                 int64_t n, DdimCoef k, int nparts, float inv_s, float c_h) {
     const int b = blockIdx.y;
     float mix = 1.0f;  // v = v_guided * mix
     if (k.has_uncond && k.rescale > 0.f) {
@@ -138,12 +141,31 @@ __global__ void __launch_bounds__(256) ddim_update_kernel(const float* x, const 
             e_t = v;
             x0 = (xi - k.sqrt_1m_acp * v) / k.sqrt_acp;
         }
+        float d = 0.f;
+        if constexpr (DPM) d = x0 * inv_s;               // D_i: the data prediction in true units, the history of the solver
         x0 *= k.scale_ratio;
         float xp = k.sqrt_a_prev * x0 + k.dir_coef * e_t;
         if (k.has_noise) xp += k.sigma * noise[off + i];
+        if constexpr (DPM) {
+            if (c_h != 0.f) xp += c_h * (d - d_last[off + i]);      // second order: added to the finished first-order value
+            d_out[off + i] = d;
+        }
         pred_x0[off + i] = x0;
         x_prev[off + i] = xp;
     }
+}
+
+__global__ void __launch_bounds__(256) ddim_update_kernel(const float* x, const float* vc, const float* vu, const float* vi,
+                                                          const float* noise, float* x_prev, float* pred_x0, const double* ws,
+                                                          int64_t n, DdimCoef k, int nparts) {
+    ddim_update_body<false>(x, vc, vu, vi, noise, nullptr, x_prev, pred_x0, nullptr, ws, n, k, nparts, 0.f, 0.f);
+}
+
+// DPM-Solver++(2M): the eta = 0 DDIM step plus c_h (D_i - D_{i+1}), D = x0 / s (include/vcx.h vcx_dpmpp2m_step_f32)
+__global__ void __launch_bounds__(256) dpmpp2m_update_kernel(const float* x, const float* vc, const float* vu, const float* vi,
+                                                             const float* d_last, float* x_prev, float* pred_x0, float* d_out,
+                                                             const double* ws, int64_t n, DdimCoef k, int nparts, float inv_s, float c_h) {
+    ddim_update_body<true>(x, vc, vu, vi, nullptr, d_last, x_prev, pred_x0, d_out, ws, n, k, nparts, inv_s, c_h);
 }
 
 inline unsigned grid_for(int64_t n, int cap = 4096) {
@@ -478,4 +500,46 @@ extern "C" int vcx_ddim_step3_f32(const float* x, const float* v_cond, const flo
     hipLaunchKernelGGL(ddim_update_kernel, dim3(gx, B), dim3(256), 0, s, x, v_cond, v_uncond, v_img, noise, x_prev, pred_x0,
                        (const double*)ws, n, k, (int)gx);
     return vcx_check_launch("vcx_ddim_step_f32");
+}
+
+extern "C" int vcx_dpmpp2m_step_f32(const float* x, const float* v_cond, const float* v_uncond, const float* v_img,
+                                    const float* d_last, float* x_prev, float* pred_x0, float* d_out, void* ws, size_t ws_bytes,
+                                    int B, int64_t n, const float* coef_host, void* stream) {
+    VCX_REQUIRE(x && v_cond && x_prev && pred_x0 && d_out && ws && coef_host, "vcx_dpmpp2m_step_f32: null pointer");
+    VCX_REQUIRE(!v_img || v_uncond, "vcx_dpmpp2m_step_f32: v_img needs v_uncond");
+    VCX_REQUIRE(B > 0 && B <= 65535 && n > 1, "vcx_dpmpp2m_step_f32: bad sizes");
+    VCX_REQUIRE(((uintptr_t)ws & 7) == 0, "vcx_dpmpp2m_step_f32: ws must be 8-byte aligned");
+    VCX_REQUIRE(ws_bytes >= vcx_ddim_ws_bytes(B, n), "vcx_dpmpp2m_step_f32: workspace of %zu bytes, vcx_ddim_ws_bytes(%d, %lld) = %zu", ws_bytes,
+                B, (long long)n, vcx_ddim_ws_bytes(B, n));
+    const float inv_s = coef_host[9], c_h = coef_host[10];
+    VCX_REQUIRE(coef_host[3] == 0.f, "vcx_dpmpp2m_step_f32: the solver is deterministic, coef_host[3] (sigma_t) must be 0");
+    VCX_REQUIRE(std::isfinite(inv_s) && std::isfinite(c_h), "vcx_dpmpp2m_step_f32: 1/s and c_h must be finite");
+    VCX_REQUIRE(d_last || c_h == 0.f, "vcx_dpmpp2m_step_f32: d_last is NULL and c_h = %g: a second-order step reads the history", (double)c_h);
+    DdimCoef k;                                             // the DDIM entries, read as vcx_ddim_step3_f32 reads them with sigma_t = 0
+    const float a_prev = coef_host[2];
+    k.sqrt_acp = coef_host[0];
+    k.sqrt_1m_acp = coef_host[1];
+    k.sqrt_a_prev = sqrtf(a_prev);
+    const float dir2 = 1.0f - a_prev;
+    k.dir_coef = sqrtf(dir2 > 0.f ? dir2 : 0.f);
+    k.sigma = 0.f;
+    k.scale_ratio = coef_host[4];
+    k.cfg = coef_host[5];
+    k.rescale = coef_host[6];
+    k.is_v = coef_host[7] != 0.f;
+    k.has_uncond = v_uncond != nullptr;
+    k.has_img = v_img != nullptr;
+    k.cfg_img = coef_host[8];
+    k.has_noise = 0;
+    hipStream_t s = (hipStream_t)stream;
+    VcxProfScope prof(VCX_FAM_ELT, s, 0.0, 4.0 * B * (double)n * 9);
+    const unsigned gx = grid_for(n, 256);
+    if (k.has_uncond && k.rescale > 0.f) {
+        hipLaunchKernelGGL(ddim_reduce_kernel, dim3(gx, B), dim3(256), 0, s, v_cond, v_uncond, v_img, (double*)ws, n, k);
+        int rc = vcx_check_launch("vcx_dpmpp2m_step_f32(reduce)");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(dpmpp2m_update_kernel, dim3(gx, B), dim3(256), 0, s, x, v_cond, v_uncond, v_img, d_last, x_prev, pred_x0, d_out,
+                       (const double*)ws, n, k, (int)gx, inv_s, c_h);
+    return vcx_check_launch("vcx_dpmpp2m_step_f32");
 }

@@ -8,14 +8,37 @@ same arithmetic; what changes is where it runs:
     dicts of tensors, instead of two sequential forwards (ddim.py:223-224);
   * CFG combine + guidance rescale (two per-sample std reductions) + v->eps/x0 + dynamic rescale + the x_{t-1} update
     are one fused launch pair, vcx_ddim_step_f32 (ddim.py:228-279 is ~30 element-wise kernels).
+
+VCX_SAMPLER=dpmpp2m (not in the reference; unset or `ddim` = the loop above, launch for launch): ddim_sampling walks the same
+timesteps with the DPM-Solver++(2M) update - the eta = 0 DDIM step plus a second-order term on the previous step's data prediction,
+one fused launch pair as well (vcx_dpmpp2m_step_f32; coefficients from utils_diffusion.dpmpp2m_coefficients).  The solver is
+deterministic: it needs eta = 0 and draws NO per-step noise, so after sampling the generator is not in the state the DDIM loop
+leaves it in (DDIM draws one Gaussian per step even at eta = 0, like the reference).  p_sample_ddim and decode() stay DDIM.
 """
+import os
+
 import numpy as np
 import torch
 
 from .... import ops
 from ....interleave import step_yield
 from ...common import noise_like
-from ..utils_diffusion import make_ddim_sampling_parameters, make_ddim_timesteps
+from ..utils_diffusion import dpmpp2m_coefficients, make_ddim_sampling_parameters, make_ddim_timesteps
+
+SAMPLERS = ("ddim", "dpmpp2m")
+
+
+def sampler_choice():
+    """VCX_SAMPLER, read when a sample() call starts: `ddim` (also unset / empty) or `dpmpp2m`; anything else is an error."""
+    name = os.environ.get("VCX_SAMPLER", "").strip().lower() or "ddim"
+    if name not in SAMPLERS:
+        raise ValueError(f"VCX_SAMPLER={os.environ['VCX_SAMPLER']!r}: expected one of {', '.join(SAMPLERS)}")
+    return name
+
+
+def _refuse_eta(what):
+    return ValueError(f"VCX_SAMPLER=dpmpp2m is a deterministic solver and cannot run with {what}: pass --ddim_eta 0 (eta=0.0), or unset "
+                      f"VCX_SAMPLER for the DDIM sampler")
 
 
 class DDIMSampler(object):
@@ -79,6 +102,8 @@ class DDIMSampler(object):
             cbs = (first[0] if isinstance(first, (list, tuple)) else first).shape[0]
             if cbs != batch_size:
                 print(f"Warning: Got {cbs} conditionings but batch-size is {batch_size}")
+        if sampler_choice() == "dpmpp2m" and float(eta) != 0.0:
+            raise _refuse_eta(f"eta = {eta} (ddim_eta)")
         self.make_schedule(ddim_num_steps=S, ddim_discretize=timestep_spacing, ddim_eta=eta, verbose=schedule_verbose)
         if len(shape) == 3:
             size = (batch_size, *shape)
@@ -120,6 +145,7 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         clean_cond = kwargs.pop("clean_cond", False)
         self._cfg_cache = None
+        dpm = self._dpmpp2m_plan(mask, x0, kwargs) if sampler_choice() == "dpmpp2m" else None
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -127,10 +153,16 @@ class DDIMSampler(object):
                 assert x0 is not None
                 img_orig = x0 if clean_cond else self.model.q_sample(x0, ts)
                 img = img_orig * mask + (1. - mask) * img
-            img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
-                                              unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
-                                              fs=fs, guidance_rescale=guidance_rescale, noise_source=noise_source, **kwargs)
+            if dpm is not None:
+                img, pred_x0 = self._dpmpp2m_step(dpm, img, cond, ts, index, first=i == 0,
+                                                  unconditional_guidance_scale=unconditional_guidance_scale,
+                                                  unconditional_conditioning=unconditional_conditioning, fs=fs,
+                                                  guidance_rescale=guidance_rescale)
+            else:
+                img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
+                                                  unconditional_guidance_scale=unconditional_guidance_scale,
+                                                  unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
+                                                  fs=fs, guidance_rescale=guidance_rescale, noise_source=noise_source, **kwargs)
             if callback:
                 callback(i)
             if img_callback:
@@ -144,6 +176,54 @@ class DDIMSampler(object):
         if self.guidance_group is not None:      # x was never sent inside the group: check once per video that it did stay bit-equal
             self.guidance_group.check_equal(img, also={"x_T": start_sum})
         return img, intermediates
+
+    # ------------------------------------------------------------------ DPM-Solver++(2M) (VCX_SAMPLER=dpmpp2m)
+    def _dpmpp2m_plan(self, mask, x0, kwargs):
+        """What one ddim_sampling call under the solver needs: per-index (c_h, order) and 1 / s from this sampler's own tables (the
+        multi-condition sampler's scale_arr_prev differs), the keyword arguments of the denoiser, and the history slot.  The history
+        lives in this dict, local to the call - not on self: two clips may interleave on samplers of one class, and the outputs a
+        guidance group exchanges are views that the next exchange overwrites."""
+        h = self._host
+        if np.any(h["sigma"] != 0):
+            raise _refuse_eta("a schedule made with eta != 0 (sigma_t != 0)")
+        if mask is not None or x0 is not None:
+            raise NotImplementedError("VCX_SAMPLER=dpmpp2m: mask / x0 blending is not implemented for the multistep solver")
+        kw = dict(kwargs)
+        if kw.pop("use_original_steps", False):
+            raise NotImplementedError("not on the ViewCrafter path")
+        for named in ("repeat_noise", "uc_type", "conditional_guidance_scale_temporal"):     # named parameters of p_sample_ddim: never the UNet's
+            kw.pop(named, None)
+        rescale = self.model.use_dynamic_rescale
+        scale = self.ddim_scale_arr.numpy() if rescale else None
+        c_h, order = dpmpp2m_coefficients(h["a"], h["a_prev"], scale, self.ddim_scale_arr_prev.numpy() if rescale else None)
+        inv_s = 1.0 / scale.astype(np.float64) if rescale else np.ones(len(c_h))
+        return dict(c_h=c_h, order=order, inv_s=inv_s, kwargs=kw, d=None)
+
+    def _dpmpp2m_step(self, dpm, x, c, t, index, first, unconditional_guidance_scale, unconditional_conditioning, fs, guidance_rescale):
+        """One solver step: the denoiser evaluations of p_sample_ddim, unchanged, then vcx_dpmpp2m_step_f32.  No noise is drawn."""
+        x = x.float().contiguous()
+        v_c, v_u, v_i, cfg_img = self._model_outputs(x, t, c, unconditional_conditioning, unconditional_guidance_scale,
+                                                     dict(dpm["kwargs"], fs=fs))
+        coef = self._step_coef(index, unconditional_guidance_scale, guidance_rescale, guided=v_u is not None, sigma=0.0)
+        second = not first and dpm["order"][index] == 2           # the first step TAKEN has no history, whatever its index
+        # D is written over the history it was computed from (a thread reads its element before it writes it): one buffer per call
+        x_prev, pred_x0, dpm["d"] = ops.dpmpp2m_step(x, v_c.contiguous(), v_u.contiguous() if v_u is not None else None,
+                                                     dpm["d"] if second else None, coef, float(dpm["inv_s"][index]),
+                                                     float(dpm["c_h"][index]) if second else 0.0,
+                                                     v_img=v_i.contiguous() if v_i is not None else None, cfg_img=cfg_img, d_out=dpm["d"])
+        return x_prev, pred_x0
+
+    def _step_coef(self, index, unconditional_guidance_scale, guidance_rescale, guided, sigma):
+        """coef_host[0..8) of the step kernels (include/vcx.h) at DDIM index `index`."""
+        h = self._host
+        step_t = int(self.ddim_timesteps[index])   # == t[i] for all i, by construction of ddim_sampling
+        coef = [float(h["sqrt_acp"][step_t]), float(h["sqrt_1m_acp"][step_t]), float(h["a_prev"][index]), sigma,
+                float(h["ratio"][index]) if self.model.use_dynamic_rescale else 1.0, float(unconditional_guidance_scale),
+                float(guidance_rescale) if guided else 0.0, 1.0 if self.model.parameterization == "v" else 0.0]
+        if self.model.parameterization != "v":
+            # eps-parameterisation reads the DDIM tables instead (ddim.py:259-260)
+            coef[0], coef[1] = float(np.sqrt(h["a"][index])), float(np.sqrt(1. - h["a"][index]))
+        return coef
 
     # ------------------------------------------------------------------ guidance evaluations split over the ranks of a group
     def _split_outputs(self, x, t, conds, kwargs):
@@ -235,16 +315,8 @@ class DDIMSampler(object):
         b, device = x.shape[0], x.device
         x = x.float().contiguous()
         v_c, v_u, v_i, cfg_img = self._model_outputs(x, t, c, unconditional_conditioning, unconditional_guidance_scale, kwargs)
-        guided = v_u is not None
-        h = self._host
-        step_t = int(self.ddim_timesteps[index])   # == t[i] for all i, by construction of ddim_sampling
-        sigma = float(h["sigma"][index])
-        coef = [float(h["sqrt_acp"][step_t]), float(h["sqrt_1m_acp"][step_t]), float(h["a_prev"][index]), sigma,
-                float(h["ratio"][index]) if self.model.use_dynamic_rescale else 1.0, float(unconditional_guidance_scale),
-                float(guidance_rescale) if guided else 0.0, 1.0 if self.model.parameterization == "v" else 0.0]
-        if self.model.parameterization != "v":
-            # eps-parameterisation reads the DDIM tables instead (ddim.py:259-260)
-            coef[0], coef[1] = float(np.sqrt(h["a"][index])), float(np.sqrt(1. - h["a"][index]))
+        sigma = float(self._host["sigma"][index])
+        coef = self._step_coef(index, unconditional_guidance_scale, guidance_rescale, guided=v_u is not None, sigma=sigma)
         # the reference draws the noise unconditionally (ddim.py:275), also when sigma_t = 0 (eta = 0): draw it too, so that a
         # fixed seed leaves the generator in the same state (the x_T of a following sample() call); the kernel skips it
         noise = noise_like(x.shape, device, repeat_noise) if noise_source is None else noise_source(x.shape, device)

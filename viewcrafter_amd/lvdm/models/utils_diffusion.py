@@ -71,6 +71,40 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
     return sigmas, alphas, alphas_prev
 
 
+def dpmpp2m_coefficients(alphas, alphas_prev, scale=None, scale_prev=None):
+    """Per DDIM index i, the second-order coefficient and the order of the DPM-Solver++(2M) step (arXiv 2211.01095; not in the reference).
+
+    The marginal is x_t = (s a) x0 + b eps with a = sqrt(alphas[i]), b = sqrt(1 - alphas[i]) and s = scale[i] (dynamic rescale; None = 1),
+    so the solver's alpha_t is s a, its sigma_t is b and lambda_i = log(s a / b); a_p, b_p, s_p, lambda_prev are the same from
+    alphas_prev[i] / scale_prev[i].  Index S - 1 is the first step taken, index 0 the last.  The step is
+        x_prev = [the eta = 0 DDIM step] + c_h (D_i - D_{i+1}),   D = x0 / s,
+        c_h = (a_p s_p - (b_p / b) a s) / (2 r),   r = (lambda_i - lambda_{i+1}) / (lambda_prev - lambda_i),
+    which is the multistep update (b_p / b) x - s_p a_p expm1(-h) (D_i + (D_i - D_{i+1}) / (2 r)), h = lambda_prev - lambda_i, with its
+    first-order part written as the DDIM step.  A step is first order (c_h = 0, no history read) where it is the first one taken, where
+    lambda_{i+1} is not finite (zero terminal SNR: the first timestep has a = 0, so the step behind it would have r = inf), and at
+    index 0: the last step is the longest in lambda, and a linear extrapolation of D over it costs more than it gains.
+
+    Everything is fp64 from the tables as given (the samplers hold them in fp32); the caller rounds c_h to fp32 once.
+    Returns (c_h, order): an fp64 array and an integer array (1 or 2) of len(alphas)."""
+    al, al_p = np.asarray(alphas, dtype=np.float64), np.asarray(alphas_prev, dtype=np.float64)
+    S = al.shape[0]
+    s = np.ones(S) if scale is None else np.asarray(scale, dtype=np.float64)
+    s_p = np.ones(S) if scale_prev is None else np.asarray(scale_prev, dtype=np.float64)
+    if not (al_p.shape == s.shape == s_p.shape == (S,)):
+        raise ValueError("dpmpp2m_coefficients: the four tables must have one entry per DDIM index")
+    a, b, a_p, b_p = np.sqrt(al), np.sqrt(1.0 - al), np.sqrt(al_p), np.sqrt(1.0 - al_p)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lam, lam_p = np.log(s * a / b), np.log(s_p * a_p / b_p)
+    c_h, order = np.zeros(S), np.ones(S, dtype=np.int64)
+    for i in range(1, S - 1):
+        if not np.isfinite(lam[i + 1]):
+            continue
+        r = (lam[i] - lam[i + 1]) / (lam_p[i] - lam[i])
+        c_h[i] = (a_p[i] * s_p[i] - (b_p[i] / b[i]) * a[i] * s[i]) / (2.0 * r)
+        order[i] = 2
+    return c_h, order
+
+
 def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
     """Reference utils_diffusion.py:147-158.  Kept for API parity (the sampler fuses it into vcx_ddim_step_f32)."""
     dims = list(range(1, noise_pred_text.ndim))

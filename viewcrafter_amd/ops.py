@@ -909,6 +909,29 @@ def ddim_step(x, v_cond, v_uncond, noise, coef, ws=None, v_img=None, cfg_img=0.0
     return x_prev, pred_x0
 
 
+def dpmpp2m_step(x, v_cond, v_uncond, d_last, coef, inv_s, c_h, ws=None, v_img=None, cfg_img=0.0, d_out=None):
+    """One DPM-Solver++(2M) update on fp32 [B, ...] tensors (include/vcx.h vcx_dpmpp2m_step_f32): coef = the 8 host floats of ddim_step
+    with coef[3] (sigma_t) = 0, inv_s = 1 / s of this step, c_h = the second-order coefficient (0: a first-order step, d_last may be None).
+    Returns (x_prev, pred_x0, d) - d = x0 / s is the history the next step passes as d_last; d_out: a buffer to write it into."""
+    _dev32(x, v_cond, v_uncond, v_img, d_last, d_out)
+    B = x.shape[0]
+    n = x.numel() // B
+    for t in (v_cond, v_uncond, v_img, d_last, d_out):
+        if t is not None and (t.numel() != x.numel() or not t.is_contiguous()):
+            raise VcxError(f"dpmpp2m_step: every tensor must be contiguous with x's {x.numel()} elements, got {tuple(t.shape)}")
+    x_prev = torch.empty_like(x)
+    pred_x0 = torch.empty_like(x)
+    if d_out is None:
+        d_out = torch.empty_like(x)
+    if ws is None:
+        ws = torch.empty((lib().vcx_ddim_ws_bytes(B, n) // 8,), dtype=torch.float64, device=x.device)
+    c = (ctypes.c_float * 11)(*([float(v) for v in coef[:8]] + [float(cfg_img), float(inv_s), float(c_h)]))
+    check(lib().vcx_dpmpp2m_step_f32(x.data_ptr(), v_cond.data_ptr(), _ptr(v_uncond), _ptr(v_img), _ptr(d_last), x_prev.data_ptr(),
+                                     pred_x0.data_ptr(), d_out.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), B, n, c,
+                                     _stream()), "dpmpp2m_step")
+    return x_prev, pred_x0, d_out
+
+
 # ------------------------------------------------------------------------------------------
 # experiment knobs (include/vcx.h VCX_TUNE_*): A/B tooling only, the defaults are the product
 # ------------------------------------------------------------------------------------------
