@@ -42,8 +42,9 @@ extern "C" {
  * four 2x2 weight sets on the tiled engine).  13: MXFP8 temporal convolutions - vcx_groupnorm_apply_mxfp8_f16, vcx_conv_t3_mxfp8,
  * vcx_conv_t3_mxfp8_ok.  14: MXFP8 ResBlock 3x3 convolutions - vcx_conv3x3_mxfp8, vcx_conv3x3_mxfp8_ok, vcx_groupnorm_apply2_mxfp8_f16.
  * 15: MXFP8 temporal attention output - vcx_attn_temporal_d64_mxfp8, vcx_attn_temporal_d64_mxfp8_ok.
- * 16: DPM-Solver++(2M) step - vcx_dpmpp2m_step_f32. */
-#define VCX_ABI_VERSION 16
+ * 16: DPM-Solver++(2M) step - vcx_dpmpp2m_step_f32.  17: MXFP8 spatial attention output - vcx_attn_flash_d64_mxfp8,
+ * vcx_attn_flash_dual_d64_mxfp8 and their _ok predicates. */
+#define VCX_ABI_VERSION 17
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -399,6 +400,36 @@ int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const void* vt1, 
                                 int nk1, int kv_rows1, int kv_div1, int64_t ldk1, int64_t ldvt1,
                                 int nk2, int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2,
                                 int64_t ldq, int64_t ldo, float scale, int flags, void* stream);
+
+/* ABI 17.  quant(vcx_attn_flash_d64_f16(...) with ldo = 64 heads) byte for byte in one pass: that entry's kernel choice (the software-pipelined
+ * kernel from 2048 keys, else the phased one with one or two query blocks per wave; knobs VCX_TUNE_FLASH_IMPL / VCX_TUNE_FLASH_QB as there), tile
+ * shape and arithmetic up to the fp16 rounding of every output value, then the MXFP8 format ("MXFP8 operands") - in each of the kernels a lane
+ * pair holds the 64 columns of a (query row, head), two MX blocks, and writes its element and scale bytes itself: no fp16 o and no quantiser
+ * pass in front of the to_out GEMM.
+ *   oq       [n_groups nq][Kp(64 heads)] element bytes, Kp = rounded up to 128; head h at columns 64 h .. 64 h + 63
+ *   oscales  [n_groups nq][Kp / 32] scale bytes; head h at columns 2 h, 2 h + 1
+ * With an odd head count the last 64 columns are padding: element bytes 0x00, scale bytes 127, written by the blocks of the last head (the
+ * buffers need no initialisation).  q / k / vt and their pitches: as vcx_attn_flash_d64_f16.  flags: VCX_ATTN_LOG2_LOGITS is REQUIRED (the
+ * model always sets it; no other instantiation exists), VCX_ATTN_ACCUMULATE is refused.  oq 16-byte aligned, oscales 4-byte aligned;
+ * n_groups nq x Kp below 4 GiB (vcx_gemm_mxfp8 addresses its operand with 32 bits).  A row's bytes depend on its group's inputs alone.
+ * Used by the opt-in route VCX_SATTN_MXFP8=1 of the Python package (default off); accuracy with a real checkpoint and any multi-GPU
+ * number are unmeasured (profiles/mxfp8_sattn.md). */
+int vcx_attn_flash_d64_mxfp8(const void* q, const void* k, const void* vt, void* oq, void* oscales, int n_groups, int heads, int nq, int nk,
+                             int kv_rows, int kv_div, int64_t ldq, int64_t ldk, int64_t ldvt, float scale, int flags, void* stream);
+/* 1 if vcx_attn_flash_d64_mxfp8 takes the call (the rules above that need no pointer), else 0 with the reason in vcx_last_error(); touches
+ * no device. */
+int vcx_attn_flash_d64_mxfp8_ok(int n_groups, int heads, int nq, int nk, int kv_rows, int kv_div, int64_t ldq, int64_t ldk, int64_t ldvt,
+                                int flags);
+/* ABI 17.  quant(vcx_attn_flash_dual_d64_f16(...) with ldo = 64 heads) byte for byte, output as above: the second-form LDS-resident kernel where
+ * that entry picks it, else the dual instantiations of the phased kernel (two query blocks per wave: packed fp16 first result; one: fp32).  The
+ * first-form resident kernel (VCX_TUNE_XATTN_RESIDENT = 2, A/B runs only; or a unit's Q rows beyond 32-bit offsets) has no MX store tail:
+ * arguments that would need it are refused.  flags: VCX_ATTN_LOG2_LOGITS required. */
+int vcx_attn_flash_dual_d64_mxfp8(const void* q, const void* k1, const void* vt1, const void* k2, const void* vt2, void* oq, void* oscales,
+                                  int n_groups, int heads, int nq, int nk1, int kv_rows1, int kv_div1, int64_t ldk1, int64_t ldvt1, int nk2,
+                                  int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2, int64_t ldq, float scale, int flags, void* stream);
+/* 1 if vcx_attn_flash_dual_d64_mxfp8 takes the call (reads the knobs, touches no device), else 0 with the reason in vcx_last_error(). */
+int vcx_attn_flash_dual_d64_mxfp8_ok(int n_groups, int heads, int nq, int nk1, int kv_rows1, int kv_div1, int64_t ldk1, int64_t ldvt1, int nk2,
+                                     int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2, int64_t ldq, int flags);
 
 /* Flash attention with ONE head of dim 512, no mask: O = softmax(scale * Q K^T) V - the AttnBlock of the VAE
  * (lvdm/modules/networks/ae_modules.py:26-78 at 9216 tokens per 576x1024 frame); the score matrix is never materialised.

@@ -15,6 +15,8 @@ A variant is  name:key=value,key=value  with keys
     ffskip   widths joined by '+' that keep two calls (attention.FF_OUT_FOLD_SKIP_DIMS), e.g. ffskip=1280 or ffskip=640+1280
     tattn    0 | 1   temporal attention on the MXFP8 route (attention.TATTN_MXFP8; off by default)
     tattnskip widths joined by '+' that keep fp16 with tattn=1 (attention.TATTN_MXFP8_SKIP_DIMS), e.g. tattnskip=320; tattnskip= for none
+    sattn    0 | 1   spatial attention on the MXFP8 route (attention.SATTN_MXFP8; off by default)
+    sattnskip widths joined by '+' that keep fp16 with sattn=1 (attention.SATTN_MXFP8_SKIP_DIMS), e.g. sattnskip=320; sattnskip= for none
 e.g.   base:gnfold=0,xattn=2  gnfold:gnfold=1,xattn=2  xattn2:gnfold=0,xattn=1  all:gnfold=1,xattn=1
 --lib runs everything on another build of the library of the SAME ABI (e.g. tools/_abl/libvcx_gelu_select.so, built by
 tools/build_abl.sh): a library-level change is then compared across two invocations on the same box."""
@@ -72,6 +74,7 @@ def main():
 
     default_ffskip = attention.FF_OUT_FOLD_SKIP_DIMS
     default_tattn = attention.TATTN_MXFP8, attention.TATTN_MXFP8_SKIP_DIMS
+    default_sattn = attention.SATTN_MXFP8, attention.SATTN_MXFP8_SKIP_DIMS
 
     def apply(settings):
         attention.GN_FOLD = settings.get("gnfold", "1") != "0"
@@ -93,6 +96,8 @@ def main():
             attention.FF_OUT_FOLD_SKIP_DIMS = default_ffskip
         attention.TATTN_MXFP8 = settings["tattn"] != "0" if "tattn" in settings else default_tattn[0]
         attention.TATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in settings["tattnskip"].split("+") if v) if "tattnskip" in settings else default_tattn[1]
+        attention.SATTN_MXFP8 = settings["sattn"] != "0" if "sattn" in settings else default_sattn[0]
+        attention.SATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in settings["sattnskip"].split("+") if v) if "sattnskip" in settings else default_sattn[1]
 
     def run(settings, steps, profile):
         apply(settings)

@@ -1,6 +1,6 @@
 // Attention kernels for gfx950: flash attention (head dim 64) on MFMA 32x32x16 f16, temporal
 // attention over T <= 32 frames on the VALU, and an in-place row softmax.
-#include "tattn_mx.h"      // (-> mx_format.h -> vcx_common.h) the MXFP8 store tail of tattn_d64_kernel
+#include "attn_mx.h"       // (-> mx_format.h -> vcx_common.h) the MXFP8 store tail of the MXQ instantiations
 #include "flash2.h"
 #include <stdlib.h>
 
@@ -29,7 +29,7 @@ struct FlashArgs {
     const half_t* q;
     const half_t* k;
     const half_t* vt;
-    half_t* o;
+    half_t* o; vcxmx::AttnMxOut mx;      // mx: the output of the MXQ instantiations (attn_mx.h), in place of o
     int heads, nq, nk, kv_rows, kv_div;
     int64_t ldq, ldk, ldvt, ldo;
     float scale_log2;
@@ -60,7 +60,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // and over (k2, vt2), each with its own softmax normalisation; the first result stays in registers (fp32 at QB = 1, packed fp16 at
 // QB = 2: include/vcx.h) and the sum is rounded.  Q is read once and O written once - as two launches these layers are overhead (Q read twice,
 // O written, read back and written again at 2.2-2.6 TB/s).
-template <int QB, bool PRE, bool DUAL = false>
+template <int QB, bool PRE, bool DUAL = false, bool MXQ = false>      // MXQ: quant(o) as MXFP8 bytes + scales (attn_mx.h)
 __global__ void __launch_bounds__(256, 2) flash_d64_kernel(FlashArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) half_t sK[2][64 * 64];
@@ -289,8 +289,8 @@ __global__ void __launch_bounds__(256, 2) flash_d64_kernel(FlashArgs p) {
                 }
             continue;
         }
-        if (qvalid[b]) {
-            half_t* orow = p.o + ((int64_t)g * p.nq + q0 + b * 32 + lq) * p.ldo + h * 64;
+        if (MXQ || qvalid[b]) {          // (MXQ: every lane takes part in the store tail's exchanges; the MXQ statements share lines with the fp16 ones because tests/rounding_quality.py pins this file's line numbers)
+            half_t* orow = p.o + ((int64_t)g * p.nq + q0 + b * 32 + lq) * p.ldo + h * 64; typedef unsigned u2v __attribute__((ext_vector_type(2))); u2v pk[8];
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -303,14 +303,14 @@ __global__ void __launch_bounds__(256, 2) flash_d64_kernel(FlashArgs p) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] += QB == 1 ? keep[QB == 1 ? b : 0][db][gq * 4 + r] : (float)keep16[QB == 2 ? b : 0][db][gq * 4 + r];
                     }
-                    if (p.accumulate & VCX_ATTN_ACCUMULATE) {
+                    if (!MXQ && (p.accumulate & VCX_ATTN_ACCUMULATE)) {
                         const h4 old = *reinterpret_cast<const h4*>(orow + d0);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] += (float)old[r];
                     }
-                    *reinterpret_cast<h4*>(orow + d0) = h4{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+                    const h4 o4 = h4{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]}; if constexpr (MXQ) pk[db * 4 + gq] = __builtin_bit_cast(u2v, o4); else *reinterpret_cast<h4*>(orow + d0) = o4;
                 }
-        }
+            if constexpr (MXQ) vcxmx::attn_mx_store(pk, p.mx, (int64_t)g * p.nq + q0 + b * 32 + lq, h, p.heads, hi, qvalid[b]); }
     }
   }
 #endif
@@ -325,7 +325,7 @@ __global__ void __launch_bounds__(256, 2) flash_d64_kernel(FlashArgs p) {
 // =======================================================================================
 struct XAttnArgs {
     const half_t* q;
-    half_t* o;
+    half_t* o; vcxmx::AttnMxOut mx;      // mx: the output of xattn_resident2_d64_kernel<MXQ = true> (attn_mx.h), in place of o
     const half_t* k1;
     const half_t* vt1;
     const half_t* k2;
@@ -558,7 +558,7 @@ __device__ __forceinline__ void row_halves(float x, float& lo, float& hi) {
 }
 
 // (XABL: timing-only ablation bits of this kernel, 0 in the product - vcx_ablate.h)
-__global__ void __launch_bounds__(512, 1) xattn_resident2_d64_kernel(XAttnArgs p, unsigned q_bytes, unsigned o_bytes) {
+template <bool MXQ = false> __global__ void __launch_bounds__(512, 1) xattn_resident2_d64_kernel(XAttnArgs p, unsigned q_bytes, unsigned o_bytes) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int T1 = 2, T2 = 4, NT = T1 + T2;
     constexpr unsigned OOB = 0xFFFFFFFFu;
@@ -804,7 +804,7 @@ __global__ void __launch_bounds__(512, 1) xattn_resident2_d64_kernel(XAttnArgs p
             row_halves(l_run[b], l_lo, l_hi);
             const float inv = 1.0f / (l_lo + l_hi);
             const int64_t qrow = r0 + b * 32 + lq;
-            const unsigned ov = qrow < row_end ? (unsigned)qrow * ldo2 + (unsigned)hi * 16u : OOB;
+            const unsigned ov = qrow < row_end ? (unsigned)qrow * ldo2 + (unsigned)hi * 16u : OOB; u2v pk8[8];      // (pk8: MXQ only)
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
                 const h8 k0 = __builtin_bit_cast(h8, sKeep[64 * (4 * b + 2 * db)]);
@@ -818,12 +818,12 @@ __global__ void __launch_bounds__(512, 1) xattn_resident2_d64_kernel(XAttnArgs p
                         const int i = gq * 4 + r;
                         o4[r] = (half_t)(oacc[b][db][i] * inv + (float)(i < 8 ? k0[i] : k1[i - 8]));
                     }
-                    pk[gq] = __builtin_bit_cast(u2v, o4);
+                    pk[gq] = pk8[4 * db + gq] = __builtin_bit_cast(u2v, o4);
                 }
                 // column group k = 4 db + gq holds columns 8 k + 4 hi .. + 3 of this lane's row: after the half swap lanes 0-31 own
                 // columns 8 k .. 8 k + 7 and lanes 32-63 columns 8 k + 8 .. 8 k + 15 (as tattn_d64_kernel)
 #pragma unroll
-                for (int gq = 0; gq < 4; gq += 2) {
+                for (int gq = 0; gq < (MXQ ? 0 : 4); gq += 2) {
                     const auto s0 = __builtin_amdgcn_permlane32_swap(pk[gq][0], pk[gq + 1][0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane32_swap(pk[gq][1], pk[gq + 1][1], false, false);
                     const u4v w = {s0[0], s1[0], s0[1], s1[1]};
@@ -833,7 +833,7 @@ __global__ void __launch_bounds__(512, 1) xattn_resident2_d64_kernel(XAttnArgs p
                     __builtin_amdgcn_raw_buffer_store_b128(w, srd_o, ov, (db * 32 + gq * 8) * 2, 0);
                     asm volatile("s_nop 1" : : "v"(w));          // (the wide-store rule again)
                 }
-            }
+            } if constexpr (MXQ) vcxmx::attn_mx_store(pk8, p.mx, (int64_t)gb * p.rows_per_unit + qrow, h, p.heads, hi, qrow < row_end);
         }
     }
 #endif
@@ -1038,7 +1038,7 @@ struct TAttnArgs {
     // relg [(b t p)][heads][64] = q . Ek[rel] per query, relp [(b t p)][heads][64] <- the probabilities by clipped distance, R = max distance
     const half_t* relg;
     half_t* relp;
-    int R; vcxmx::TAttnMxOut mx;      // mx: the output of tattn_d64_kernel<.., false, MXQ = true> (tattn_mx.h), in place of o
+    int R; vcxmx::AttnMxOut mx;       // mx: the output of tattn_d64_kernel<.., false, MXQ = true> (attn_mx.h), in place of o
 };
 
 // One wave per (pixel, head): S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_32x32x16_f16 (T <= 32 keys = one MFMA
@@ -1199,7 +1199,7 @@ __global__ void __launch_bounds__(512) tattn_d64_kernel(TAttnArgs p) {
         for (int gq = 0; gq < 4; ++gq)
             pk[db * 4 + gq] = __builtin_bit_cast(u2v, h4{(half_t)oacc[db][gq * 4 + 0], (half_t)oacc[db][gq * 4 + 1],
                                                         (half_t)oacc[db][gq * 4 + 2], (half_t)oacc[db][gq * 4 + 3]});
-    if constexpr (MXQ) { static_assert(!REL, "no relative-position form"); vcxmx::tattn_mx_store(pk, p.mx, ((int64_t)b * p.T + lq) * p.P + pix, h, p.heads, hi, rvalid); return; }
+    if constexpr (MXQ) { static_assert(!REL, "no relative-position form"); vcxmx::attn_mx_store(pk, p.mx, ((int64_t)b * p.T + lq) * p.P + pix, h, p.heads, hi, rvalid); return; }
     half_t* dst = p.o + (((int64_t)b * p.T + lq) * p.P + pix) * p.ldo + h * 64 + hi * 8;
 #pragma unroll
     for (int k = 0; k < 8; k += 2) {
@@ -1393,19 +1393,44 @@ __global__ void __launch_bounds__(256) softmax_rows_kernel(half_t* x, int n, int
 
 }  // namespace
 
-extern "C" int vcx_attn_flash_d64_f16(const void* q, const void* k, const void* vt, void* o, int n_groups, int heads,
-                                      int nq, int nk, int kv_rows, int kv_div, int64_t ldq, int64_t ldk, int64_t ldvt,
-                                      int64_t ldo, float scale, int flags, void* stream) {
-    VCX_REQUIRE(q && k && vt && o, "vcx_attn_flash_d64_f16: null pointer");
-    VCX_REQUIRE(n_groups > 0 && heads > 0 && nq > 0 && nk > 0 && kv_div > 0, "vcx_attn_flash_d64_f16: empty problem");
-    VCX_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && kv_rows % 8 == 0 && kv_rows >= nk,
-                "vcx_attn_flash_d64_f16: strides must be multiples of 8 and kv_rows >= nk (ldq=%lld ldk=%lld ldvt=%lld kv_rows=%d nk=%d)",
-                (long long)ldq, (long long)ldk, (long long)ldvt, kv_rows, nk);
-    VCX_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) & 15) == 0 && ((uintptr_t)o & 7) == 0,
-                "vcx_attn_flash_d64_f16: pointers must be 16-byte aligned");
-    VCX_REQUIRE((int64_t)n_groups * heads * ((nq + 127) / 128) < (1ll << 30), "vcx_attn_flash_d64_f16: too many workgroups");
+// vcx_attn_flash_d64_mxfp8 / vcx_attn_flash_dual_d64_mxfp8 (ABI 17): what the MXQ store tail adds to the rules of the fp16 entries - base-2
+// logits (the only instantiations), no accumulate, and an output the GEMM behind it can address with 32 bits
+static const char* attn_mx_refusal(int n_groups, int heads, int nq, int flags) {
+    if ((flags & ~(VCX_ATTN_LOG2_LOGITS | VCX_ATTN_ACCUMULATE)) != 0) return "unknown flags";
+    if (flags & VCX_ATTN_ACCUMULATE) return "VCX_ATTN_ACCUMULATE is refused (the output is not read back)";
+    if (!(flags & VCX_ATTN_LOG2_LOGITS)) return "VCX_ATTN_LOG2_LOGITS is required (only the base-2 instantiations exist)";
+    if (n_groups <= 0 || heads <= 0 || nq <= 0) return "empty problem";
+    if ((double)n_groups * nq * (double)vcxmx::mx_kp(64 * (int64_t)heads) >= 4294967296.0)
+        return "n_groups nq x Kp(64 heads) must stay below 4 GiB (the GEMM behind it addresses its operand with 32 bits)";
+    return nullptr;
+}
+
+// the rules of vcx_attn_flash_d64_f16 that need no pointer (mx: of vcx_attn_flash_d64_mxfp8, ldo = 64 heads)
+static const char* flash_refusal(bool mx, int n_groups, int heads, int nq, int nk, int kv_rows, int kv_div, int64_t ldq, int64_t ldk, int64_t ldvt,
+                                 int64_t ldo, int flags) {
+    if (!(n_groups > 0 && heads > 0 && nq > 0 && nk > 0 && kv_div > 0)) return "empty problem";
+    if (!(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && kv_rows % 8 == 0 && kv_rows >= nk))
+        return "strides must be multiples of 8 and kv_rows >= nk";
+    if (!((int64_t)n_groups * heads * ((nq + 127) / 128) < (1ll << 30))) return "too many workgroups";
+    if (!(((int64_t)(nk - 1) * ldk + 64) * 2 < 0xFFFF0000ll && (63ll * ldvt + nk + 8) * 2 < 0xFFFF0000ll))
+        return "K / V^T extents per (group, head) must stay below 4 GiB";
+    return mx ? attn_mx_refusal(n_groups, heads, nq, flags) : nullptr;
+}
+
+// One dispatch for vcx_attn_flash_d64_f16 (mx == nullptr) and vcx_attn_flash_d64_mxfp8: the same kernel, tile shape and knobs for the same
+// arguments; the MX entry launches the MXQ instantiation of whatever the fp16 entry would.
+static int flash_d64_run(const char* who, const void* q, const void* k, const void* vt, void* o, const vcxmx::AttnMxOut* mx, int n_groups, int heads,
+                         int nq, int nk, int kv_rows, int kv_div, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, float scale, int flags,
+                         void* stream) {
+    VCX_REQUIRE(q && k && vt && (mx ? mx->q && mx->s : o != nullptr), "%s: null pointer", who);
+    const char* why = flash_refusal(mx != nullptr, n_groups, heads, nq, nk, kv_rows, kv_div, ldq, ldk, ldvt, ldo, flags);
+    VCX_REQUIRE(!why, "%s: %s (n_groups=%d heads=%d nq=%d nk=%d kv_rows=%d ldq=%lld ldk=%lld ldvt=%lld flags=0x%x)", who, why, n_groups, heads, nq, nk,
+                kv_rows, (long long)ldq, (long long)ldk, (long long)ldvt, flags);
+    VCX_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) & 15) == 0 && (mx ? (((uintptr_t)mx->q & 15) | ((uintptr_t)mx->s & 3)) == 0 : ((uintptr_t)o & 7) == 0),
+                "%s: pointers must be 16-byte aligned (scale bytes: 4)", who);
     FlashArgs a;
     a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.o = (half_t*)o;
+    a.mx = mx ? *mx : vcxmx::AttnMxOut{nullptr, nullptr, 0};
     a.heads = heads; a.nq = nq; a.nk = nk; a.kv_rows = kv_rows; a.kv_div = kv_div;
     a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
     a.scale_log2 = scale * 1.4426950408889634f;
@@ -1414,9 +1439,7 @@ extern "C" int vcx_attn_flash_d64_f16(const void* q, const void* k, const void* 
     const bool pre = flags & VCX_ATTN_LOG2_LOGITS;
     hipStream_t s = (hipStream_t)stream;
     const double nprob = (double)n_groups * heads;
-    VcxProfScope prof(VCX_FAM_FLASH, s, 4.0 * nprob * nq * (double)nk * 64, 2.0 * nprob * 64 * (2.0 * nq + 2.0 * nk));
-    VCX_REQUIRE(((int64_t)(nk - 1) * ldk + 64) * 2 < 0xFFFF0000ll && (63ll * ldvt + nk + 8) * 2 < 0xFFFF0000ll,
-                "vcx_attn_flash_d64_f16: K / V^T extents per (group, head) must stay below 4 GiB");
+    VcxProfScope prof(VCX_FAM_FLASH, s, 4.0 * nprob * nq * (double)nk * 64, 2.0 * nprob * 64 * ((mx ? 1.0 + 33.0 / 64 : 2.0) * nq + 2.0 * nk));
     // Long key sequences with base-2 logits and whole 64-key tiles: the software-pipelined kernel (attention_v2.hip: MFMA and
     // softmax overlapped inside one wave per SIMD).  One block per CU and a prologue that is not hidden behind another block:
     // it pays from ~2000 keys up (same-box A/Bs: round 3, profiles/r03_flash_v2.md: +4.5 % at 9216 keys, level at 2304 / 1152, -18 % at 576;
@@ -1426,6 +1449,7 @@ extern "C" int vcx_attn_flash_d64_f16(const void* q, const void* k, const void* 
     if (impl != 1 && pre && !(flags & VCX_ATTN_ACCUMULATE) && nk % 64 == 0 && (impl == 2 || nk >= 2048)) {
         Flash2Args f;
         f.q = (const half_t*)q; f.k = (const half_t*)k; f.vt = (const half_t*)vt; f.o = (half_t*)o;
+        f.mx = a.mx;
         f.heads = heads; f.nq = nq; f.nk = nk; f.kv_rows = kv_rows; f.kv_div = kv_div;
         f.ldq = ldq; f.ldk = ldk; f.ldvt = ldvt; f.ldo = ldo;
         f.nqb = (nq + 255) / 256;
@@ -1443,36 +1467,86 @@ extern "C" int vcx_attn_flash_d64_f16(const void* q, const void* k, const void* 
     if (qb2) {
         a.nqb = blocks2;
         dim3 grid(blocks2 * prob_pad);
-        if (pre) hipLaunchKernelGGL((flash_d64_kernel<2, true>), grid, dim3(256), 0, s, a);
+        if (mx) hipLaunchKernelGGL((flash_d64_kernel<2, true, false, true>), grid, dim3(256), 0, s, a);
+        else if (pre) hipLaunchKernelGGL((flash_d64_kernel<2, true>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((flash_d64_kernel<2, false>), grid, dim3(256), 0, s, a);
     } else {
         a.nqb = (nq + 127) / 128;
         dim3 grid(a.nqb * prob_pad);
-        if (pre) hipLaunchKernelGGL((flash_d64_kernel<1, true>), grid, dim3(256), 0, s, a);
+        if (mx) hipLaunchKernelGGL((flash_d64_kernel<1, true, false, true>), grid, dim3(256), 0, s, a);
+        else if (pre) hipLaunchKernelGGL((flash_d64_kernel<1, true>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((flash_d64_kernel<1, false>), grid, dim3(256), 0, s, a);
     }
-    return vcx_check_launch("vcx_attn_flash_d64_f16");
+    return vcx_check_launch(who);
 }
 
-extern "C" int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const void* vt1, const void* k2, const void* vt2, void* o,
-                                           int n_groups, int heads, int nq, int nk1, int kv_rows1, int kv_div1, int64_t ldk1,
-                                           int64_t ldvt1, int nk2, int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2,
-                                           int64_t ldq, int64_t ldo, float scale, int flags, void* stream) {
-    VCX_REQUIRE(q && k1 && vt1 && k2 && vt2 && o, "vcx_attn_flash_dual_d64_f16: null pointer");
-    VCX_REQUIRE(n_groups > 0 && heads > 0 && nq > 0 && nk1 > 0 && nk2 > 0 && kv_div1 > 0 && kv_div2 > 0,
-                "vcx_attn_flash_dual_d64_f16: empty problem");
-    VCX_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0 && ldk1 % 8 == 0 && ldvt1 % 8 == 0 && ldk2 % 8 == 0 && ldvt2 % 8 == 0 &&
-                kv_rows1 % 8 == 0 && kv_rows1 >= nk1 && kv_rows2 % 8 == 0 && kv_rows2 >= nk2,
-                "vcx_attn_flash_dual_d64_f16: strides must be multiples of 8 and kv_rows >= nk");
-    VCX_REQUIRE((((uintptr_t)q | (uintptr_t)k1 | (uintptr_t)vt1 | (uintptr_t)k2 | (uintptr_t)vt2) & 15) == 0 && ((uintptr_t)o & 7) == 0,
-                "vcx_attn_flash_dual_d64_f16: pointers must be 16-byte aligned");
-    VCX_REQUIRE(!(flags & VCX_ATTN_ACCUMULATE), "vcx_attn_flash_dual_d64_f16: VCX_ATTN_ACCUMULATE is not supported here");
-    VCX_REQUIRE((int64_t)n_groups * heads * ((nq + 127) / 128) < (1ll << 30), "vcx_attn_flash_dual_d64_f16: too many workgroups");
-    VCX_REQUIRE(((int64_t)(nk1 - 1) * ldk1 + 64) * 2 < 0xFFFF0000ll && (63ll * ldvt1 + nk1 + 8) * 2 < 0xFFFF0000ll &&
-                ((int64_t)(nk2 - 1) * ldk2 + 64) * 2 < 0xFFFF0000ll && (63ll * ldvt2 + nk2 + 8) * 2 < 0xFFFF0000ll,
-                "vcx_attn_flash_dual_d64_f16: K / V^T extents per (group, head) must stay below 4 GiB");
+extern "C" int vcx_attn_flash_d64_f16(const void* q, const void* k, const void* vt, void* o, int n_groups, int heads,
+                                      int nq, int nk, int kv_rows, int kv_div, int64_t ldq, int64_t ldk, int64_t ldvt,
+                                      int64_t ldo, float scale, int flags, void* stream) {
+    return flash_d64_run("vcx_attn_flash_d64_f16", q, k, vt, o, nullptr, n_groups, heads, nq, nk, kv_rows, kv_div, ldq, ldk, ldvt, ldo, scale, flags, stream);
+}
+
+extern "C" int vcx_attn_flash_d64_mxfp8_ok(int n_groups, int heads, int nq, int nk, int kv_rows, int kv_div, int64_t ldq, int64_t ldk, int64_t ldvt,
+                                           int flags) {
+    const char* why = flash_refusal(true, n_groups, heads, nq, nk, kv_rows, kv_div, ldq, ldk, ldvt, 64 * (int64_t)heads, flags);
+    if (!why) return 1;
+    vcx_set_error("vcx_attn_flash_d64_mxfp8_ok(n_groups=%d, heads=%d, nq=%d, nk=%d, kv_rows=%d, kv_div=%d, ldq=%lld, ldk=%lld, ldvt=%lld, flags=0x%x): %s",
+                  n_groups, heads, nq, nk, kv_rows, kv_div, (long long)ldq, (long long)ldk, (long long)ldvt, flags, why);
+    return 0;
+}
+
+extern "C" int vcx_attn_flash_d64_mxfp8(const void* q, const void* k, const void* vt, void* oq, void* oscales, int n_groups, int heads, int nq, int nk,
+                                        int kv_rows, int kv_div, int64_t ldq, int64_t ldk, int64_t ldvt, float scale, int flags, void* stream) {
+    const vcxmx::AttnMxOut mx{(uint8_t*)oq, (uint8_t*)oscales, vcxmx::mx_kp(64 * (int64_t)(heads > 0 ? heads : 1))};
+    return flash_d64_run("vcx_attn_flash_d64_mxfp8", q, k, vt, nullptr, &mx, n_groups, heads, nq, nk, kv_rows, kv_div, ldq, ldk, ldvt, 64 * (int64_t)heads,
+                         scale, flags, stream);
+}
+
+// which kernel vcx_attn_flash_dual_d64_f16 / _mxfp8 runs: the LDS-resident forms where both key sets are shared by the same frame groups and fit
+enum { DUAL_FLASH = 0, DUAL_RESIDENT = 1, DUAL_RESIDENT2 = 2 };
+static int dual_kernel_choice(int n_groups, int nq, int nk1, int kv_div1, int nk2, int kv_div2, int64_t ldq, int64_t ldo, bool o_aligned16) {
+    const bool resident_on = vcx_tune(VCX_TUNE_XATTN_RESIDENT) != 0;
+    if (!(resident_on && kv_div1 == kv_div2 && n_groups % kv_div1 == 0 && nk1 <= 128 && nk2 <= 256)) return DUAL_FLASH;
+    // second form (half tiles, prefetched fragments and query rows, first result parked in the other 64 KB of LDS): needs 32-bit
+    // byte offsets inside a unit's Q / O rows and 16-byte output stores; knob XATTN_RESIDENT = 2 keeps the first form (A/B runs)
+    const int64_t rows_per_unit = (int64_t)kv_div1 * nq;
+    const int64_t q_ext = ((rows_per_unit - 1) * ldq + 64) * 2, o_ext = ((rows_per_unit - 1) * ldo + 64) * 2;
+    if (vcx_tune(VCX_TUNE_XATTN_RESIDENT) != 2 && q_ext < 0xFFFF0000ll && o_ext < 0xFFFF0000ll && ldo % 8 == 0 && o_aligned16) return DUAL_RESIDENT2;
+    return DUAL_RESIDENT;
+}
+
+static const char* dual_refusal(bool mx, int n_groups, int heads, int nq, int nk1, int kv_rows1, int kv_div1, int64_t ldk1, int64_t ldvt1, int nk2,
+                                int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2, int64_t ldq, int64_t ldo, int flags) {
+    if (!(n_groups > 0 && heads > 0 && nq > 0 && nk1 > 0 && nk2 > 0 && kv_div1 > 0 && kv_div2 > 0)) return "empty problem";
+    if (!(ldq % 8 == 0 && ldo % 4 == 0 && ldk1 % 8 == 0 && ldvt1 % 8 == 0 && ldk2 % 8 == 0 && ldvt2 % 8 == 0 && kv_rows1 % 8 == 0 && kv_rows1 >= nk1 &&
+          kv_rows2 % 8 == 0 && kv_rows2 >= nk2))
+        return "strides must be multiples of 8 and kv_rows >= nk";
+    if (flags & VCX_ATTN_ACCUMULATE) return "VCX_ATTN_ACCUMULATE is not supported here";
+    if (!((int64_t)n_groups * heads * ((nq + 127) / 128) < (1ll << 30))) return "too many workgroups";
+    if (!(((int64_t)(nk1 - 1) * ldk1 + 64) * 2 < 0xFFFF0000ll && (63ll * ldvt1 + nk1 + 8) * 2 < 0xFFFF0000ll &&
+          ((int64_t)(nk2 - 1) * ldk2 + 64) * 2 < 0xFFFF0000ll && (63ll * ldvt2 + nk2 + 8) * 2 < 0xFFFF0000ll))
+        return "K / V^T extents per (group, head) must stay below 4 GiB";
+    if (!mx) return nullptr;
+    if (const char* why = attn_mx_refusal(n_groups, heads, nq, flags)) return why;
+    if (dual_kernel_choice(n_groups, nq, nk1, kv_div1, nk2, kv_div2, ldq, ldo, true) == DUAL_RESIDENT)
+        return "these arguments select the first-form resident kernel (VCX_TUNE_XATTN_RESIDENT = 2 or a unit's rows beyond 32-bit offsets), which has no MX store tail";
+    return nullptr;
+}
+
+// One dispatch for vcx_attn_flash_dual_d64_f16 (mx == nullptr) and vcx_attn_flash_dual_d64_mxfp8, as flash_d64_run
+static int flash_dual_d64_run(const char* who, const void* q, const void* k1, const void* vt1, const void* k2, const void* vt2, void* o,
+                              const vcxmx::AttnMxOut* mx, int n_groups, int heads, int nq, int nk1, int kv_rows1, int kv_div1, int64_t ldk1,
+                              int64_t ldvt1, int nk2, int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2, int64_t ldq, int64_t ldo, float scale,
+                              int flags, void* stream) {
+    VCX_REQUIRE(q && k1 && vt1 && k2 && vt2 && (mx ? mx->q && mx->s : o != nullptr), "%s: null pointer", who);
+    const char* why = dual_refusal(mx != nullptr, n_groups, heads, nq, nk1, kv_rows1, kv_div1, ldk1, ldvt1, nk2, kv_rows2, kv_div2, ldk2, ldvt2, ldq, ldo, flags);
+    VCX_REQUIRE(!why, "%s: %s (n_groups=%d heads=%d nq=%d nk1=%d nk2=%d flags=0x%x)", who, why, n_groups, heads, nq, nk1, nk2, flags);
+    VCX_REQUIRE((((uintptr_t)q | (uintptr_t)k1 | (uintptr_t)vt1 | (uintptr_t)k2 | (uintptr_t)vt2) & 15) == 0 &&
+                (mx ? (((uintptr_t)mx->q & 15) | ((uintptr_t)mx->s & 3)) == 0 : ((uintptr_t)o & 7) == 0),
+                "%s: pointers must be 16-byte aligned (scale bytes: 4)", who);
     FlashArgs a;
     a.q = (const half_t*)q; a.o = (half_t*)o;
+    a.mx = mx ? *mx : vcxmx::AttnMxOut{nullptr, nullptr, 0};
     a.k = (const half_t*)k1; a.vt = (const half_t*)vt1; a.nk = nk1; a.kv_rows = kv_rows1; a.kv_div = kv_div1; a.ldk = ldk1; a.ldvt = ldvt1;
     a.k2 = (const half_t*)k2; a.vt2 = (const half_t*)vt2; a.nk2 = nk2; a.kv_rows2 = kv_rows2; a.kv_div2 = kv_div2; a.ldk2 = ldk2; a.ldvt2 = ldvt2;
     a.heads = heads; a.nq = nq; a.ldq = ldq; a.ldo = ldo;
@@ -1481,12 +1555,12 @@ extern "C" int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const 
     a.nprob = n_groups * heads;
     hipStream_t s = (hipStream_t)stream;
     const double nprob = (double)n_groups * heads;
-    VcxProfScope prof(VCX_FAM_FLASH, s, 4.0 * nprob * nq * (double)(nk1 + nk2) * 64, 2.0 * nprob * 64 * (2.0 * nq + 2.0 * (nk1 + nk2)));
+    VcxProfScope prof(VCX_FAM_FLASH, s, 4.0 * nprob * nq * (double)(nk1 + nk2) * 64, 2.0 * nprob * 64 * ((mx ? 1.0 + 33.0 / 64 : 2.0) * nq + 2.0 * (nk1 + nk2)));
     // Both key sets shared by the same frame groups and small enough for LDS: the resident-K/V kernel (no per-tile pipeline)
-    const bool resident_on = vcx_tune(VCX_TUNE_XATTN_RESIDENT) != 0;
-    if (resident_on && kv_div1 == kv_div2 && n_groups % kv_div1 == 0 && nk1 <= 128 && nk2 <= 256) {
+    const int choice = dual_kernel_choice(n_groups, nq, nk1, kv_div1, nk2, kv_div2, ldq, ldo, mx || ((uintptr_t)o & 15) == 0);
+    if (choice != DUAL_FLASH) {
         XAttnArgs x;
-        x.q = (const half_t*)q; x.o = (half_t*)o;
+        x.q = (const half_t*)q; x.o = (half_t*)o; x.mx = a.mx;
         x.k1 = (const half_t*)k1; x.vt1 = (const half_t*)vt1; x.k2 = (const half_t*)k2; x.vt2 = (const half_t*)vt2;
         x.heads = heads; x.nk1 = nk1; x.nk2 = nk2; x.kv_rows1 = kv_rows1; x.kv_rows2 = kv_rows2;
         x.ldq = ldq; x.ldo = ldo; x.ldk1 = ldk1; x.ldvt1 = ldvt1; x.ldk2 = ldk2; x.ldvt2 = ldvt2;
@@ -1507,17 +1581,21 @@ extern "C" int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const 
         x.rows_per_block = ((iters + split - 1) / split) * 512;
         x.split = (int)((x.rows_per_unit + x.rows_per_block - 1) / x.rows_per_block);
         constexpr int XSMEM = 6 * 64 * 64 * 2 * 2;
-        // second form (half tiles, prefetched fragments and query rows, first result parked in the other 64 KB of LDS): needs 32-bit
-        // byte offsets inside a unit's Q / O rows and 16-byte output stores; knob XATTN_RESIDENT = 2 keeps the first form (A/B runs)
-        const int64_t q_ext = ((x.rows_per_unit - 1) * ldq + 64) * 2, o_ext = ((x.rows_per_unit - 1) * ldo + 64) * 2;
-        if (vcx_tune(VCX_TUNE_XATTN_RESIDENT) != 2 && q_ext < 0xFFFF0000ll && o_ext < 0xFFFF0000ll && ldo % 8 == 0 && ((uintptr_t)o & 15) == 0) {
+        if (choice == DUAL_RESIDENT2) {
+            const int64_t q_ext = ((x.rows_per_unit - 1) * ldq + 64) * 2, o_ext = ((x.rows_per_unit - 1) * ldo + 64) * 2;
             constexpr int XSMEM2 = XSMEM + 8 * 8192;
+            if (mx) {
+                static VcxLdsAttr lds2mx;
+                if (!lds2mx.ensure(reinterpret_cast<const void*>(xattn_resident2_d64_kernel<true>), XSMEM2, "vcx_attn_flash_dual_d64_mxfp8(resident2)")) return VCX_ELAUNCH;
+                hipLaunchKernelGGL(xattn_resident2_d64_kernel<true>, dim3(x.nunits * x.split), dim3(512), XSMEM2, s, x, (unsigned)q_ext, (unsigned)o_ext);
+                return vcx_check_launch("vcx_attn_flash_dual_d64_mxfp8(resident2)");
+            }
             static VcxLdsAttr lds2;
-            if (!lds2.ensure(reinterpret_cast<const void*>(xattn_resident2_d64_kernel), XSMEM2, "vcx_attn_flash_dual_d64_f16(resident2)")) return VCX_ELAUNCH;
-            hipLaunchKernelGGL(xattn_resident2_d64_kernel, dim3(x.nunits * x.split), dim3(512), XSMEM2, s, x, (unsigned)q_ext, (unsigned)o_ext);
+            if (!lds2.ensure(reinterpret_cast<const void*>(xattn_resident2_d64_kernel<false>), XSMEM2, "vcx_attn_flash_dual_d64_f16(resident2)")) return VCX_ELAUNCH;
+            hipLaunchKernelGGL(xattn_resident2_d64_kernel<false>, dim3(x.nunits * x.split), dim3(512), XSMEM2, s, x, (unsigned)q_ext, (unsigned)o_ext);
             return vcx_check_launch("vcx_attn_flash_dual_d64_f16(resident2)");
         }
-        static VcxLdsAttr lds;
+        static VcxLdsAttr lds;      // (never with mx: dual_refusal)
         if (!lds.ensure(reinterpret_cast<const void*>(xattn_resident_d64_kernel), XSMEM, "vcx_attn_flash_dual_d64_f16")) return VCX_ELAUNCH;
         hipLaunchKernelGGL(xattn_resident_d64_kernel, dim3(x.nunits * x.split), dim3(512), XSMEM, s, x);
         return vcx_check_launch("vcx_attn_flash_dual_d64_f16(resident)");
@@ -1534,13 +1612,41 @@ extern "C" int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const 
     dim3 grid(a.nqb * ((a.nprob + 7) / 8 * 8));
     if (qb2) {
         if (pre) a.scale_log2 = 1.0f;       // the plain kernel multiplies the scores by scale_log2: base-2 logits need 1
-        hipLaunchKernelGGL((flash_d64_kernel<2, false, true>), grid, dim3(256), 0, s, a);
+        if (mx) hipLaunchKernelGGL((flash_d64_kernel<2, false, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((flash_d64_kernel<2, false, true>), grid, dim3(256), 0, s, a);
     } else if (pre) {
-        hipLaunchKernelGGL((flash_d64_kernel<1, true, true>), grid, dim3(256), 0, s, a);
+        if (mx) hipLaunchKernelGGL((flash_d64_kernel<1, true, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((flash_d64_kernel<1, true, true>), grid, dim3(256), 0, s, a);
     } else {
         hipLaunchKernelGGL((flash_d64_kernel<1, false, true>), grid, dim3(256), 0, s, a);
     }
-    return vcx_check_launch("vcx_attn_flash_dual_d64_f16");
+    return vcx_check_launch(who);
+}
+
+extern "C" int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const void* vt1, const void* k2, const void* vt2, void* o,
+                                           int n_groups, int heads, int nq, int nk1, int kv_rows1, int kv_div1, int64_t ldk1,
+                                           int64_t ldvt1, int nk2, int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2,
+                                           int64_t ldq, int64_t ldo, float scale, int flags, void* stream) {
+    return flash_dual_d64_run("vcx_attn_flash_dual_d64_f16", q, k1, vt1, k2, vt2, o, nullptr, n_groups, heads, nq, nk1, kv_rows1, kv_div1, ldk1, ldvt1, nk2,
+                              kv_rows2, kv_div2, ldk2, ldvt2, ldq, ldo, scale, flags, stream);
+}
+
+extern "C" int vcx_attn_flash_dual_d64_mxfp8_ok(int n_groups, int heads, int nq, int nk1, int kv_rows1, int kv_div1, int64_t ldk1, int64_t ldvt1, int nk2,
+                                                int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2, int64_t ldq, int flags) {
+    const char* why = dual_refusal(true, n_groups, heads, nq, nk1, kv_rows1, kv_div1, ldk1, ldvt1, nk2, kv_rows2, kv_div2, ldk2, ldvt2, ldq,
+                                   64 * (int64_t)heads, flags);
+    if (!why) return 1;
+    vcx_set_error("vcx_attn_flash_dual_d64_mxfp8_ok(n_groups=%d, heads=%d, nq=%d, nk1=%d, kv_rows1=%d, kv_div1=%d, nk2=%d, kv_rows2=%d, kv_div2=%d, ldq=%lld, "
+                  "flags=0x%x): %s", n_groups, heads, nq, nk1, kv_rows1, kv_div1, nk2, kv_rows2, kv_div2, (long long)ldq, flags, why);
+    return 0;
+}
+
+extern "C" int vcx_attn_flash_dual_d64_mxfp8(const void* q, const void* k1, const void* vt1, const void* k2, const void* vt2, void* oq, void* oscales,
+                                             int n_groups, int heads, int nq, int nk1, int kv_rows1, int kv_div1, int64_t ldk1, int64_t ldvt1, int nk2,
+                                             int kv_rows2, int kv_div2, int64_t ldk2, int64_t ldvt2, int64_t ldq, float scale, int flags, void* stream) {
+    const vcxmx::AttnMxOut mx{(uint8_t*)oq, (uint8_t*)oscales, vcxmx::mx_kp(64 * (int64_t)(heads > 0 ? heads : 1))};
+    return flash_dual_d64_run("vcx_attn_flash_dual_d64_mxfp8", q, k1, vt1, k2, vt2, nullptr, &mx, n_groups, heads, nq, nk1, kv_rows1, kv_div1, ldk1, ldvt1,
+                              nk2, kv_rows2, kv_div2, ldk2, ldvt2, ldq, 64 * (int64_t)heads, scale, flags, stream);
 }
 
 extern "C" int vcx_attn_flash_d512_f16(const void* q, const void* k, const void* vt, void* o, int n_groups, int nq, int nk, int kv_rows, int64_t ldq,

@@ -270,7 +270,7 @@ FI float row_max_across_halves(float m) {
 // ABL: timing-only ablation bits (knob EXP0; 0 in production, anything else computes garbage): 1 no vmcnt wait at the barrier,
 // 2 no barrier, 4 no exp2, 8 no softmax stream at all, 16 no fragment reads in the loop, 32 no DMA in the loop, 64 no MFMAs
 // SUMV: row sums by v_add_f32 in the softmax stream (1) or by 8 extra MFMAs per tile (0)
-template <int ABL, int SUMV, int VAR>
+template <int ABL, int SUMV, int VAR, bool MXQ = false>      // MXQ: quant(o) as MXFP8 bytes + scales (attn_mx.h), appended last
 __global__ void __launch_bounds__(256, 1) flash2_d64_kernel(Flash2Args p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // four distinct objects: slot s of K / V^T (see the header: compile-time slots keep the DMA waits exact)
@@ -550,17 +550,17 @@ __global__ void __launch_bounds__(256, 1) flash2_d64_kernel(Flash2Args p) {
         f16v o[2];
         acc_read_o<2 * b>(o[0]);
         acc_read_o<2 * b + 1>(o[1]);
-        if (qvalid[b]) {
-            half_t* orow = p.o + ((int64_t)g * p.nq + q0 + b * 32 + lq) * p.ldo + h * 64;
+        if (MXQ || qvalid[b]) {          // (MXQ: every lane takes part in the store tail's exchanges; the MXQ statements share lines with the fp16 ones because tests/rounding_quality.py pins this file's line numbers)
+            half_t* orow = p.o + ((int64_t)g * p.nq + q0 + b * 32 + lq) * p.ldo + h * 64; typedef u32 u2v __attribute__((ext_vector_type(2))); u2v pk[8];
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) {
                     const int d0 = db * 32 + 8 * gq + 4 * hi;
-                    *reinterpret_cast<h4*>(orow + d0) = h4{(half_t)(o[db][gq * 4 + 0] * inv), (half_t)(o[db][gq * 4 + 1] * inv),
-                                                           (half_t)(o[db][gq * 4 + 2] * inv), (half_t)(o[db][gq * 4 + 3] * inv)};
+                    const h4 o4 = h4{(half_t)(o[db][gq * 4 + 0] * inv), (half_t)(o[db][gq * 4 + 1] * inv),
+                                     (half_t)(o[db][gq * 4 + 2] * inv), (half_t)(o[db][gq * 4 + 3] * inv)}; if constexpr (MXQ) pk[db * 4 + gq] = __builtin_bit_cast(u2v, o4); else *reinterpret_cast<h4*>(orow + d0) = o4;
                 }
-        }
+            if constexpr (MXQ) vcxmx::attn_mx_store(pk, p.mx, (int64_t)g * p.nq + q0 + b * 32 + lq, h, p.heads, hi, qvalid[b]); }
     });
 #endif
 }
@@ -571,14 +571,19 @@ int vcx_flash2_launch(const Flash2Args& a, hipStream_t s) {
     const int prob_pad = (a.nprob + 7) / 8 * 8;
     const dim3 grid((unsigned)(a.nqb * prob_pad));
 #define F2_LAUNCH(A, SV) hipLaunchKernelGGL((flash2_d64_kernel<A, SV, F2_VAR_DEFAULT>), grid, dim3(256), 0, s, a)
+    // vcx_attn_flash_d64_mxfp8 (a.mx.q set): the product kernel with the quantising store tail; no ablation form.  Instantiated BEHIND the fp16
+    // kernel, so that the fp16 kernel stays the first match of the build audit's name prefixes (tools/isa_audit.py KERNELS).
+#define F2_LAUNCH_MX hipLaunchKernelGGL((flash2_d64_kernel<0, F2_SUMV_DEFAULT, F2_VAR_DEFAULT, true>), grid, dim3(256), 0, s, a)
 #define F2_LAUNCHV(A, SV, V) hipLaunchKernelGGL((flash2_d64_kernel<A, SV, V>), grid, dim3(256), 0, s, a)
 #ifndef VCX_FLASH2_ABLATIONS
     // the product: one kernel, no knob read - the scratch knobs EXP0 / EXP1 ("free for one-off experiments", vcx.h) must not be
     // able to turn every 9216-key self-attention into VCX_EINVAL because some unrelated experiment set them
-    F2_LAUNCH(0, F2_SUMV_DEFAULT);
+    if (!a.mx.q) F2_LAUNCH(0, F2_SUMV_DEFAULT);
+    else F2_LAUNCH_MX;
 #else
     const int abl = vcx_tune(VCX_TUNE_EXP0), sumv = vcx_tune(VCX_TUNE_EXP1);      // timing-only ablations / A-B (tools/flash_ab.py); 0, 0 = the product
-    if (abl == 0 && sumv == 0) F2_LAUNCH(0, F2_SUMV_DEFAULT);
+    if (abl == 0 && sumv == 0 && !a.mx.q) F2_LAUNCH(0, F2_SUMV_DEFAULT);
+    else if (a.mx.q) F2_LAUNCH_MX;
     else if (abl == 0 && sumv == 1) F2_LAUNCH(0, 1);
     else if (abl == 0 && sumv == 2) F2_LAUNCH(0, 0);
     else if (abl == 0 && sumv >= 10 && sumv <= 13) {       // A/B of the stream variants: EXP1 = 10 + VAR
@@ -604,5 +609,6 @@ int vcx_flash2_launch(const Flash2Args& a, hipStream_t s) {
 #endif
 #undef F2_LAUNCH
 #undef F2_LAUNCHV
-    return vcx_check_launch("vcx_attn_flash_d64_f16(v2)");
+#undef F2_LAUNCH_MX
+    return vcx_check_launch(a.mx.q ? "vcx_attn_flash_d64_mxfp8(v2)" : "vcx_attn_flash_d64_f16(v2)");
 }

@@ -1,24 +1,27 @@
-// MXFP8 store tail of the temporal attention kernel (attention.hip tattn_d64_kernel<CAUSAL, false, MXQ = true>; include/vcx.h
-// vcx_attn_temporal_d64_mxfp8, ABI 15): the output values, each rounded to fp16 as the fp16 kernel stores it, leave as MXFP8 element bytes
-// + block scales (mx_format.h) for the to_out GEMM.  One wave holds a (pixel, head): a head's 64 columns are two MX blocks, so the wave
-// quantises its own rows - half the bytes written and no quantiser pass.  quant(the fp16 kernel's o with ldo = D) byte for byte, the K
-// padding of a row included.  Everything up to the packed fp16 words `pk` is the fp16 kernel's code.
+// MXFP8 store tail of the attention kernels whose output feeds a to_out GEMM on the block-scaled matrix pipe: tattn_d64_kernel<CAUSAL, false,
+// MXQ = true> (vcx_attn_temporal_d64_mxfp8, ABI 15) and the MXQ instantiations of flash_d64_kernel, xattn_resident2_d64_kernel (attention.hip)
+// and flash2_d64_kernel (attention_v2.hip) behind vcx_attn_flash_d64_mxfp8 / vcx_attn_flash_dual_d64_mxfp8 (ABI 17).  The output values, each
+// rounded to fp16 as the fp16 kernel stores it, leave as MXFP8 element bytes + block scales (mx_format.h).  In all four kernels a lane pair
+// (l, l ^ 32) holds the 64 columns of one (row, head) - two MX blocks - so the wave quantises its own rows: half the bytes written and no
+// quantiser pass.  quant(the fp16 kernel's o with ldo = D) byte for byte, the K padding of a row included.  Everything up to the packed fp16
+// words `pk` is the fp16 kernel's code.
 #pragma once
 #include "mx_format.h"
 
 namespace vcxmx {
 
-// element bytes [(b t p)][ldq], scale bytes [(b t p)][ldq / 32], ldq = Kp(64 heads)
-struct TAttnMxOut {
+// element bytes [rows][ldq], scale bytes [rows][ldq / 32], ldq = Kp(64 heads)
+struct AttnMxOut {
     uint8_t* q;
     uint8_t* s;
     int64_t ldq;
 };
 
-// pk[4 db + gq] = the packed fp16 words of columns 8 (4 db + gq) + 4 hi .. + 3 of output row (frame) lq, lane = 32 hi + lq - what the fp16
-// store tail starts from.  `row` = (b T + lq) P + pix; rvalid = lq < T (all 64 lanes take part in the exchanges, only valid rows store).
+// pk[4 db + gq] = the packed fp16 words of columns 8 (4 db + gq) + 4 hi .. + 3 of head h of the lane's output row, lane = 32 hi + lq - what
+// the fp16 store tails start from (the MFMA 32x32 accumulator layout of O^T).  `row` = the row's index in the output; rvalid = the row
+// exists (all 64 lanes take part in the exchanges, only valid rows store).
 template <class U2>
-__device__ __forceinline__ void tattn_mx_store(const U2 (&pk)[8], const TAttnMxOut& o, int64_t row, int h, int heads, int hi, bool rvalid) {
+__device__ __forceinline__ void attn_mx_store(const U2 (&pk)[8], const AttnMxOut& o, int64_t row, int h, int heads, int hi, bool rvalid) {
     typedef unsigned u4v __attribute__((ext_vector_type(4)));
     // The fp16 tail's swap: v_permlane32_swap on the words of groups k and k + 1 leaves this lane with chunk j = k / 2 = columns
     // 16 j + 8 hi .. + 7.  MX block blk = chunks 2 blk and 2 blk + 1 of both lane halves.
@@ -47,7 +50,7 @@ __device__ __forceinline__ void tattn_mx_store(const U2 (&pk)[8], const TAttnMxO
         if (rvalid) *reinterpret_cast<u4v*>(qrow + 32 * blk + 16 * hi) = u4v{t0[0], t1[0], t0[1], t1[1]};
     }
     if (rvalid && hi == 0) *reinterpret_cast<unsigned short*>(srow) = (unsigned short)(sb[0] | (sb[1] << 8));
-    // odd head count (D % 128 == 64): the last head's wave also writes the row's K padding - 64 zero bytes under scale 1
+    // odd head count (D % 128 == 64): the last head's lanes also write the row's K padding - 64 zero bytes under scale 1
     if ((heads & 1) && h == heads - 1 && rvalid) {
         *reinterpret_cast<u4v*>(qrow + 64 + 16 * hi) = u4v{0u, 0u, 0u, 0u};
         *reinterpret_cast<u4v*>(qrow + 96 + 16 * hi) = u4v{0u, 0u, 0u, 0u};

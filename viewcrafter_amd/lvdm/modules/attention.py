@@ -55,7 +55,7 @@ FF_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_FF_MXFP8_SKIP
 # LayerNorm + quantiser in one pass, the q|k|v projection reading those bytes (un-folded weights, a zero bias: the reference has none),
 # the temporal attention kernel writing MXFP8 bytes + scales itself (vcx_attn_temporal_d64_mxfp8: a head's 64 columns are two MX blocks
 # held by one wave, so no quantiser pass), to_out with bias and residual reading them.  T <= 32, no relative position; any refusal keeps
-# the fp16 calls for the whole transformer.  The spatial transformer stays fp16.  Accuracy with a real checkpoint is unmeasured; what was
+# the fp16 calls for the whole transformer.  (The spatial transformer: SATTN_MXFP8 below.)  Accuracy with a real checkpoint is unmeasured; what was
 # measured is in profiles/mxfp8_tattn.md.  Off: no new launch, no new allocation, every output bit as before.
 TATTN_MXFP8 = os.environ.get("VCX_TATTN_MXFP8", "0") == "1"
 # Widths whose temporal attentions stay on the fp16 route although the switch is on: those whose isolated MX layer is not faster than
@@ -63,6 +63,20 @@ TATTN_MXFP8 = os.environ.get("VCX_TATTN_MXFP8", "0") == "1"
 # pads a sixth of K, N = 320 half-fills the third column tile), 640 / 1280 are 1.05x / 1.26x against a spread of 0.5 % (profiles/mxfp8_tattn.md).
 # VCX_TATTN_MXFP8_SKIP_DIMS="" puts every width on MX.
 TATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_TATTN_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+# Opt-in (VCX_SATTN_MXFP8=1, default off; independent of the other four switches): the attention projections of every block of a
+# SpatialTransformer on the MXFP8 matrix pipe - LayerNorm + quantiser in one pass in front of q|k, V^T (vcx_gemm_mxfp8 with its operands
+# swapped: ops.linear_t_mxfp8) and the cross-attention's query projection, un-folded weights carrying the base-2 logit scale; the three
+# spatial attention kernels write MXFP8 bytes + scales themselves (vcx_attn_flash_d64_mxfp8 / vcx_attn_flash_dual_d64_mxfp8: the fp16
+# kernels with a quantising store tail, so no quantiser pass), and both to_out layers read them, with bias and residual.  The context
+# K / V (cached per video), proj_in and the feed-forward + proj_out keep their code; no row-statistics buffers are requested.  Any
+# refusal keeps the fp16 calls for the whole transformer.  Accuracy with a real checkpoint is unmeasured; what was measured is in
+# profiles/mxfp8_sattn.md.  Off: no new launch, no new allocation, every output bit as before.
+SATTN_MXFP8 = os.environ.get("VCX_SATTN_MXFP8", "0") == "1"
+# Widths whose spatial attentions stay on the fp16 route although the switch is on, by the rule of profiles/mxfp8_tattn.md: a width stays on
+# fp16 unless its isolated MX layer beats the fp16 layer by more than the fp16 layer's own spread in the same run.  320 by default: the two
+# attentions of a 320-wide block are 0.94x of fp16 on MX (Kp = 384 pads a sixth of K; to_out 0.74x, q|k 0.91x), 640 / 1280 are 1.04x / 1.15x
+# against a spread of 0.2 - 0.7 % (profiles/mxfp8_sattn.md).  VCX_SATTN_MXFP8_SKIP_DIMS="" puts every width on MX.
+SATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_SATTN_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
 
 # A transformer's last two linear layers - ff.net[2] + block residual, then proj_out + transformer residual - have nothing between them
 # and the token stream between them has no other reader (depth 1; proj_out follows the last block), so they run as ONE GEMM over
@@ -288,13 +302,24 @@ class CrossAttention(PackedModule):
 
     def mx_packed(self):
         """TATTN_MXFP8 (temporal self-attention): the MXFP8 pairs of the UN-folded cat(Wq, Wk, Wv) and of to_out's weight, a zero bias [3D]
-        for the projection that has none (vcx_gemm_mxfp8 wants one) and bo.  Built at first use of the route, inside the pack: dropped with it."""
+        for the projection that has none (vcx_gemm_mxfp8 wants one) and bo.  SATTN_MXFP8 (kind "spatial"): self-attention - the pairs of
+        sqrt(scale log2 e) * cat(Wq, Wk) (scaled in fp32, one fp16 rounding), of Wv and of to_out's weight, a zero bias [2D]; cross-attention -
+        the pairs of scale log2 e * Wq and of to_out's weight, a zero bias [D].  Built at first use of the route, inside the pack: dropped with it."""
         pk = self.packed()
         if "mx" not in pk:
             with torch.no_grad():
-                wqkv = _f16(torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach(), self.to_v.weight.detach()], 0))
-                pk["mx"] = dict(wqkv=pack_mxfp8(wqkv), zero=torch.zeros(wqkv.shape[0], dtype=torch.float32, device=wqkv.device),
-                                wo=pack_mxfp8(pk["wo"]), bo=pk["bo"])
+                wq, wk, wv = self.to_q.weight.detach().float(), self.to_k.weight.detach().float(), self.to_v.weight.detach().float()
+                zeros = lambda n: torch.zeros(n, dtype=torch.float32, device=wq.device)
+                if self.kind == "temporal":
+                    wqkv = _f16(torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach(), self.to_v.weight.detach()], 0))
+                    mx = dict(wqkv=pack_mxfp8(wqkv), zero=zeros(wqkv.shape[0]))
+                elif self.is_self:
+                    wqk = _f16(torch.cat([wq, wk], 0) * math.sqrt(self.scale * ops.LOG2E))
+                    mx = dict(wqk=pack_mxfp8(wqk), wv=pack_mxfp8(_f16(wv)), zero=zeros(wqk.shape[0]))
+                else:
+                    wq2 = _f16(wq * (self.scale * ops.LOG2E))
+                    mx = dict(wq=pack_mxfp8(wq2), zero=zeros(wq2.shape[0]))
+                pk["mx"] = dict(mx, wo=pack_mxfp8(pk["wo"]), bo=pk["bo"])
         return pk["mx"]
 
     def forward(self, *args, **kwargs):
@@ -496,6 +521,38 @@ class SpatialTransformer(PackedModule):
     def project_context(self, ctx):
         return [project_context(blk.attn2, ctx) for blk in self.transformer_blocks]
 
+    def _mx_route(self, x, context_kv, frames_per_video, cfg_repeat, N, D):
+        """SATTN_MXFP8: do the attentions of every block of this call run on the MX route?  Decided once per call, before anything runs:
+        width not skipped, GPU tensors, and every predicate of the library - asked about the frames of ONE video (a row's route must not
+        depend on the batch it runs in: B = 2 against two B = 1, the shared CFG prefix against the replicated batch) and about the call
+        itself, before and behind the CFG replication (only the 32-bit extents depend on the batch).  Any refusal keeps the fp16 calls
+        for the whole transformer."""
+        n, H, W, _ = x.shape
+        if not SATTN_MXFP8 or D in SATTN_MXFP8_SKIP_DIMS:
+            return False
+        attns = [a for blk in self.transformer_blocks for a in (blk.attn1, blk.attn2)]
+        if any(a.to_out[0].bias is None or a.inner_dim != D or a.query_dim != D for a in attns):
+            return False
+        N_img, heads = H * W, self.n_heads
+        for frames in sorted({frames_per_video, n, n * cfg_repeat}):
+            tokens = frames * N
+            if not (ops.linear_mxfp8_ok(tokens, 2 * D, D) and ops.linear_t_mxfp8_ok(tokens, D, D) and ops.linear_mxfp8_ok(tokens, D, D)
+                    and ops.linear_mxfp8_ok(tokens, D, D, residual=True)
+                    and ops.flash_attn_mxfp8_ok(n_groups=frames, heads=heads, nq=N, nk=N_img, kv_rows=N, kv_div=1, ldq=2 * D, ldk=2 * D, ldvt=tokens)):
+                return False
+            for kv in context_kv:
+                nb = kv.n_txt_rows // 80
+                if kv.k_img is not None:
+                    ok = ops.flash_attn_dual_mxfp8_ok(n_groups=frames, heads=heads, nq=N, nk1=kv.n_txt, kv_rows1=80, kv_div1=frames_per_video, ldk1=D,
+                                                      ldvt1=nb * 80, nk2=kv.n_img, kv_rows2=kv.n_img, kv_div2=1 if kv.img_per_frame else frames_per_video,
+                                                      ldk2=D, ldvt2=kv.vt_img.shape[1], ldq=D)
+                else:
+                    ok = ops.flash_attn_mxfp8_ok(n_groups=frames, heads=heads, nq=N, nk=kv.n_txt, kv_rows=80, kv_div=frames_per_video, ldq=D, ldk=D,
+                                                 ldvt=nb * 80)
+                if not ok:
+                    return False
+        return True
+
     def forward(self, x, context_kv=None, frames_per_video=1, cfg_repeat=1, colstats=None, want_colstats=False, **kwargs):
         """x [n, H, W, C] fp16 channels-last, n = b*t frames; context_kv from project_context().
         cfg_repeat = r > 1: x holds ONE copy of a batch whose r conditionings (classifier-free guidance: cond / uncond / ...)
@@ -508,6 +565,7 @@ class SpatialTransformer(PackedModule):
         n, H, W, C = x.shape
         N_img = H * W
         pk = self.packed()
+        mx = self._mx_route(x, context_kv, frames_per_video, cfg_repeat, (N_img + 7) // 8 * 8, pk["win"].shape[0])      # SATTN_MXFP8, decided before anything runs
         # colstats: column moments of x from the convolution that produced it (ResBlock): the norm then needs no statistics pass
         stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, N_img, C)
         D_in = pk["win"].shape[0]
@@ -538,7 +596,8 @@ class SpatialTransformer(PackedModule):
         rs_eps = blk0.norm1.eps
         rs = None
         video_rows = frames_per_video * N
-        if _folded(blk0.attn1.packed()["qk"], tokens, D_in, D_in) and ops.rowstats_ok(tokens, D_in, C, lda=C, unit_rows=N_img if fold else None,
+        # (no row statistics on the MX route: the quantising LayerNorm computes its own)
+        if not mx and _folded(blk0.attn1.packed()["qk"], tokens, D_in, D_in) and ops.rowstats_ok(tokens, D_in, C, lda=C, unit_rows=N_img if fold else None,
                                                                                       video_rows=video_rows):
             rs = ops.rowstats_buffer(tokens, x.device)
         if fold:
@@ -548,6 +607,11 @@ class SpatialTransformer(PackedModule):
         D, heads = t.shape[1], self.n_heads
         for bi, (blk, kv) in enumerate(zip(self.transformer_blocks, context_kv)):
             ln = blk.ln_params()
+            if mx:
+                t, n, tokens, xin = _sattn_mx_block(blk, kv, ln, t, xin, n, N, N_img, D, heads, frames_per_video, cfg_repeat if bi == 0 else 1)
+                if bi + 1 < len(self.transformer_blocks):
+                    t = blk.ff.run(t, ln[2])
+                continue
             a1, a2 = blk.attn1.packed(), blk.attn2.packed()
             # ---- self-attention over the h*w tokens of each frame
             # scale * log2(e) rides in the projections (sqrt of it on Q and on K: one fp16 rounding each, as without it), so the
@@ -590,6 +654,34 @@ class SpatialTransformer(PackedModule):
             ops.copy2d(out, unpadded, n, N_img * C, N * C, N_img * C)
             out = unpadded
         return out.view(n, H, W, C), cs_out
+
+
+def _sattn_mx_block(blk, kv, ln, t, xin, n, N, N_img, D, heads, frames_per_video, cfg_repeat):
+    """The two attentions of one SpatialTransformer block on the SATTN_MXFP8 route: ten calls, in this order.  -> (t, n, tokens, xin), the
+    last three as the CFG replication in front of the cross-attention leaves them."""
+    m1, m2 = blk.attn1.mx_packed(), blk.attn2.mx_packed()
+    tokens = n * N
+    an = ops.layer_norm_mxfp8(t, *ln[0])
+    qk = ops.linear_mxfp8(an, m1["wqk"], m1["zero"], K=D)                     # [tokens, 2D] fp16, base-2 logit scale in the weights
+    vt = ops.linear_t_mxfp8(an, m1["wv"], K=D)                                # [D, tokens] fp16
+    o = ops.flash_attn_mxfp8(qk, qk[:, D:], vt, n_groups=n, heads=heads, nq=N, nk=N_img, kv_rows=N, kv_div=1, ldq=2 * D, ldk=2 * D, ldvt=tokens,
+                             scale=blk.attn1.scale)                           # MXFP8 pair [tokens, Kp(D)]
+    t = ops.linear_mxfp8(o, m1["wo"], m1["bo"], K=D, residual=t)
+    an2 = ops.layer_norm_mxfp8(t, *ln[1])
+    q2 = ops.linear_mxfp8(an2, m2["wq"], m2["zero"], K=D)
+    if cfg_repeat > 1:      # from here on the r conditionings differ
+        t, q2, xin = ops.repeat_rows(t, cfg_repeat), ops.repeat_rows(q2, cfg_repeat), ops.repeat_rows(xin, cfg_repeat)
+        n, tokens = n * cfg_repeat, tokens * cfg_repeat
+    nb = kv.n_txt_rows // 80
+    if kv.k_img is not None:
+        o2 = ops.flash_attn_dual_mxfp8(q2, kv.k_txt, kv.vt_txt, kv.k_img, kv.vt_img, n_groups=n, heads=heads, nq=N, nk1=kv.n_txt, kv_rows1=80,
+                                       kv_div1=frames_per_video, ldk1=D, ldvt1=nb * 80, nk2=kv.n_img, kv_rows2=kv.n_img,
+                                       kv_div2=1 if kv.img_per_frame else frames_per_video, ldk2=D, ldvt2=kv.vt_img.shape[1], ldq=D, scale=blk.attn2.scale)
+    else:
+        o2 = ops.flash_attn_mxfp8(q2, kv.k_txt, kv.vt_txt, n_groups=n, heads=heads, nq=N, nk=kv.n_txt, kv_rows=80, kv_div=frames_per_video, ldq=D, ldk=D,
+                                  ldvt=nb * 80, scale=blk.attn2.scale)
+    t = ops.linear_mxfp8(o2, m2["wo"], m2["bo"], K=D, residual=t)
+    return t, n, tokens, xin
 
 
 class TemporalTransformer(PackedModule):

@@ -529,6 +529,31 @@ def linear_mxfp8(a, w, bias, *, K, residual=None, geglu=False, mx_out=False):
     return out
 
 
+_ZERO_BIAS = {}      # (entries, device) -> fp32 zeros: the bias vcx_gemm_mxfp8 wants where the layer has none (linear_t_mxfp8)
+
+
+def _zero_bias(n, device):
+    key = (n, str(device))
+    if key not in _ZERO_BIAS:
+        _ZERO_BIAS[key] = torch.zeros(n, dtype=torch.float32, device=device)
+    return _ZERO_BIAS[key]
+
+
+def linear_t_mxfp8_ok(tokens, D, K):
+    """Does linear_t_mxfp8 take `tokens` activation rows x K onto D weight rows?  vcx_gemm_mxfp8 with the operands swapped: the library's
+    answer for M = D, N = tokens, plus the tile overreach of the token side, which the library guards for its M side only - the column
+    tiles reach up to 127 rows past `tokens`, and those 32-bit offsets must not wrap back into the buffer."""
+    return tokens % 8 == 0 and (tokens + 127) * mx_kp(K) < (1 << 32) and lib().vcx_gemm_mxfp8_ok(D, tokens, K, _mx_flags()) == 1
+
+
+def linear_t_mxfp8(x, w, *, K):
+    """The transposed projection fp16 [D, tokens] = w x^T (V^T of the spatial self-attention) of MXFP8 pairs x [tokens, K], w [D, K]:
+    linear_mxfp8(x, w, 0) transposed, bit for bit.  vcx_gemm_mxfp8 is symmetric in its operands, so this is that call with the weight
+    pair as `a` and a cached zero bias of `tokens` entries (the bias is per output column); no kernel of its own."""
+    tokens = x[0].shape[0]
+    return linear_mxfp8(w, x, _zero_bias(tokens, x[0].device), K=K)
+
+
 def group_norm_mxfp8(x, gamma, beta, eps, silu, groups=32, stats=None, x2=None):
     """quant_mxfp8(group_norm(x, ...).view(rows, C)), byte for byte, in one pass: the normalised fp16 tensor is never written.
     x [n_outer, pixels, C] fp16 (contiguous, C % 32 == 0); statistics computed here or handed in, as for group_norm.  x2
@@ -723,6 +748,41 @@ def flash_attn_dual(q, k1, vt1, k2, vt2, out, *, n_groups, heads, nq, nk1, kv_ro
                                             kv_rows2, kv_div2, ldk2, ldvt2, ldq, ldo, scale,
                                             ATTN_LOG2_LOGITS if log2_logits else 0, _stream()), "attn_flash_dual_d64")
     return out
+
+
+def flash_attn_mxfp8_ok(*, n_groups, heads, nq, nk, kv_rows, kv_div, ldq, ldk, ldvt, log2_logits=True, accumulate=False):
+    """Does vcx_attn_flash_d64_mxfp8 take this geometry, these pitches and flags?  The library's answer (no device needed)."""
+    flags = (ATTN_ACCUMULATE if accumulate else 0) | (ATTN_LOG2_LOGITS if log2_logits else 0)
+    return lib().vcx_attn_flash_d64_mxfp8_ok(n_groups, heads, nq, nk, kv_rows, kv_div, ldq, ldk, ldvt, flags) == 1
+
+
+def flash_attn_mxfp8(q, k, vt, *, n_groups, heads, nq, nk, kv_rows, kv_div, ldq, ldk, ldvt, scale=1.0, log2_logits=True):
+    """quant_mxfp8(flash_attn(q, k, vt, ...) with ldo = 64 heads), byte for byte, in one pass: the fp16 attention output is never written.
+    Returns (element bytes [n_groups * nq, Kp(64 heads)], scale bytes [n_groups * nq, Kp / 32]), the a operand of linear_mxfp8.  Base-2
+    logits only (include/vcx.h)."""
+    _dev16(q, k, vt)
+    oq, os_ = _mx_buffers(n_groups * nq, 64 * heads, q.device)
+    check(lib().vcx_attn_flash_d64_mxfp8(q.data_ptr(), k.data_ptr(), vt.data_ptr(), oq.data_ptr(), os_.data_ptr(), n_groups, heads, nq, nk, kv_rows,
+                                         kv_div, ldq, ldk, ldvt, scale, ATTN_LOG2_LOGITS if log2_logits else 0, _stream()), "attn_flash_d64_mxfp8")
+    return oq, os_
+
+
+def flash_attn_dual_mxfp8_ok(*, n_groups, heads, nq, nk1, kv_rows1, kv_div1, ldk1, ldvt1, nk2, kv_rows2, kv_div2, ldk2, ldvt2, ldq,
+                             log2_logits=True):
+    """Does vcx_attn_flash_dual_d64_mxfp8 take the call (it has no first-form resident kernel: knob XATTN_RESIDENT = 2)?  The library's answer."""
+    return lib().vcx_attn_flash_dual_d64_mxfp8_ok(n_groups, heads, nq, nk1, kv_rows1, kv_div1, ldk1, ldvt1, nk2, kv_rows2, kv_div2, ldk2, ldvt2, ldq,
+                                                  ATTN_LOG2_LOGITS if log2_logits else 0) == 1
+
+
+def flash_attn_dual_mxfp8(q, k1, vt1, k2, vt2, *, n_groups, heads, nq, nk1, kv_rows1, kv_div1, ldk1, ldvt1, nk2, kv_rows2, kv_div2, ldk2, ldvt2,
+                          ldq, scale=1.0, log2_logits=True):
+    """quant_mxfp8(flash_attn_dual(...) with ldo = 64 heads), byte for byte, in one pass; returns the MXFP8 pair as flash_attn_mxfp8."""
+    _dev16(q, k1, vt1, k2, vt2)
+    oq, os_ = _mx_buffers(n_groups * nq, 64 * heads, q.device)
+    check(lib().vcx_attn_flash_dual_d64_mxfp8(q.data_ptr(), k1.data_ptr(), vt1.data_ptr(), k2.data_ptr(), vt2.data_ptr(), oq.data_ptr(), os_.data_ptr(),
+                                              n_groups, heads, nq, nk1, kv_rows1, kv_div1, ldk1, ldvt1, nk2, kv_rows2, kv_div2, ldk2, ldvt2, ldq, scale,
+                                              ATTN_LOG2_LOGITS if log2_logits else 0, _stream()), "attn_flash_dual_d64_mxfp8")
+    return oq, os_
 
 
 def temporal_attn(qkv, out, *, B, T, P, heads, ld, k_off, v_off, ldo, scale, causal=False):
