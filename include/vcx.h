@@ -43,8 +43,9 @@ extern "C" {
  * vcx_conv_t3_mxfp8_ok.  14: MXFP8 ResBlock 3x3 convolutions - vcx_conv3x3_mxfp8, vcx_conv3x3_mxfp8_ok, vcx_groupnorm_apply2_mxfp8_f16.
  * 15: MXFP8 temporal attention output - vcx_attn_temporal_d64_mxfp8, vcx_attn_temporal_d64_mxfp8_ok.
  * 16: DPM-Solver++(2M) step - vcx_dpmpp2m_step_f32.  17: MXFP8 spatial attention output - vcx_attn_flash_d64_mxfp8,
- * vcx_attn_flash_dual_d64_mxfp8 and their _ok predicates. */
-#define VCX_ABI_VERSION 17
+ * vcx_attn_flash_dual_d64_mxfp8 and their _ok predicates.  18: a second tile configuration (128 x 160) of the MXFP8 GEMM kernel for
+ * N = 160 j - vcx_gemm_mxfp8_cfg. */
+#define VCX_ABI_VERSION 18
 
 int vcx_abi_version(void);
 const char* vcx_last_error(void);
@@ -279,8 +280,9 @@ int vcx_quant_mxfp8_f16(const void* x, int64_t ldx, void* q, void* scales, int64
 int vcx_layernorm_mxfp8_f16(const void* x, void* q, void* scales, const float* gamma, const float* beta, int64_t rows, int C, float eps,
                             void* stream);
 /* out[m, n] = epilogue( sum_k A[m, k] W[n, k] ), both operands MXFP8 over the same K (A: M rows, W: N rows), fp32 accumulation.
- * Operands reach LDS by buffer-load DMA with descriptor zero-fill, persistent XCD-aware tile walk, no atomics.  One tile shape and
- * one K order: a row's result depends neither on M nor on the tile or the grid it runs in.  flags (exactly one of):
+ * Operands reach LDS by buffer-load DMA with descriptor zero-fill, persistent XCD-aware tile walk, no atomics.  Two tile shapes
+ * (vcx_gemm_mxfp8_cfg) that give the same bytes and one K order: a row's result depends neither on M nor on the tile or the grid it
+ * runs in.  flags (exactly one of):
  *   VCX_GEMM_BIAS_N                                          out fp16 [M][ldc] = acc + bias[n]
  *   VCX_GEMM_BIAS_N | VCX_GEMM_RESIDUAL                      ... + residual[m * ldr + n]
  *   VCX_GEMM_BIAS_N | VCX_GEMM_GEGLU                         out fp16 [M][ldc], N / 2 columns: x * gelu_erf(gate), W / bias rows packed as
@@ -295,6 +297,16 @@ int vcx_gemm_mxfp8(const void* a, const void* a_scales, const void* w, const voi
  * words above, K % 32 == 0, N % 8 == 0 (GEGLU: N % 64 == 0, i.e. N / 2 % 32 == 0), every operand, output and residual extent below
  * 4 GiB (32-bit buffer offsets, as in the fp16 DMA engine).  Touches no device; callers ask it instead of restating the rules. */
 int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags);
+/* ABI 18.  The tile configuration vcx_gemm_mxfp8 (gather_mode 0), vcx_conv_t3_mxfp8 (1) or vcx_conv3x3_mxfp8 (2) runs a call of N output
+ * columns and this flag word on: 0 = 128 x 128, 1 = 128 x 160 (column tiles that divide N = 160 j: 320 columns are two whole tiles, not two
+ * and a half).  The launchers switch on this answer; like vcx_gemm_route it needs no pointer and no device.  The configurations compute the
+ * same bytes - the tile shape does not enter a row's arithmetic - so the answer is a matter of speed alone.  Rule: 1 iff the flag word's
+ * epilogue exists on the wide configuration (the plain and the column-moment epilogues of all three entry points; not GEGLU), N % 160 == 0 and
+ * N % 128 != 0.  A function of N, never of M: a row's configuration cannot depend on the batch.  Environment variable VCX_GEMM_MX_CFG, read
+ * once at the first use (tests, A/B runs): unset = the rule; 0 = always 128 x 128; 1 = 128 x 160 wherever its epilogue exists, ragged N
+ * (any N % 8 == 0) included.  A flag word or N the entry point refuses answers 0.  (A launcher keeps 128 x 128 where (N + 159) weight rows
+ * would pass the 32-bit offsets its _ok predicate checked for N + 127.)  Negative: an unknown gather mode. */
+int vcx_gemm_mxfp8_cfg(int64_t N, int flags, int gather_mode);
 /* ABI 13.  quant(vcx_groupnorm_apply_f16(x)) byte for byte in one pass: that kernel's thread map and arithmetic, every value rounded to fp16
  * as it would store it, then quantised per block of 32 channels; the fp16 tensor is never written.  x fp16 [n_outer][pixels][C] dense,
  * C % 32 == 0; q [n_outer pixels][Kp(C)], scales [n_outer pixels][Kp(C) / 32], padding (element bytes 0x00, scale bytes 127) included;
@@ -308,7 +320,7 @@ int vcx_groupnorm_apply_mxfp8_f16(const void* x, void* q, void* scales, const fl
  *   w / w_scales   [N][3][Kp(Cin)] / [N][3][Kp(Cin) / 32]: tap-major, every tap quantised and padded on its own (no block mixes taps;
  *                  packing.pack_conv_t3_mxfp8)
  * flags: VCX_GEMM_BIAS_N (required), optionally | VCX_GEMM_RESIDUAL, | VCX_GEMM_COLSTATS (colstats points at the first of this call's N
- * columns inside a [B T P / 64][ldcs][2] buffer, as for vcx_gemm_f16).  One tile shape and one K order (tap 0, 1, 2): a row's bits depend
+ * columns inside a [B T P / 64][ldcs][2] buffer, as for vcx_gemm_f16).  One K order (tap 0, 1, 2) in both tile shapes: a row's bits depend
  * neither on B, nor on the number of rows, nor on the tile or the grid.  Shapes: vcx_conv_t3_mxfp8_ok. */
 int vcx_conv_t3_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, const float* bias, const void* residual,
                       float* colstats, int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int flags,
@@ -334,7 +346,7 @@ int vcx_groupnorm_apply2_mxfp8_f16(const void* x1, int c1, const void* x2, void*
  *                  (no block and no K-step mixes taps; packing.pack_conv3x3_mxfp8)
  *   rowadd         fp32 [.][rowadd_ld], one row per rowadd_div output rows (the timestep embedding: rowadd_div = frames per video * H W)
  * flags: VCX_GEMM_BIAS_N (required), optionally | VCX_GEMM_ROWADD, | VCX_GEMM_RESIDUAL, | VCX_GEMM_COLSTATS (colstats points at the first of
- * this call's N columns inside a [n H W / 64][ldcs][2] buffer, as for vcx_gemm_f16).  One tile shape and one K order: a row's bits depend
+ * this call's N columns inside a [n H W / 64][ldcs][2] buffer, as for vcx_gemm_f16).  One K order in both tile shapes: a row's bits depend
  * neither on n, nor on the number of rows, nor on the tile or the grid.  Shapes: vcx_conv3x3_mxfp8_ok. */
 int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, const float* bias, const float* rowadd,
                       const void* residual, float* colstats, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr,

@@ -17,6 +17,9 @@ A variant is  name:key=value,key=value  with keys
     tattnskip widths joined by '+' that keep fp16 with tattn=1 (attention.TATTN_MXFP8_SKIP_DIMS), e.g. tattnskip=320; tattnskip= for none
     sattn    0 | 1   spatial attention on the MXFP8 route (attention.SATTN_MXFP8; off by default)
     sattnskip widths joined by '+' that keep fp16 with sattn=1 (attention.SATTN_MXFP8_SKIP_DIMS), e.g. sattnskip=320; sattnskip= for none
+    ff / tconv / resconv  0 | 1   the feed-forward pair / TemporalConvBlock / ResBlock convolutions on the MXFP8 route (attention.FF_MXFP8,
+             openaimodel3d.TCONV_MXFP8 / RESCONV_MXFP8; off by default), with ffmxskip / tconvskip / resconvskip = widths joined by '+' that keep
+             fp16 (the *_SKIP_DIMS lists; `tconvskip=` for none)
 e.g.   base:gnfold=0,xattn=2  gnfold:gnfold=1,xattn=2  xattn2:gnfold=0,xattn=1  all:gnfold=1,xattn=1
 --lib runs everything on another build of the library of the SAME ABI (e.g. tools/_abl/libvcx_gelu_select.so, built by
 tools/build_abl.sh): a library-level change is then compared across two invocations on the same box."""
@@ -46,6 +49,7 @@ def main():
     from viewcrafter_amd.builder import build_diffusion_model, randomize_parameters
     from viewcrafter_amd.lvdm.models.samplers.ddim import DDIMSampler
     from viewcrafter_amd.lvdm.modules import attention
+    from viewcrafter_amd.lvdm.modules.networks import openaimodel3d
     ops.require_gpu()
     print(f"library: {_lib.LIB_PATH}", flush=True)
     cfg_name, T, h, w = WORKLOADS[args.workload]
@@ -76,7 +80,14 @@ def main():
     default_tattn = attention.TATTN_MXFP8, attention.TATTN_MXFP8_SKIP_DIMS
     default_sattn = attention.SATTN_MXFP8, attention.SATTN_MXFP8_SKIP_DIMS
 
+    mx_switches = {"ff": (attention, "FF_MXFP8", "ffmxskip"), "tconv": (openaimodel3d, "TCONV_MXFP8", "tconvskip"),
+                   "resconv": (openaimodel3d, "RESCONV_MXFP8", "resconvskip")}
+    default_mx = {k: (getattr(mod, name), getattr(mod, name + "_SKIP_DIMS")) for k, (mod, name, _) in mx_switches.items()}
+
     def apply(settings):
+        for k, (mod, name, skip) in mx_switches.items():
+            setattr(mod, name, settings[k] != "0" if k in settings else default_mx[k][0])
+            setattr(mod, name + "_SKIP_DIMS", frozenset(int(v) for v in settings[skip].split("+") if v) if skip in settings else default_mx[k][1])
         attention.GN_FOLD = settings.get("gnfold", "1") != "0"
         attention.GN_FOLD_SPATIAL = {"0": 0, "2": 2}.get(settings.get("gnspatial", "1"), 1)
         lnff, lnff_min = settings.get("lnff", "2") != "0", (640 if settings.get("lnff", "2") == "2" else 0)      # 2 (the product): levels 1-3 only (C >= 640)

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libvcx.so")
 
 # every symbol include/vcx.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
-    "vcx_abi_version", "vcx_last_error", "vcx_device_arch", "vcx_gemm_f16", "vcx_gemm_units_f16", "vcx_gemm_route", "vcx_quant_mxfp8_f16", "vcx_layernorm_mxfp8_f16", "vcx_gemm_mxfp8", "vcx_gemm_mxfp8_ok",
+    "vcx_abi_version", "vcx_last_error", "vcx_device_arch", "vcx_gemm_f16", "vcx_gemm_units_f16", "vcx_gemm_route", "vcx_quant_mxfp8_f16", "vcx_layernorm_mxfp8_f16", "vcx_gemm_mxfp8", "vcx_gemm_mxfp8_ok", "vcx_gemm_mxfp8_cfg",
     "vcx_groupnorm_apply_mxfp8_f16", "vcx_conv_t3_mxfp8", "vcx_conv_t3_mxfp8_ok",
     "vcx_groupnorm_apply2_mxfp8_f16", "vcx_conv3x3_mxfp8", "vcx_conv3x3_mxfp8_ok",
     "vcx_groupnorm_ws_bytes", "vcx_groupnorm_stats_f16", "vcx_groupnorm_apply_f16", "vcx_groupnorm_apply2_f16", "vcx_groupnorm_stats_from_colstats_f32", "vcx_groupnorm_fold_linear_f16", "vcx_layernorm_f16", "vcx_rowstats_f16",
@@ -25,7 +25,7 @@ SYMBOLS = [
     "vcx_dpmpp2m_step_f32", "vcx_profile_begin", "vcx_profile_end", "vcx_tune_set", "vcx_tune_get",
 ]
 
-ABI_VERSION = 17         # include/vcx.h VCX_ABI_VERSION
+ABI_VERSION = 18         # include/vcx.h VCX_ABI_VERSION
 # experiment knobs (include/vcx.h VCX_TUNE_*): name -> (index, default)
 TUNE = {"GEMM_CFG": (0, -1), "GEMM_DMA": (1, 1), "FLASH_QB": (2, 0), "XATTN_RESIDENT": (3, 1), "FLASH_IMPL": (4, 0), "EXP0": (5, 0),
         "EXP1": (6, 0), "GEMM_WS": (7, 1)}
@@ -89,6 +89,7 @@ def lib():
     L.vcx_gemm_mxfp8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                  c_int64, c_int, c_void_p]
     L.vcx_gemm_mxfp8_ok.argtypes = [c_int64, c_int64, c_int64, c_int]
+    L.vcx_gemm_mxfp8_cfg.argtypes = [c_int64, c_int, c_int]
     L.vcx_groupnorm_apply_mxfp8_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_float, c_int, c_void_p]
     L.vcx_conv_t3_mxfp8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
                                     c_int64, c_int64, c_int64, c_int, c_void_p]

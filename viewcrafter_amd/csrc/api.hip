@@ -69,6 +69,16 @@ int vcx_tune(int knob) {
     std::call_once(g_tune_once, tune_init);
     return g_tune[knob].load(std::memory_order_relaxed);
 }
+// VCX_GEMM_MX_CFG (include/vcx.h vcx_gemm_mxfp8_cfg): -1 = unset (the rule), 0 / 1 = one tile configuration wherever it exists; read once
+static int g_mx_cfg = -1;
+static std::once_flag g_mx_cfg_once;
+int vcx_mx_cfg_knob() {
+    std::call_once(g_mx_cfg_once, [] {
+        const char* e = getenv("VCX_GEMM_MX_CFG");
+        g_mx_cfg = (e && (e[0] == '0' || e[0] == '1') && !e[1]) ? e[0] - '0' : -1;
+    });
+    return g_mx_cfg;
+}
 extern "C" int vcx_tune_get(int knob) {
     if (knob < 0 || knob >= VCX_TUNE_COUNT) { vcx_set_error("vcx_tune_get: no knob %d", knob); return VCX_EINVAL; }
     return vcx_tune(knob);

@@ -16,9 +16,12 @@
 // elements held by its neighbours (groups 2 (g >> 1) and 2 (g >> 1) + 1 hold block g's elements).  tests/test_mxfp8_gpu.py checks the
 // whole path with exact data and per-(row, block) scales: a lane that fed 32 consecutive elements was an exact mismatch.
 //
-// ONE tile shape (128 x 128, 2 x 2 waves, 64 x 64 per wave) and one K order: a row's result does not depend on M, on the tile it falls
-// into or on the grid.  A wave's 64 packed GEGLU columns are 32 output columns - one MX block of the next layer's K axis - so the
-// quantising epilogue takes a block's maximum inside the wave, across the four lane groups, with two lane swaps.  No atomics.
+// TWO tile shapes - 128 x 128 (Cfg128: 2 x 2 waves, 64 x 64 per wave) and 128 x 160 (Cfg160: 64 x 80 per wave, for N = 160 j: 320 columns
+// are two whole tiles of 160, not two and a half of 128) - and ONE K order: the tile shape does not enter a row's arithmetic (same K-steps,
+// same instruction, same epilogue statements), so a row's result does not depend on M, on the tile it falls into, on the configuration or
+// on the grid, and both configurations give the same bytes.  vcx_gemm_mxfp8_cfg (below) chooses from N alone.  A wave's 64 packed GEGLU
+// columns are 32 output columns - one MX block of the next layer's K axis - so the quantising epilogue takes a block's maximum inside the
+// wave, across the four lane groups, with two lane swaps: the GEGLU epilogues exist on Cfg128 only.  No atomics.
 //
 // vcx_conv_t3_mxfp8 (T3 = true): the (3,1,1) temporal convolution as a GATHERED mode of the same kernel.  K is three taps of Kp(Cin) each
 // (weights [N][3][Kp], tap-major, every tap padded on its own: no MX block and no K-step straddles two taps); K-step kt belongs to tap
@@ -81,11 +84,17 @@ struct MxCfg {
     static constexpr int MF = TBM / NWM / 16, NF = TBN / NWN / 16;
     static constexpr int XROWS = TBM * 8 / THREADS, WROWS = TBN * 8 / THREADS, RSTEP = THREADS / 8;
     static constexpr size_t TILE = (size_t)(TBM + TBN) * KSTEP;             // element bytes of one stage
-    static constexpr size_t SCALES = (size_t)(TBM + TBN) * 4;               // scale dwords of one stage
+    // scale dwords of one stage: [TBM] activation rows, then the weight rows rounded up to whole waves - every scale DMA instruction is
+    // issued by all 64 lanes of a wave (a lane beyond TBN weight rows has an out-of-range offset and writes a zero into the padding)
+    static constexpr int SROWS = TBM + (TBN + 63) / 64 * 64;
+    static constexpr int SPASS = (SROWS + THREADS - 1) / THREADS;           // scale-DMA passes: one dword per thread and pass
+    static constexpr size_t SCALES = (size_t)SROWS * 4;
     static constexpr size_t STAGES = 2 * (TILE + SCALES);
     static constexpr size_t STRIP = (size_t)TBN * NWM * sizeof(float);      // gemm_epilogue's strip of column addends per wave
     static constexpr size_t SMEM = STAGES + STRIP;
-    static_assert(TBM + TBN == THREADS && TBM % 64 == 0, "scale DMA: one dword per thread, a wave's 64 rows on one operand");
+    // pass 0 covers the activation rows and the first THREADS - TBM weight rows, a second pass (Cfg160: wave 0, weight rows 128 .. 159) the rest
+    static_assert(TBM % 64 == 0 && TBM < THREADS && SPASS <= 2, "scale DMA: one dword per thread and pass, a wave's 64 rows on one operand");
+    static_assert(XROWS * THREADS == TBM * 8 && WROWS * THREADS == TBN * 8, "tile DMA: whole rows of 8 threads");
 };
 
 __device__ __forceinline__ int mx_lds_off(int row, int chunk) {      // byte offset of a 16-byte chunk of a [rows][128] byte tile (lds_off's swizzle)
@@ -170,7 +179,8 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
     constexpr int WM = TBM / Cfg::NWM, WN = TBN / Cfg::NWN;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];      // ALL of the kernel's LDS: [2] tiles, [2] scale dwords, strips
     unsigned char* sT = smem_raw;                                     // stage b: X tile [TBM][128], then W tile [TBN][128]
-    unsigned* sS = reinterpret_cast<unsigned*>(smem_raw + 2 * Cfg::TILE);      // stage b: [TBM] activation-row dwords, then [TBN] weight-row dwords
+    unsigned* sS = reinterpret_cast<unsigned*>(smem_raw + 2 * Cfg::TILE);      // stage b: [TBM] activation-row dwords, then the weight-row dwords (Cfg::SROWS in all)
+    constexpr int SROWS = Cfg::SROWS;
 
     const __amdgpu_buffer_rsrc_t srd_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.A), 0, (int)p.a_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t srd_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.W), 0, (int)p.w_bytes, 0x00020000);
@@ -185,6 +195,9 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
     const int chunk = tid & 7;   // LDS chunk position inside the 128-byte row
     const int r0 = tid >> 3;     // tile row of this thread's first DMA instruction
     const bool scale_is_a = wave < TBM / 64;      // wave-uniform: this wave's scale dwords belong to activation rows
+    // wave-uniform: this wave also issues a second scale pass, for the weight rows THREADS - TBM + 64 wave ... that pass 0 does not reach
+    [[maybe_unused]] const bool scale2 = Cfg::SPASS > 1 && Cfg::THREADS + wave * 64 < SROWS;
+    [[maybe_unused]] unsigned soff_w2 = OOB;
 
     unsigned xoff[XROWS], woff[WROWS], soff_v;
     // T3: bit 3 i + tap = the source row of tap `tap` exists for this thread's DMA row i (i = XROWS: its scale row); xoff / soff_v then hold
@@ -239,6 +252,11 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             const int n = tile_n * TBN + (tid - TBM);
             soff_v = n < p.N ? (unsigned)n * (wpitch >> 5) : OOB;
         }
+        if constexpr (Cfg::SPASS > 1) {
+            const int r = Cfg::THREADS - TBM + tid;      // weight row of the second pass
+            const int n = tile_n * TBN + r;
+            soff_w2 = (r < TBN && n < p.N) ? (unsigned)n * (wpitch >> 5) : OOB;
+        }
     };
     // issue the DMA of K-step kt of the load tile into LDS stage `buf` (T3: kt is K-step kk of tap `tap`, kt = tap nk_tap + kk; C9: kt is
     // tap `tap` of slab kk, kt = 9 kk + tap)
@@ -266,7 +284,7 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
         for (int i = 0; i < WROWS; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_w, (lds_ptr_t)(dw + RSTEP * i * KSTEP), 16, woff[i], soff, 0, 0);
         // the K-step's four scale bytes of every tile row: one dword per thread, lane-linear behind the wave's base
-        unsigned* ds = sS + buf * (TBM + TBN) + wave * 64;
+        unsigned* ds = sS + buf * SROWS + wave * 64;
         if constexpr (GATHER) {
             if (scale_is_a) {
                 const unsigned vo = valid(XROWS) ? soff_v + sshift : OOB;
@@ -276,6 +294,9 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             }
         } else {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(scale_is_a ? srd_as : srd_ws, (lds_ptr_t)ds, 4, soff_v, (unsigned)kt * 4u, 0, 0);
+        }
+        if constexpr (Cfg::SPASS > 1) {      // the weight side is linear in K in every gather mode
+            if (scale2) __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_ws, (lds_ptr_t)(ds + Cfg::THREADS), 4, soff_w2, (unsigned)kt * 4u, 0, 0);
         }
     };
 
@@ -320,7 +341,7 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
         if (more) load_tile(lkt, cur ^ 1, ltap, lkk);        // async: lands in the other stage while this one is consumed
         const unsigned char* cx = sT + cur * Cfg::TILE;
         const unsigned char* cw = cx + TBM * KSTEP;
-        const unsigned* csx = sS + cur * (TBM + TBN);
+        const unsigned* csx = sS + cur * SROWS;
         const unsigned* csw = csx + TBM;
         auto frag = [&](const unsigned char* base, int row) {      // the lane's 32 K-elements of `row`: 16-byte chunks lg and 4 + lg (see the file header)
             const i4v lo = *reinterpret_cast<const i4v*>(base + mx_lds_off(row, lg));
@@ -411,6 +432,8 @@ int launch_mx(const MxArgs& a, hipStream_t s) {
 }
 
 using Cfg128 = MxCfg<128, 128, 2, 2>;
+using Cfg160 = MxCfg<128, 160, 2, 2>;      // 64 x 80 per wave (MF 4, NF 5); plain and column-moment epilogues, every gather mode
+static_assert(Cfg160::TBM == Cfg128::TBM, "the shape predicates' row reach (127 rows past M) holds for both configurations");
 constexpr unsigned long long LIM = 0xFFFF0000ull;      // 32-bit buffer offsets, as in the fp16 DMA engine
 
 // the epilogue a flag word selects: 0 / 1 / 2 as gemm_mx_kernel's EPI, -1 = a combination this entry point does not have
@@ -497,7 +520,35 @@ bool c9_takes(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int flags
     return true;
 }
 
+// The tile configuration of a call: 0 = Cfg128, 1 = Cfg160 (include/vcx.h vcx_gemm_mxfp8_cfg).  A function of N, the flag word and the gather
+// mode - never of M: a row's configuration cannot depend on the batch.  Cfg160 has the plain and the column-moment epilogue only.
+int mx_cfg_of(int64_t N, int flags, int gm) {
+    bool has;
+    if (gm == 0) has = epi_of(flags) == 0;
+    else {
+        const int may = VCX_GEMM_BIAS_N | VCX_GEMM_RESIDUAL | VCX_GEMM_COLSTATS | (gm == 2 ? VCX_GEMM_ROWADD : 0);
+        has = (flags & VCX_GEMM_BIAS_N) && !(flags & ~may);
+    }
+    if (!has || N <= 0 || N % 8 != 0) return 0;
+    const int knob = vcx_mx_cfg_knob();
+    if (knob >= 0) return knob;
+    return N % Cfg160::TBN == 0 && N % Cfg128::TBN != 0;
+}
+
+// the launchers' configuration: mx_cfg_of's, unless the wide tile's reach of TBN - 1 weight rows past N leaves the 32-bit offsets (row_bytes =
+// taps x Kp; the shape predicates vouch for Cfg128's reach only) - such a call keeps Cfg128, which computes the same bytes
+int mx_cfg_launch(int64_t N, int flags, int gm, unsigned long long row_bytes) {
+    const int cfg = mx_cfg_of(N, flags, gm);
+    if (cfg == 1 && ((unsigned long long)N + Cfg160::TBN - 1) * row_bytes >= LIM) return 0;
+    return cfg;
+}
+
 }  // namespace
+
+extern "C" int vcx_gemm_mxfp8_cfg(int64_t N, int flags, int gather_mode) {
+    VCX_REQUIRE(gather_mode >= 0 && gather_mode <= 2, "vcx_gemm_mxfp8_cfg: gather mode %d (0 = vcx_gemm_mxfp8, 1 = vcx_conv_t3_mxfp8, 2 = vcx_conv3x3_mxfp8)", gather_mode);
+    return mx_cfg_of(N, flags, gather_mode);
+}
 
 extern "C" int vcx_conv3x3_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
                                     int64_t rowadd_div, int flags) {
@@ -548,8 +599,9 @@ extern "C" int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void
     p.flags = flags;
     p.colstats = colstats;
     p.ldcs = ldcs;
+    const int cfg = mx_cfg_launch(N, flags, 2, 9ull * (unsigned long long)p.kp);
     p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
-    p.tiles_n = (int)((N + Cfg128::TBN - 1) / Cfg128::TBN);
+    p.tiles_n = (int)((N + (cfg ? Cfg160::TBN : Cfg128::TBN) - 1) / (cfg ? Cfg160::TBN : Cfg128::TBN));
     p.a_bytes = (unsigned)(M * p.kp);
     p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
     p.w_bytes = (unsigned)(N * 9 * p.kp);
@@ -558,8 +610,8 @@ extern "C" int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void
     p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + N)) : 0u;
     hipStream_t s = (hipStream_t)stream;
     VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * 9.0 * Cin, (double)(M + 9 * N) * p.kp + 2.0 * M * N);
-    if (flags & VCX_GEMM_COLSTATS) return launch_mx<Cfg128, 3, 2>(p, s);
-    return launch_mx<Cfg128, 0, 2>(p, s);
+    if (flags & VCX_GEMM_COLSTATS) return cfg ? launch_mx<Cfg160, 3, 2>(p, s) : launch_mx<Cfg128, 3, 2>(p, s);
+    return cfg ? launch_mx<Cfg160, 0, 2>(p, s) : launch_mx<Cfg128, 0, 2>(p, s);
 }
 
 extern "C" int vcx_conv_t3_mxfp8_ok(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
@@ -603,8 +655,9 @@ extern "C" int vcx_conv_t3_mxfp8(const void* a, const void* a_scales, const void
     p.flags = flags;
     p.colstats = colstats;
     p.ldcs = ldcs;
+    const int cfg = mx_cfg_launch(N, flags, 1, 3ull * (unsigned long long)p.kp);
     p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
-    p.tiles_n = (int)((N + Cfg128::TBN - 1) / Cfg128::TBN);
+    p.tiles_n = (int)((N + (cfg ? Cfg160::TBN : Cfg128::TBN) - 1) / (cfg ? Cfg160::TBN : Cfg128::TBN));
     p.a_bytes = (unsigned)(M * p.kp);
     p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
     p.w_bytes = (unsigned)(N * 3 * p.kp);
@@ -613,8 +666,8 @@ extern "C" int vcx_conv_t3_mxfp8(const void* a, const void* a_scales, const void
     p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + N)) : 0u;
     hipStream_t s = (hipStream_t)stream;
     VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * 3.0 * Cin, (double)(M + 3 * N) * p.kp + 2.0 * M * N);
-    if (flags & VCX_GEMM_COLSTATS) return launch_mx<Cfg128, 3, 1>(p, s);
-    return launch_mx<Cfg128, 0, 1>(p, s);
+    if (flags & VCX_GEMM_COLSTATS) return cfg ? launch_mx<Cfg160, 3, 1>(p, s) : launch_mx<Cfg128, 3, 1>(p, s);
+    return cfg ? launch_mx<Cfg160, 0, 1>(p, s) : launch_mx<Cfg128, 0, 1>(p, s);
 }
 
 extern "C" int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags) {
@@ -655,8 +708,9 @@ extern "C" int vcx_gemm_mxfp8(const void* a, const void* a_scales, const void* w
     p.ldc = (int)ldc;
     p.ldr = (int)ldr;
     p.flags = flags;
+    const int cfg = mx_cfg_launch(N, flags, 0, (unsigned long long)p.kp);      // (1 for the plain epilogue only)
     p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
-    p.tiles_n = epi == 2 ? 2 * p.kpo / Cfg128::TBN : (int)((N + Cfg128::TBN - 1) / Cfg128::TBN);
+    p.tiles_n = epi == 2 ? 2 * p.kpo / Cfg128::TBN : (int)((N + (cfg ? Cfg160::TBN : Cfg128::TBN) - 1) / (cfg ? Cfg160::TBN : Cfg128::TBN));
     p.a_bytes = (unsigned)(M * p.kp);
     p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
     p.w_bytes = (unsigned)(N * p.kp);
@@ -667,7 +721,7 @@ extern "C" int vcx_gemm_mxfp8(const void* a, const void* a_scales, const void* w
     hipStream_t s = (hipStream_t)stream;
     VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * K, (double)(M + N) * p.kp + 2.0 * M * nout);
     switch (epi) {
-        case 0: return launch_mx<Cfg128, 0>(p, s);
+        case 0: return cfg ? launch_mx<Cfg160, 0>(p, s) : launch_mx<Cfg128, 0>(p, s);
         case 1: return launch_mx<Cfg128, 1>(p, s);
         default: return launch_mx<Cfg128, 2>(p, s);
     }

@@ -503,6 +503,15 @@ def linear_mxfp8_ok(rows, N, K, *, residual=False, geglu=False, mx_out=False):
     return lib().vcx_gemm_mxfp8_ok(rows, N, K, _mx_flags(residual, geglu, mx_out)) == 1
 
 
+def gemm_mxfp8_cfg(N, flags=GEMM_BIAS_N, gather_mode=0):
+    """The tile configuration the MXFP8 GEMM kernel runs N output columns with this flag word on: 0 = 128 x 128, 1 = 128 x 160 (N = 160 j).
+    gather_mode 0 = linear_mxfp8, 1 = temporal_conv3_mxfp8, 2 = conv3x3_mxfp8.  The launchers' own answer (vcx_gemm_mxfp8_cfg: N, flags and
+    the environment variable VCX_GEMM_MX_CFG, no device); both configurations compute the same bytes."""
+    cfg = lib().vcx_gemm_mxfp8_cfg(N, flags, gather_mode)
+    check(min(cfg, 0), "gemm_mxfp8_cfg")
+    return cfg
+
+
 def linear_mxfp8(a, w, bias, *, K, residual=None, geglu=False, mx_out=False):
     """a, w: (element bytes, scale bytes) pairs of [rows, K] and [N, K] matrices (quant_mxfp8 / layer_norm_mxfp8 / a mx_out=True
     layer; packing.pack_mxfp8).  Returns fp16 [rows, N] = a w^T + bias (+ residual), or with geglu=True (w and bias packed by
