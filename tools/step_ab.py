@@ -20,6 +20,8 @@ A variant is  name:key=value,key=value  with keys
     ff / tconv / resconv  0 | 1   the feed-forward pair / TemporalConvBlock / ResBlock convolutions on the MXFP8 route (attention.FF_MXFP8,
              openaimodel3d.TCONV_MXFP8 / RESCONV_MXFP8; off by default), with ffmxskip / tconvskip / resconvskip = widths joined by '+' that keep
              fp16 (the *_SKIP_DIMS lists; `tconvskip=` for none)
+    fcache   N       feature cache (viewcrafter_amd/feature_cache.py): timed step i is a full forward iff i % N == 0, shallow otherwise (the
+             warm-up step fills the slot); 0 / 1 / absent = no cache object.  fcdepth = d (default 0)
 e.g.   base:gnfold=0,xattn=2  gnfold:gnfold=1,xattn=2  xattn2:gnfold=0,xattn=1  all:gnfold=1,xattn=1
 --lib runs everything on another build of the library of the SAME ABI (e.g. tools/_abl/libvcx_gelu_select.so, built by
 tools/build_abl.sh): a library-level change is then compared across two invocations on the same box."""
@@ -47,6 +49,7 @@ def main():
     from bench import WORKLOADS, synth_conditioning
     from viewcrafter_amd import ops
     from viewcrafter_amd.builder import build_diffusion_model, randomize_parameters
+    from viewcrafter_amd.feature_cache import FeatureCache
     from viewcrafter_amd.lvdm.models.samplers.ddim import DDIMSampler
     from viewcrafter_amd.lvdm.modules import attention
     from viewcrafter_amd.lvdm.modules.networks import openaimodel3d
@@ -64,11 +67,15 @@ def main():
     sampler.share_cfg_prefix = True
     n_sched = len(sampler.ddim_timesteps)
 
-    def one_step(x, i):
+    def one_step(x, i, fcache=None, interval=0):
         index = n_sched - 1 - (i % n_sched)
         ts = torch.full((1,), int(sampler.ddim_timesteps[index]), device="cuda", dtype=torch.long)
+        kw = {}
+        if fcache is not None:
+            fcache.set_mode("full" if i % interval == 0 else "shallow")
+            kw["feature_cache"] = fcache
         x, _ = sampler.p_sample_ddim(x, cond, ts, index=index, unconditional_guidance_scale=7.5, unconditional_conditioning=uc, fs=fs,
-                                     guidance_rescale=0.7, cfg_img=None, unconditional_conditioning_img_nonetext=None)
+                                     guidance_rescale=0.7, cfg_img=None, unconditional_conditioning_img_nonetext=None, **kw)
         return x
 
     variants = []
@@ -114,15 +121,17 @@ def main():
         apply(settings)
         torch.manual_seed(7)                         # the eta = 1 noise of every run is the same draw
         x = x0.clone()
+        interval = int(settings.get("fcache", "0"))
+        fcache = FeatureCache(depth=int(settings.get("fcdepth", "0"))) if interval >= 2 else None
         with torch.no_grad():
-            x = one_step(x, 0)                       # packs / caches of this variant
+            x = one_step(x, 0, fcache, interval)     # packs / caches of this variant (and the feature cache's first full forward)
             torch.cuda.synchronize()
             if profile:
                 ops.profile_begin(1 << 16)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for i in range(1, 1 + steps):
-                x = one_step(x, i)
+                x = one_step(x, i, fcache, interval)
             e1.record()
             torch.cuda.synchronize()
             prof = ops.profile_end() if profile else None

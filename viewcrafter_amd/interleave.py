@@ -37,6 +37,12 @@ def step_yield():
         il._switch(_tls.lane)
 
 
+def current_lane():
+    """The lane of run_interleaved this thread runs (0 outside it): state that a clip keeps on the SHARED model from one step to the next
+    (the feature cache's storage, feature_cache.py) is keyed by it, so two clips taking turns never read each other's."""
+    return _tls.lane if getattr(_tls, "interleaver", None) is not None else 0
+
+
 class _Interleaver:
     def __init__(self, n_lanes, streams=None):
         self.cv = threading.Condition()

@@ -14,6 +14,12 @@ timesteps with the DPM-Solver++(2M) update - the eta = 0 DDIM step plus a second
 one fused launch pair as well (vcx_dpmpp2m_step_f32; coefficients from utils_diffusion.dpmpp2m_coefficients).  The solver is
 deterministic: it needs eta = 0 and draws NO per-step noise, so after sampling the generator is not in the state the DDIM loop
 leaves it in (DDIM draws one Gaussian per step even at eta = 0, like the reference).  p_sample_ddim and decode() stay DDIM.
+
+VCX_FEATURE_CACHE=N (not in the reference; unset, 0 or 1 = the loops above, launch for launch): only the steps at loop positions
+i % N == 0 run the whole UNet, the others a shallow forward on top of the deep feature the last full step left behind
+(viewcrafter_amd/feature_cache.py; VCX_FEATURE_CACHE_DEPTH).  Either sampler, decode() and the multi-condition sampler go through it; the
+cache object is local to the call, and every denoiser evaluation of a step that runs on its own (the one-after-the-other guidance
+route, a guidance group's rank) has its own slot.
 """
 import os
 
@@ -21,6 +27,7 @@ import numpy as np
 import torch
 
 from .... import ops
+from ....feature_cache import feature_cache_plan, from_env as feature_cache_from_env
 from ....interleave import step_yield
 from ...common import noise_like
 from ..utils_diffusion import dpmpp2m_coefficients, make_ddim_sampling_parameters, make_ddim_timesteps
@@ -145,9 +152,14 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         clean_cond = kwargs.pop("clean_cond", False)
         self._cfg_cache = None
+        fcache, fplan = self._feature_cache(total_steps)
+        if fcache is not None:
+            kwargs = dict(kwargs, feature_cache=fcache)       # a keyword of the denoiser, like fs: p_sample_ddim and the solver's plan pass it on
         dpm = self._dpmpp2m_plan(mask, x0, kwargs) if sampler_choice() == "dpmpp2m" else None
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
+            if fcache is not None:
+                fcache.set_mode("full" if fplan[i] else "shallow")
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if mask is not None:   # vestigial in ViewCrafter (mask is always None)
                 assert x0 is not None
@@ -176,6 +188,23 @@ class DDIMSampler(object):
         if self.guidance_group is not None:      # x was never sent inside the group: check once per video that it did stay bit-equal
             self.guidance_group.check_equal(img, also={"x_T": start_sum})
         return img, intermediates
+
+    # ------------------------------------------------------------------ feature cache (VCX_FEATURE_CACHE)
+    def _feature_cache(self, total_steps):
+        """(cache object of this call, [step i is full]) or (None, None) with the switch off - read now, as VCX_SAMPLER is."""
+        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
+        fcache, interval = feature_cache_from_env(unet)
+        if fcache is None:
+            return None, None
+        return fcache, feature_cache_plan(total_steps, interval)
+
+    def _evaluate(self, x, t, c, kwargs, position=0):
+        """One denoiser evaluation; `position` = which of a step's evaluations it is where they run one after the other: each is a
+        stream of its own from step to step, so each has its own slot of the feature cache."""
+        fcache = kwargs.get("feature_cache")
+        if fcache is not None:
+            fcache.position = position
+        return self.model.apply_model(x, t, c, **kwargs)
 
     # ------------------------------------------------------------------ DPM-Solver++(2M) (VCX_SAMPLER=dpmpp2m)
     def _dpmpp2m_plan(self, mask, x0, kwargs):
@@ -238,7 +267,7 @@ class DDIMSampler(object):
             stats["forwards"] += 1
             stats["batch"] = x.shape[0]
         # the outputs are views of the group's ONE reused buffer: valid until the next exchange (the step kernel reads them now)
-        return group.exchange(self.model.apply_model(x, t, conds[group.position], **kwargs))
+        return group.exchange(self._evaluate(x, t, conds[group.position], kwargs, position=group.position))
 
     # ------------------------------------------------------------------ CFG batching
     @staticmethod
@@ -279,26 +308,26 @@ class DDIMSampler(object):
         n, b = len(conds), x.shape[0]
         kw = dict(kwargs)
         if self._shares_prefix(conds):
-            out = self.model.apply_model(x, t, self._cfg_cond(*conds, shared=True), cfg_repeat=n, **kw)
+            out = self._evaluate(x, t, self._cfg_cond(*conds, shared=True), dict(kw, cfg_repeat=n))
         else:
             if torch.is_tensor(kw.get("fs")):
                 kw["fs"] = torch.cat([kw["fs"]] * n, 0)
-            out = self.model.apply_model(torch.cat([x] * n, 0), torch.cat([t] * n, 0), self._cfg_cond(*conds), **kw)
+            out = self._evaluate(torch.cat([x] * n, 0), torch.cat([t] * n, 0), self._cfg_cond(*conds), kw)
         return [out[i * b:(i + 1) * b] for i in range(n)]
 
     def _model_outputs(self, x, t, c, unconditional_conditioning, unconditional_guidance_scale, kwargs):
         """Denoiser evaluations of one step (reference ddim.py:218-231).  Returns (v_cond, v_uncond | None, v_img | None,
         cfg_img)."""
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
-            return self.model.apply_model(x, t, c, **kwargs), None, None, 0.0
+            return self._evaluate(x, t, c, kwargs), None, None, 0.0
         if self.guidance_group is not None:
             v_c, v_u = self._split_outputs(x, t, (c, unconditional_conditioning), kwargs)
             return v_c, v_u, None, 0.0
         if self._batchable(c, unconditional_conditioning):
             v_c, v_u = self._apply_batched(x, t, (c, unconditional_conditioning), kwargs)
         elif isinstance(c, (torch.Tensor, dict)):
-            v_c = self.model.apply_model(x, t, c, **kwargs)
-            v_u = self.model.apply_model(x, t, unconditional_conditioning, **kwargs)
+            v_c = self._evaluate(x, t, c, kwargs, position=0)
+            v_u = self._evaluate(x, t, unconditional_conditioning, kwargs, position=1)
         else:
             raise NotImplementedError
         return v_c, v_u, None, 0.0
@@ -335,10 +364,14 @@ class DDIMSampler(object):
             raise NotImplementedError("DDPM-step decoding is not on the ViewCrafter path")
         steps = np.asarray(self.ddim_timesteps)[:t_start]
         x = x_latent
+        fcache, fplan = self._feature_cache(len(steps))
+        fkw = {} if fcache is None else dict(feature_cache=fcache)
         for done, index in enumerate(range(len(steps) - 1, -1, -1)):
             ts = torch.full((x.shape[0],), int(steps[index]), device=x.device, dtype=torch.long)
+            if fcache is not None:
+                fcache.set_mode("full" if fplan[done] else "shallow")
             x, _ = self.p_sample_ddim(x, cond, ts, index=index, unconditional_guidance_scale=unconditional_guidance_scale,
-                                      unconditional_conditioning=unconditional_conditioning)
+                                      unconditional_conditioning=unconditional_conditioning, **fkw)
             if callback:
                 callback(done)
         return x

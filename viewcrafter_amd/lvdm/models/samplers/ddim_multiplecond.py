@@ -41,13 +41,13 @@ class DDIMSampler(_DDIMSampler):
             cfg_img = unconditional_guidance_scale
         uc_img = kwargs["unconditional_conditioning_img_nonetext"]
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
-            return self.model.apply_model(x, t, c, **kwargs), None, None, 0.0
+            return self._evaluate(x, t, c, kwargs), None, None, 0.0
         if self.guidance_group is not None:
             v_c, v_u, v_i = self._split_outputs(x, t, (c, unconditional_conditioning, uc_img), kwargs)
         elif self._batchable(c, unconditional_conditioning, uc_img):
             v_c, v_u, v_i = self._apply_batched(x, t, (c, unconditional_conditioning, uc_img), kwargs)
         else:
-            v_c = self.model.apply_model(x, t, c, **kwargs)
-            v_u = self.model.apply_model(x, t, unconditional_conditioning, **kwargs)
-            v_i = self.model.apply_model(x, t, uc_img, **kwargs)
+            v_c = self._evaluate(x, t, c, kwargs, position=0)        # one after the other: three slots of the feature cache
+            v_u = self._evaluate(x, t, unconditional_conditioning, kwargs, position=1)
+            v_i = self._evaluate(x, t, uc_img, kwargs, position=2)
         return v_c, v_u, v_i, float(cfg_img)

@@ -28,14 +28,21 @@ class CatTarget:
     """Where the last layer of a block writes when its output is the LEFT part of the next block's channel concat: `data`
     [M, data_ld] fp16 (columns [0, c_left) are this block's output; data_ld = ld = c_left + c_right with the skip tensor copied
     behind them, or - `split` - data_ld = c_left: a plain tensor, the skip stays where it is) and, when the shapes allow it,
-    `moments` [M / 64, ld, 2] fp32 for the column moments of those columns."""
+    `moments` [M / 64, ld, 2] fp32 for the column moments of those columns.  `buffers` = (data, moments or None) of an earlier
+    target of the same shape: this one is laid over them instead of allocating (the feature cache keeps one target's storage alive
+    across forwards, feature_cache.py)."""
     __slots__ = ("data", "moments", "ld", "c_left", "data_ld", "split")
 
-    def __init__(self, M, c_left, c_right, device, with_moments, split=False):
+    def __init__(self, M, c_left, c_right, device, with_moments, split=False, buffers=None):
         self.c_left = c_left
         self.ld = c_left + c_right
         self.split = bool(split and with_moments)
         self.data_ld = c_left if self.split else self.ld
+        if buffers is not None:
+            self.data, self.moments = buffers[0], buffers[1] if with_moments else None
+            if tuple(self.data.shape) != (M, self.data_ld) or (with_moments and (self.moments is None or tuple(self.moments.shape) != (M // 64, self.ld, 2))):
+                raise ValueError(f"preallocated concat target of shape {tuple(self.data.shape)} does not fit [{M}, {self.data_ld}]")
+            return
         self.data = torch.empty((M, self.data_ld), dtype=torch.float16, device=device)
         self.moments = torch.empty((M // 64, self.ld, 2), dtype=torch.float32, device=device) if with_moments else None
 

@@ -639,17 +639,27 @@ class UNetModel(PackedModule):
         # hipGraph replay of the whole forward (launch-bound at the small UNet levels): opt-in, see forward_graphed()
         self.use_hip_graph = False
         self._graphs = {}
+        # feature cache (feature_cache.py): (slot, input shapes, cfg_repeat, depth) -> the storage of the concat target that output_blocks[L-2-d]
+        # writes, kept from a full forward for the shallow forwards that follow; allocated at first use, released by drop_feature_cache()
+        self._feature_store = {}
 
     # ------------------------------------------------------------------ packing / caches
     def _drop_packed(self):
         super()._drop_packed()
         self._ctx_cache = {}
         self._graphs = {}
+        self._feature_store = {}
 
     def _apply(self, fn, recurse=True):
         self._ctx_cache = {}
         self._graphs = {}
+        self._feature_store = {}
         return super()._apply(fn, recurse)
+
+    def drop_feature_cache(self):
+        """Release the feature cache's storage - and the captured graphs, whose launches address it."""
+        self._feature_store = {}
+        self._graphs = {k: v for k, v in self._graphs.items() if k[-1] is None}
 
     def _pack(self):
         c0 = self.input_blocks[0][0]
@@ -725,34 +735,78 @@ class UNetModel(PackedModule):
         # every ResBlock starts its emb branch with SiLU (emb_layers.0): do it once
         return ops.to_f16(ops.silu_f32(emb))
 
-    def forward(self, x, timesteps, context=None, features_adapter=None, fs=None, **kwargs):
+    def forward(self, x, timesteps, context=None, features_adapter=None, fs=None, feature_cache=None, **kwargs):
+        """feature_cache (feature_cache.FeatureCache; None = the plain forward): its mode says whether this call is a full forward that
+        leaves the deep feature behind in its slot, or a shallow one on top of what the slot holds (_forward_body)."""
+        if feature_cache is not None and features_adapter is not None:
+            raise NotImplementedError("feature_cache with features_adapter: an adapter feature is added behind input blocks that a shallow "
+                                      "forward skips - run without VCX_FEATURE_CACHE")
         if self.use_hip_graph and features_adapter is None and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
-            return self.forward_graphed(x, timesteps, context, fs, cfg_repeat=int(kwargs.get("cfg_repeat", 1) or 1))
-        return self._forward(x, timesteps, context=context, features_adapter=features_adapter, fs=fs, **kwargs)
+            return self.forward_graphed(x, timesteps, context, fs, cfg_repeat=int(kwargs.get("cfg_repeat", 1) or 1), feature_cache=feature_cache)
+        return self._forward(x, timesteps, context=context, features_adapter=features_adapter, fs=fs, feature_cache=feature_cache, **kwargs)
 
-    def forward_graphed(self, x, timesteps, context, fs, cfg_repeat=1):
+    GRAPH_SLOTS = 4             # captured graphs kept without a feature cache
+    GRAPH_SLOTS_CACHED = 8      # ... with one: full + shallow graphs of two lanes, and the next pair of clips' beside them
+
+    def _feature_begin(self, fc, shapes, r):
+        """Checks ahead of a forward with a feature cache (eager or replayed): the depth's range, and - shallow - that the slot is valid."""
+        L = len(self.output_blocks)
+        if not 0 <= fc.depth <= L - 2:
+            raise ValueError(f"feature cache depth {fc.depth}: expected 0 .. {L - 2} for a UNet of {L} output blocks")
+        if fc.mode == "shallow":
+            fc.check(shapes, r)
+            if (fc.slot, shapes, r, fc.depth) not in self._feature_store:
+                raise RuntimeError(f"feature cache: the storage of slot {fc.slot} was released (drop_feature_cache, or its captured graphs were evicted)")
+        elif fc.mode != "full":
+            raise ValueError(f"feature cache mode {fc.mode!r}: expected 'full' or 'shallow'")
+
+    def _evict_graphs(self, key):
+        """_graphs is full: drop every captured graph but the partner of `key` (the other mode of the same slot, inputs and conditioning),
+        and with the graphs of a slot its storage - a shallow forward of an evicted slot then fails loudly until a full one refills it."""
+        partner = lambda k: k[-1] is not None and k[:-1] == key[:-1] and k[-1][1:] == key[-1][1:]
+        self._graphs = {k: v for k, v in self._graphs.items() if partner(k)}
+        mine = (key[-1][2], key[0], key[5], key[-1][1])
+        self._feature_store = {k: v for k, v in self._feature_store.items() if k == mine}
+
+    def forward_graphed(self, x, timesteps, context, fs, cfg_repeat=1, feature_cache=None):
         """Replay the forward as one hipGraph (captured through torch.cuda.CUDAGraph: every libvcx call is stream-ordered,
         allocation-free and sync-free, so the ctypes launches are captured like any other kernel).  One graph per
         (shapes, conditioning tensor); inputs are copied into static buffers, the output buffer is reused by the next
         replay (the DDIM update consumes it first)."""
         parts = list(x) if isinstance(x, (list, tuple)) else [x]
-        key = (tuple(tuple(p.shape) for p in parts), context.data_ptr(), context._version, tuple(context.shape),
-               None if fs is None else tuple(fs.shape), cfg_repeat)
+        fc = feature_cache
+        shapes = tuple(tuple(p.shape) for p in parts)
+        # with a feature cache: one graph per mode, depth and slot - the full and the shallow graph of a slot address the same storage
+        # (_feature_store: allocated by the warm-up below, in the ordinary allocator - not in either capture's private pool)
+        key = (shapes, context.data_ptr(), context._version, tuple(context.shape),
+               None if fs is None else tuple(fs.shape), cfg_repeat, None if fc is None else (fc.mode, fc.depth, fc.slot))
+        if fc is not None:
+            self._feature_begin(fc, shapes, cfg_repeat)
         ent = self._graphs.get(key)
         if ent is None:
+            fkw = {} if fc is None else dict(feature_cache=fc)
+            filled = None if fc is None else dict(fc.filled)
             static = dict(parts=[p.detach().clone().float() for p in parts], t=timesteps.detach().clone(),
                           fs=None if fs is None else fs.detach().clone())
             with torch.no_grad():
-                self._forward(static["parts"], static["t"], context=context, fs=static["fs"], cfg_repeat=cfg_repeat)   # warm-up: packs, caches K/V
+                self._forward(static["parts"], static["t"], context=context, fs=static["fs"], cfg_repeat=cfg_repeat, **fkw)   # warm-up: packs, caches K/V
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    out = self._forward(static["parts"], static["t"], context=context, fs=static["fs"], cfg_repeat=cfg_repeat)
-            if len(self._graphs) >= 4:
-                self._graphs.clear()
+                    out = self._forward(static["parts"], static["t"], context=context, fs=static["fs"], cfg_repeat=cfg_repeat, **fkw)
+            if fc is None:
+                if len(self._graphs) >= self.GRAPH_SLOTS:
+                    self._graphs.clear()
+                    self._feature_store = {}
+            else:
+                fc.filled = filled          # the replay below fills the slot, not the capture
+                if len(self._graphs) >= self.GRAPH_SLOTS_CACHED:
+                    self._evict_graphs(key)
             # the captured launches bake in the addresses of the projected context K/V (allocated by the warm-up in the
-            # ordinary caching allocator): the entry owns them, so clearing _ctx_cache cannot free what a replay reads
-            ent = self._graphs[key] = (graph, static, out, context, self._context_kv(context, static["parts"][0].shape[2]))
+            # ordinary caching allocator): the entry owns them, so clearing _ctx_cache cannot free what a replay reads - and
+            # likewise the feature cache's storage of its slot, which both of the slot's graphs address
+            ent = self._graphs[key] = (graph, static, out, context, self._context_kv(context, static["parts"][0].shape[2]),
+                                       None if fc is None else self._feature_store.get((fc.slot, shapes, cfg_repeat, fc.depth)))
         graph, static, out = ent[:3]
         for dst, src in zip(static["parts"], parts):
             dst.copy_(src)
@@ -760,9 +814,11 @@ class UNetModel(PackedModule):
         if fs is not None:
             static["fs"].copy_(fs)
         graph.replay()
+        if fc is not None and fc.mode == "full":
+            fc.mark_filled(shapes, cfg_repeat)
         return out
 
-    def _forward(self, x, timesteps, context=None, features_adapter=None, fs=None, cfg_repeat=1, **kwargs):
+    def _forward(self, x, timesteps, context=None, features_adapter=None, fs=None, cfg_repeat=1, feature_cache=None, **kwargs):
         """x [B, in_channels, T, h, w] fp32 (or a list of tensors to be concatenated on channels, which is how
         DiffusionWrapper avoids materialising torch.cat([x] + c_concat)); timesteps [B] int64; context [B, L, D];
         fs [B] int64.  Extra keywords (cfg_img, unconditional_conditioning_img_nonetext, ...) leak in from the
@@ -785,6 +841,13 @@ class UNetModel(PackedModule):
         r = int(cfg_repeat or 1)
         if context.shape[0] != b * r:
             raise ValueError(f"context batch {context.shape[0]} != {b} videos x cfg_repeat {r}")
+        fc = feature_cache
+        if fc is not None:
+            if features_adapter is not None:
+                raise NotImplementedError("feature_cache with features_adapter: an adapter feature is added behind input blocks that a shallow "
+                                          "forward skips - run without VCX_FEATURE_CACHE")
+            shapes = tuple(tuple(p.shape) for p in parts)
+            self._feature_begin(fc, shapes, r)
         pk = self.packed()
         emb = self._embed(pk, timesteps, fs, b, device)
         ckv = self._context_kv(context, t)
@@ -798,14 +861,28 @@ class UNetModel(PackedModule):
                 o, n_e = pk["emb_off"][id(rb)]
                 rb._emb_all = emb_all[:, o:o + n_e]
         try:
-            return self._forward_body(parts, pk, emb, ckv, b, t, hh, ww, cin, r, device, features_adapter)
+            if fc is None:
+                return self._forward_body(parts, pk, emb, ckv, b, t, hh, ww, cin, r, device, features_adapter)
+            store = self._feature_store.setdefault((fc.slot, shapes, r, fc.depth), {})
+            y = self._forward_body(parts, pk, emb, ckv, b, t, hh, ww, cin, r, device, None, store=store, shallow=fc.mode == "shallow",
+                                   depth=fc.depth)
+            if fc.mode == "full":
+                fc.mark_filled(shapes, r)
+            return y
         finally:
             for rb in rbs:
                 rb._emb_all = None
 
-    def _forward_body(self, parts, pk, emb, ckv, b, t, hh, ww, cin, r, device, features_adapter):
+    def _forward_body(self, parts, pk, emb, ckv, b, t, hh, ww, cin, r, device, features_adapter, store=None, shallow=False, depth=0):
+        """store (feature cache; None = the plain forward): the dict of _feature_store that keeps what output_blocks[keep] writes, keep =
+        L - 2 - depth - `data` / `moments`, the buffers of its CatTarget, and `target`, that target as the full forward left it (level 2),
+        or `h`, a copy of its plain output (levels 0 / 1).  shallow: run input_blocks[0 .. depth], then output_blocks[keep + 1 ..] on
+        top of the stored target."""
         # batch currently flowing through the graph: b until the first SpatialTransformer replicated it, b * r afterwards
         cur_b = b
+        n_out = len(self.output_blocks)
+        keep = n_out - 2 - depth if store is not None else -1
+        first_out = keep + 1 if shallow else 0
 
         def replicate(a):      # [cur_b * t, H, W, C] -> [r * cur_b * t, H, W, C]
             n_, H_, W_, C_ = a.shape
@@ -830,6 +907,8 @@ class UNetModel(PackedModule):
         adapter_idx = 0
         cs = None              # column moments of h (None: not known - the consumer makes its statistics pass)
         for i, module in enumerate(self.input_blocks):
+            if shallow and i > depth:
+                break
             flow = Flow(colstats=cs, want=lvl2)
             if i == 0:
                 h = ops.conv2d(h, pk["w_in"], pk["b_in"], kh=3, kw=3)
@@ -850,36 +929,59 @@ class UNetModel(PackedModule):
             hs.append((h, cs))
         if features_adapter is not None and len(features_adapter) != adapter_idx:
             raise ValueError("Wrong features_adapter")                  # the reference's assertion, openaimodel3d.py:588
-        if cur_b != b * r:     # a graph without attention in the input path: replicate ahead of the middle block
-            h, cs, hs, emb, cur_b = replicate(h), replicate_cs(cs), [(replicate(a), replicate_cs(c)) for a, c in hs], ops.repeat_rows(emb, r), b * r
+        if cur_b != b * r:     # a graph without attention in the input path (or a shallow forward that stops ahead of it): replicate ahead of the middle block
+            if not shallow:    # (a shallow forward goes on from the stored target: h itself is not read again)
+                h, cs = replicate(h), replicate_cs(cs)
+            hs, emb, cur_b = [(replicate(a), replicate_cs(c)) for a, c in hs], ops.repeat_rows(emb, r), b * r
         b = cur_b
         if not lvl2:           # round-3 data path: materialised concat (two copies), statistics pass for every cross-module norm
-            h = self.middle_block(h, emb, context=ckv, batch_size=b)
-            for module in self.output_blocks:
+            if shallow:
+                skip = hs[-1][0]
+                h = store["h"].view(*skip.shape[:3], -1)
+            else:
+                h = self.middle_block(h, emb, context=ckv, batch_size=b)
+            for j in range(first_out, n_out):
                 skip, _ = hs.pop()
                 n, H, W, c1 = h.shape
                 h = ops.concat_channels(h.view(n * H * W, c1), skip.view(n * H * W, skip.shape[-1])).view(n, H, W, -1)
-                h = module(h, emb, context=ckv, batch_size=b)
+                h = self.output_blocks[j](h, emb, context=ckv, batch_size=b)
+                if j == keep:  # the kept feature: a copy in storage that outlives the forward (these levels have no concat target to lay over it)
+                    n, H, W, c1 = h.shape
+                    if "h" not in store:
+                        store["h"] = torch.empty((n * H * W, c1), dtype=torch.float16, device=device)
+                    ops.copy2d(h.reshape(n * H * W, c1), store["h"], n * H * W, c1, c1, c1)
             cs = None
         else:
             # Up path (openaimodel3d.py:595-597: h = torch.cat([h, hs.pop()], dim=1); h = module(h, ...)).  The block that PRODUCES h
             # writes it straight into the left columns of the next block's concatenated input - and its column moments into the left
             # columns of that tensor's moment buffer - so only the skip half is copied, and the GroupNorm in front of the next
             # ResBlock takes its statistics from the two producers' epilogues.
-            def target_for(n_, H_, W_, c_left, consumer):
+            def target_for(n_, H_, W_, c_left, consumer, kept=None):
                 skip, skip_cs = hs[-1]
                 M_ = n_ * H_ * W_
                 ok = skip_cs is not None and ops.colstats_ok(M_, H_ * W_, 64, c_left + skip.shape[-1])
                 # split (the concat is read in place) only into a block that starts with a ResBlock - the layer that can read two halves
                 split = CAT_SPLIT and SKIP_FOLD and c_left % 64 == 0 and skip.shape[-1] % 64 == 0 and isinstance(list(consumer)[0], ResBlock)
-                return CatTarget(M_, c_left, skip.shape[-1], device, with_moments=ok, split=split)
-            n, H, W, _ = h.shape
-            tgt = target_for(n, H, W, _out_channels_of(self.middle_block), self.output_blocks[0])
-            flow = Flow(colstats=cs, target=tgt)
-            h = self.middle_block(h, emb, context=ckv, batch_size=b, flow=flow)
-            for j, module in enumerate(self.output_blocks):
+                if kept is None:
+                    return CatTarget(M_, c_left, skip.shape[-1], device, with_moments=ok, split=split)
+                # the feature cache's target: the same target, over buffers that outlive this forward (allocated by the first one)
+                tg = CatTarget(M_, c_left, skip.shape[-1], device, with_moments=ok, split=split,
+                               buffers=(kept["data"], kept["moments"]) if "data" in kept else None)
+                kept["data"], kept["moments"], kept["target"] = tg.data, tg.moments, tg
+                return tg
+            if shallow:        # go on from what the last full forward of this slot wrote: [its h | this forward's skip]
+                tgt = store["target"]
+                hshape = (*hs[-1][0].shape[:3], tgt.c_left)
+            else:
+                n, H, W, _ = h.shape
+                tgt = target_for(n, H, W, _out_channels_of(self.middle_block), self.output_blocks[0])
+                flow = Flow(colstats=cs, target=tgt)
+                h = self.middle_block(h, emb, context=ckv, batch_size=b, flow=flow)
+                hshape = h.shape
+            for j in range(first_out, n_out):
+                module = self.output_blocks[j]
                 skip, skip_cs = hs.pop()
-                n, H, W, c1 = h.shape
+                n, H, W, c1 = hshape
                 M, c2 = n * H * W, skip.shape[-1]
                 if not tgt.split:
                     ops.copy2d(skip.view(M, c2), tgt.data[:, c1:], M, c2, c2, tgt.ld)
@@ -892,9 +994,10 @@ class UNetModel(PackedModule):
                 if j + 1 < len(self.output_blocks):
                     last = list(module)[-1]
                     up = 2 if isinstance(last, Upsample) or (isinstance(last, ResBlock) and last.up) else 1
-                    tgt = target_for(n, H * up, W * up, _out_channels_of(module), self.output_blocks[j + 1])
+                    tgt = target_for(n, H * up, W * up, _out_channels_of(module), self.output_blocks[j + 1], kept=store if j == keep else None)
                 flow = Flow(colstats=cat_cs, want=tgt is None, target=tgt)
                 h = module(hcat, emb, context=ckv, batch_size=b, flow=flow, x2=x2)
+                hshape = h.shape
             cs = flow.colstats
         n, H, W, c = h.shape
         stats = None if cs is None else ops.group_norm_stats_from_colstats(cs, n, H * W, c)
