@@ -44,7 +44,9 @@ extern "C" {
  * 15: MXFP8 temporal attention output - vcx_attn_temporal_d64_mxfp8, vcx_attn_temporal_d64_mxfp8_ok.
  * 16: DPM-Solver++(2M) step - vcx_dpmpp2m_step_f32.  17: MXFP8 spatial attention output - vcx_attn_flash_d64_mxfp8,
  * vcx_attn_flash_dual_d64_mxfp8 and their _ok predicates.  18: a second tile configuration (128 x 160) of the MXFP8 GEMM kernel for
- * N = 160 j - vcx_gemm_mxfp8_cfg. */
+ * N = 160 j - vcx_gemm_mxfp8_cfg.  Added under 18 (purely additive, no signature changed): the ResBlock skip convolution as a K tail of the
+ * MXFP8 3x3 convolution - vcx_conv3x3_tail_mxfp8, vcx_conv3x3_tail_mxfp8_ok, vcx_groupnorm_apply_mxfp8_raw_f16,
+ * vcx_groupnorm_apply2_mxfp8_raw_f16. */
 #define VCX_ABI_VERSION 18
 
 int vcx_abi_version(void);
@@ -358,6 +360,37 @@ int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void* w, const 
  * their flag.  Touches no device. */
 int vcx_conv3x3_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
                          int64_t rowadd_div, int flags);
+/* ABI 18 (added).  vcx_groupnorm_apply_mxfp8_f16 / vcx_groupnorm_apply2_mxfp8_f16 with a second, raw output from the same pass: (q, scales) are
+ * byte for byte what the parent entry point writes, (rq, rscales) are byte for byte vcx_quant_mxfp8_f16 of the input rows themselves - for two
+ * sources of the channel concat [x1 | x2] - padding (element bytes 0x00, scale bytes 127) included: [n_outer pixels][Kp(C)] and
+ * [n_outer pixels][Kp(C) / 32], rq 16-byte and rscales 4-byte aligned.  The dense MXFP8 image of a ResBlock's input that
+ * vcx_conv3x3_tail_mxfp8 reads as its K tail. */
+int vcx_groupnorm_apply_mxfp8_raw_f16(const void* x, void* q, void* scales, void* rq, void* rscales, const float* stats, const float* gamma,
+                                      const float* beta, int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream);
+int vcx_groupnorm_apply2_mxfp8_raw_f16(const void* x1, int c1, const void* x2, void* q, void* scales, void* rq, void* rscales, const float* stats,
+                                       const float* gamma, const float* beta, int n_outer, int64_t pixels, int C, int groups, float eps, int silu,
+                                       void* stream);
+/* ABI 18 (added).  vcx_conv3x3_mxfp8 with a 1x1 convolution of a second MXFP8 source as a linear K tail (a ResBlock's second convolution
+ * and its skip convolution in one accumulation):
+ *   out[(f,y,x), o] = bias[o] + sum_{ky,kx} sum_c A[(f, y + ky - 1, x + kx - 1), c] W3[o, c, ky, kx] + sum_c T[(f,y,x), c] W1[o, c]
+ *   a / a_scales   as for vcx_conv3x3_mxfp8
+ *   t / t_scales   [n H W][Kp(Ct)] / [n H W][Kp(Ct) / 32]: row m of the tail is read for output row m, wherever it sits in its frame
+ *   w / w_scales   [N][9 Kp(Cin) + Kp(Ct)] / [N][(9 Kp(Cin) + Kp(Ct)) / 32]: vcx_conv3x3_mxfp8's row, then the 1x1 weight quantised per
+ *                  32-channel block and padded to Kp(Ct) on its own (no block and no K-step straddles main and tail;
+ *                  packing.pack_conv3x3_tail_mxfp8)
+ *   bias           the sum of the two convolutions' biases
+ * flags: VCX_GEMM_BIAS_N (required), optionally | VCX_GEMM_COLSTATS; a residual or a row addend is refused.  One K order in both tile shapes
+ * - the main K-steps as vcx_conv3x3_mxfp8, then the tail's in ascending K - so a row's bits depend neither on n, nor on the number of rows,
+ * nor on the tile or the grid.  Shapes: vcx_conv3x3_tail_mxfp8_ok. */
+int vcx_conv3x3_tail_mxfp8(const void* a, const void* a_scales, const void* t, const void* t_scales, const void* w, const void* w_scales, void* out,
+                           const float* bias, float* colstats, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Ct, int64_t N, int64_t ldc,
+                           int64_t ldcs, int flags, void* stream);
+/* 1 if vcx_conv3x3_tail_mxfp8 takes the call, else 0 with the reason in vcx_last_error(): the flag words above, Cin % 32 == 0, Ct % 32 == 0,
+ * N % 8 == 0, ldc >= N and % 8 == 0, COLSTATS: n H W % 64 == 0, ldcs >= colstats_col + N, ldcs and colstats_col even, every dimension
+ * below 2^31; 32-bit buffer offsets: (n H W + 127 + W + 1) Kp(Cin), (n H W + 127) Kp(Ct), (N + 127) (9 Kp(Cin) + Kp(Ct)) and the output
+ * below 4 GiB.  ldcs / colstats_col are ignored without COLSTATS.  Touches no device. */
+int vcx_conv3x3_tail_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Ct, int64_t N, int64_t ldc, int64_t ldcs, int64_t colstats_col,
+                              int flags);
 
 /* ------------------------------------------------------------------------------------
  * Flash attention, head dim 64, no mask:  O = softmax(scale * Q K^T) V

@@ -2,8 +2,9 @@
 switches - VCX_FF_MXFP8 (feed-forward), VCX_TCONV_MXFP8 (temporal convolutions), VCX_RESCONV_MXFP8 (ResBlock 3x3 convolutions),
 VCX_TATTN_MXFP8 (temporal attention) and VCX_SATTN_MXFP8 (spatial attention) - off, alone and together: one UNet forward, and a 10-step DDIM trajectory (eta 0, CFG 7.5, guidance rescale 0.7) of the product sampler against
 the oracle sampler on the oracle UNet.  The skip lists are as the environment sets them; --all-widths empties all five.  Figures for
-profiles/mxfp8_ff.md, profiles/mxfp8_tconv.md, profiles/mxfp8_resconv.md, profiles/mxfp8_tattn.md and profiles/mxfp8_sattn.md.
-    python tools/mxfp8_accuracy.py [--steps 10] [--all-widths] [--only-tconv | --only-resconv | --only-tattn | --only-sattn]"""
+profiles/mxfp8_ff.md, profiles/mxfp8_tconv.md, profiles/mxfp8_resconv.md, profiles/mxfp8_tattn.md and profiles/mxfp8_sattn.md; the last row
+of the default table and --only-restail add VCX_RESCONV_MXFP8_TAIL (the skip convolution as a K tail; profiles/mxfp8_resconv_tail.md).
+    python tools/mxfp8_accuracy.py [--steps 10] [--all-widths] [--only-tconv | --only-resconv | --only-tattn | --only-sattn | --only-restail]"""
 import argparse
 import os
 import sys
@@ -34,6 +35,8 @@ def main():
     ap.add_argument("--only-resconv", action="store_true", help="all off, the ResBlock switch alone (under both KEEP_FOLD settings), all three switches on")
     ap.add_argument("--only-tattn", action="store_true", help="all off, the temporal-attention switch alone, all four switches on")
     ap.add_argument("--only-sattn", action="store_true", help="all off, the spatial-attention switch alone, all five switches on")
+    ap.add_argument("--only-restail", action="store_true", help="all off, the ResBlock switch alone, the ResBlock switch with VCX_RESCONV_MXFP8_TAIL, all five switches "
+                                                                "without and with it")
     a = ap.parse_args()
     from oracle import lvdm_oracle as O
     from viewcrafter_amd.builder import build_diffusion_model, randomize_parameters
@@ -66,13 +69,18 @@ def main():
     was = A.FF_MXFP8, U.TCONV_MXFP8, A.FF_MXFP8_SKIP_DIMS, U.TCONV_MXFP8_SKIP_DIMS, U.RESCONV_MXFP8, U.RESCONV_MXFP8_SKIP_DIMS, U.RESCONV_MXFP8_KEEP_FOLD
     was_tattn = A.TATTN_MXFP8, A.TATTN_MXFP8_SKIP_DIMS
     was_sattn = A.SATTN_MXFP8, A.SATTN_MXFP8_SKIP_DIMS
+    was_tail = U.RESCONV_MXFP8_TAIL
     if a.all_widths:
         A.FF_MXFP8_SKIP_DIMS = U.TCONV_MXFP8_SKIP_DIMS = U.RESCONV_MXFP8_SKIP_DIMS = A.TATTN_MXFP8_SKIP_DIMS = A.SATTN_MXFP8_SKIP_DIMS = frozenset()
     print(f"skip lists: feed-forward {sorted(A.FF_MXFP8_SKIP_DIMS)}, temporal convolutions {sorted(U.TCONV_MXFP8_SKIP_DIMS)}, "
           f"ResBlock convolutions {sorted(U.RESCONV_MXFP8_SKIP_DIMS)}, temporal attention {sorted(A.TATTN_MXFP8_SKIP_DIMS)}, "
           f"spatial attention {sorted(A.SATTN_MXFP8_SKIP_DIMS)}", flush=True)
-    # (feed-forward, temporal convolutions, ResBlock convolutions, KEEP_FOLD or None = as set, temporal attention[, spatial attention])
-    if a.only_sattn:
+    # (feed-forward, temporal convolutions, ResBlock convolutions, KEEP_FOLD or None = as set, temporal attention[, spatial attention[, the
+    # skip convolution as a K tail]])
+    if a.only_restail:
+        rows = [(False, False, False, None, False, False, False), (False, False, True, False, False, False, False), (False, False, True, False, False, False, True),
+                (True, True, True, False, True, True, False), (True, True, True, False, True, True, True)]
+    elif a.only_sattn:
         rows = [(False, False, False, None, False, False), (False, False, False, None, False, True), (True, True, True, None, True, True)]
     elif a.only_tattn:
         rows = [(False, False, False, None, False), (False, False, False, None, True), (True, True, True, None, True)]
@@ -81,13 +89,15 @@ def main():
     else:
         rows = [(ff, tconv, False, None, False) for ff, tconv in ((False, False), (True, False), (False, True), (True, True)) if not (a.only_tconv and ff and not tconv)]
         rows += [(False, False, True, None, False), (True, True, True, None, False), (False, False, False, None, True), (True, True, True, None, True)]
+        rows += [(False, False, True, False, False, False, True)]
     try:
         with torch.no_grad():
             ref_fwd = O.unet_forward(sd, hp, x, ts, ctx, fs)
             ref_traj, _ = O.ddim_sample(apply_oracle, tables, scale_arr, x_T, cond, uc, steps=a.steps, eta=0.0, cfg_scale=7.5, guidance_rescale=0.7,
                                         spacing="uniform_trailing", parameterization="v")
             for ff, tconv, resconv, keep, tattn, *rest in rows:
-                sattn = bool(rest and rest[0])
+                sattn, tail = bool(rest and rest[0]), bool(len(rest) > 1 and rest[1])
+                U.RESCONV_MXFP8_TAIL = tail
                 A.FF_MXFP8, U.TCONV_MXFP8, U.RESCONV_MXFP8, A.TATTN_MXFP8, A.SATTN_MXFP8 = ff, tconv, resconv, tattn, sattn
                 U.RESCONV_MXFP8_KEEP_FOLD = was[6] if keep is None else keep
                 y = unet._forward(x, ts, context=ctx, fs=fs)
@@ -95,12 +105,13 @@ def main():
                                                     unconditional_guidance_scale=7.5, unconditional_conditioning=uc, eta=0.0, cfg_img=None, mask=None,
                                                     x0=None, fs=fs, timestep_spacing="uniform_trailing", guidance_rescale=0.7, x_T=x_T,
                                                     log_every_t=a.steps, unconditional_conditioning_img_nonetext=None)
-                print(f"VCX_FF_MXFP8={int(ff)} VCX_TCONV_MXFP8={int(tconv)} VCX_RESCONV_MXFP8={int(resconv)}" + (f" (KEEP_FOLD={int(U.RESCONV_MXFP8_KEEP_FOLD)})" if resconv else "") + f" VCX_TATTN_MXFP8={int(tattn)} VCX_SATTN_MXFP8={int(sattn)}: UNet forward vs fp32 oracle rel-L2 {rel_l2(y, ref_fwd):.3e} PSNR {psnr(y, ref_fwd):.2f} dB | "
+                print(f"VCX_FF_MXFP8={int(ff)} VCX_TCONV_MXFP8={int(tconv)} VCX_RESCONV_MXFP8={int(resconv)}" + (f" (KEEP_FOLD={int(U.RESCONV_MXFP8_KEEP_FOLD)}, TAIL={int(tail)})" if resconv else "") + f" VCX_TATTN_MXFP8={int(tattn)} VCX_SATTN_MXFP8={int(sattn)}: UNet forward vs fp32 oracle rel-L2 {rel_l2(y, ref_fwd):.3e} PSNR {psnr(y, ref_fwd):.2f} dB | "
                       f"{a.steps}-step trajectory, final latent rel-L2 {rel_l2(ours, ref_traj):.3e} PSNR {psnr(ours, ref_traj):.2f} dB", flush=True)
     finally:
         A.FF_MXFP8, U.TCONV_MXFP8, A.FF_MXFP8_SKIP_DIMS, U.TCONV_MXFP8_SKIP_DIMS, U.RESCONV_MXFP8, U.RESCONV_MXFP8_SKIP_DIMS, U.RESCONV_MXFP8_KEEP_FOLD = was
         A.TATTN_MXFP8, A.TATTN_MXFP8_SKIP_DIMS = was_tattn
         A.SATTN_MXFP8, A.SATTN_MXFP8_SKIP_DIMS = was_sattn
+        U.RESCONV_MXFP8_TAIL = was_tail
 
 
 if __name__ == "__main__":

@@ -20,6 +20,8 @@ A variant is  name:key=value,key=value  with keys
     ff / tconv / resconv  0 | 1   the feed-forward pair / TemporalConvBlock / ResBlock convolutions on the MXFP8 route (attention.FF_MXFP8,
              openaimodel3d.TCONV_MXFP8 / RESCONV_MXFP8; off by default), with ffmxskip / tconvskip / resconvskip = widths joined by '+' that keep
              fp16 (the *_SKIP_DIMS lists; `tconvskip=` for none)
+    restail  0 | 1   with resconv=1: a ResBlock's skip convolution as a K tail of its MXFP8 second convolution (openaimodel3d.RESCONV_MXFP8_TAIL;
+             off by default), e.g.  mx:resconv=1  tail:resconv=1,restail=1
     fcache   N       feature cache (viewcrafter_amd/feature_cache.py): timed step i is a full forward iff i % N == 0, shallow otherwise (the
              warm-up step fills the slot); 0 / 1 / absent = no cache object.  fcdepth = d (default 0)
 e.g.   base:gnfold=0,xattn=2  gnfold:gnfold=1,xattn=2  xattn2:gnfold=0,xattn=1  all:gnfold=1,xattn=1
@@ -90,11 +92,13 @@ def main():
     mx_switches = {"ff": (attention, "FF_MXFP8", "ffmxskip"), "tconv": (openaimodel3d, "TCONV_MXFP8", "tconvskip"),
                    "resconv": (openaimodel3d, "RESCONV_MXFP8", "resconvskip")}
     default_mx = {k: (getattr(mod, name), getattr(mod, name + "_SKIP_DIMS")) for k, (mod, name, _) in mx_switches.items()}
+    default_restail = openaimodel3d.RESCONV_MXFP8_TAIL
 
     def apply(settings):
         for k, (mod, name, skip) in mx_switches.items():
             setattr(mod, name, settings[k] != "0" if k in settings else default_mx[k][0])
             setattr(mod, name + "_SKIP_DIMS", frozenset(int(v) for v in settings[skip].split("+") if v) if skip in settings else default_mx[k][1])
+        openaimodel3d.RESCONV_MXFP8_TAIL = settings["restail"] != "0" if "restail" in settings else default_restail
         attention.GN_FOLD = settings.get("gnfold", "1") != "0"
         attention.GN_FOLD_SPATIAL = {"0": 0, "2": 2}.get(settings.get("gnspatial", "1"), 1)
         lnff, lnff_min = settings.get("lnff", "2") != "0", (640 if settings.get("lnff", "2") == "2" else 0)      # 2 (the product): levels 1-3 only (C >= 640)

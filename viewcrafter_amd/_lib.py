@@ -16,6 +16,7 @@ SYMBOLS = [
     "vcx_abi_version", "vcx_last_error", "vcx_device_arch", "vcx_gemm_f16", "vcx_gemm_units_f16", "vcx_gemm_route", "vcx_quant_mxfp8_f16", "vcx_layernorm_mxfp8_f16", "vcx_gemm_mxfp8", "vcx_gemm_mxfp8_ok", "vcx_gemm_mxfp8_cfg",
     "vcx_groupnorm_apply_mxfp8_f16", "vcx_conv_t3_mxfp8", "vcx_conv_t3_mxfp8_ok",
     "vcx_groupnorm_apply2_mxfp8_f16", "vcx_conv3x3_mxfp8", "vcx_conv3x3_mxfp8_ok",
+    "vcx_groupnorm_apply_mxfp8_raw_f16", "vcx_groupnorm_apply2_mxfp8_raw_f16", "vcx_conv3x3_tail_mxfp8", "vcx_conv3x3_tail_mxfp8_ok",
     "vcx_groupnorm_ws_bytes", "vcx_groupnorm_stats_f16", "vcx_groupnorm_apply_f16", "vcx_groupnorm_apply2_f16", "vcx_groupnorm_stats_from_colstats_f32", "vcx_groupnorm_fold_linear_f16", "vcx_layernorm_f16", "vcx_rowstats_f16",
     "vcx_attn_flash_d64_f16", "vcx_attn_flash_d512_f16", "vcx_attn_flash_dual_d64_f16", "vcx_attn_temporal_d64_f16", "vcx_attn_temporal_d64_masked_f16", "vcx_attn_temporal_d64_rel_f16",
     "vcx_attn_temporal_d64_mxfp8", "vcx_attn_temporal_d64_mxfp8_ok", "vcx_attn_flash_d64_mxfp8", "vcx_attn_flash_d64_mxfp8_ok",
@@ -99,6 +100,13 @@ def lib():
     L.vcx_conv3x3_mxfp8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                     c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]
     L.vcx_conv3x3_mxfp8_ok.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int]
+    L.vcx_groupnorm_apply_mxfp8_raw_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
+                                                    c_float, c_int, c_void_p]
+    L.vcx_groupnorm_apply2_mxfp8_raw_f16.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                                     c_int, c_int, c_float, c_int, c_void_p]
+    L.vcx_conv3x3_tail_mxfp8.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                         c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]
+    L.vcx_conv3x3_tail_mxfp8_ok.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int]
     L.vcx_groupnorm_ws_bytes.argtypes = [c_int, c_int64, c_int]
     L.vcx_groupnorm_stats_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]
     L.vcx_groupnorm_apply_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,

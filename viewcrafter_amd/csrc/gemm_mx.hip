@@ -40,6 +40,13 @@
 // (m / W) % H and m % W when a tile's offsets are set up; 5 rows x 6 bits in the register T3 uses 15 bits of), a tap is valid iff both of
 // its bits are set, and its offset is one add and one select at issue.  A missing source row gets an out-of-range offset: no read of the
 // neighbouring frame, no wrap to the previous image row at x = 0 or the next one at x = W - 1, no negative offset at m < W + 1.
+//
+// vcx_conv3x3_tail_mxfp8 (GM = 2, TAIL): the second convolution of a ResBlock with its 1x1 skip convolution as a LINEAR K TAIL.  After the
+// 9 Kp(Cin) / 128 gathered K-steps of a tile, Kp(Ct) / 128 further K-steps read row m ITSELF of a second MXFP8 source t [M][Kp(Ct)] (the
+// quantised block input, written by the raw quantising GroupNorm apply) through descriptors of its own: no tap, no validity bits beyond
+// m < M (a tail row exists for every row, wherever it sits in its frame), rows beyond M out of range.  The weight rows are
+// [9 Kp(Cin) main | Kp(Ct) tail] (packing.pack_conv3x3_tail_mxfp8), linear in K like every weight side: main and tail are quantised and
+// padded on their own, no MX block and no K-step straddles them.  One K order - main steps, then tail steps ascending - in both tile shapes.
 #include "gemm_epilogue.h"
 #include "mx_format.h"
 
@@ -73,6 +80,11 @@ struct MxArgs {
     int GH, GW;
     const float* rowadd;
     int rowadd_ld, rowadd_div;
+    // vcx_conv3x3_tail_mxfp8: the linear tail source [M][kpt] / [M][kpt / 32] (the weight's row pitch is 9 kp + kpt)
+    const unsigned char* Tl;
+    const unsigned char* Tls;
+    int kpt;
+    unsigned t_bytes, ts_bytes;
     float* colstats;                  // VCX_GEMM_COLSTATS: (mean, M2) per 64-row strip and output column (gemm_epilogue.h, LNF = 3)
     int64_t ldcs;
 };
@@ -168,11 +180,12 @@ __device__ __forceinline__ void mx_geglu_epilogue(const MxArgs& p, f4 (&acc)[Cfg
 
 // EPI: 0 = bias / residual, fp16 out (gemm_epilogue.h, the fp16 engine's epilogue); 1 = GEGLU, fp16 out; 2 = GEGLU, MXFP8 out;
 // 3 = EPI 0 + column moments of the output (VCX_GEMM_COLSTATS).  GM, the gather mode of the activation operand: 0 = linear, 1 = the temporal
-// 3-tap convolution, 2 = the spatial 3x3 convolution (file header).
-template <class Cfg, int EPI, int GM = 0>
+// 3-tap convolution, 2 = the spatial 3x3 convolution (file header).  TAIL (GM = 2 only): linear K-steps of a second source behind the gathered ones.
+template <class Cfg, int EPI, int GM = 0, bool TAIL = false>
 __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool T3 = GM == 1, C9 = GM == 2, GATHER = GM != 0;
+    static_assert(!TAIL || (C9 && (EPI == 0 || EPI == 3)), "the K tail belongs to the 3x3 gather, plain and column-moment epilogues");
     constexpr int VB = C9 ? 6 : 3;      // validity bits per DMA row
     constexpr int TBM = Cfg::TBM, TBN = Cfg::TBN, NFRAG = Cfg::NF, MFRAG = Cfg::MF;
     constexpr int XROWS = Cfg::XROWS, WROWS = Cfg::WROWS, RSTEP = Cfg::RSTEP;
@@ -186,6 +199,11 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
     const __amdgpu_buffer_rsrc_t srd_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.W), 0, (int)p.w_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t srd_as = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.As), 0, (int)p.as_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t srd_ws = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.Ws), 0, (int)p.ws_bytes, 0x00020000);
+
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t srd_t =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(TAIL ? p.Tl : p.A), 0, TAIL ? (int)p.t_bytes : 0, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t srd_ts =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(TAIL ? p.Tls : p.As), 0, TAIL ? (int)p.ts_bytes : 0, 0x00020000);
 
     const int ntiles = p.tiles_m * p.tiles_n;
     const int G = gridDim.x;
@@ -216,10 +234,14 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             return 2u | (t > 0u ? 1u : 0u) | (t + 1u < (unsigned)p.T ? 4u : 0u);
         }
     };
-    const unsigned wpitch = (unsigned)(C9 ? 9 * p.kp : T3 ? 3 * p.kp : p.kp);      // bytes of a weight row
+    const unsigned wpitch = (unsigned)(C9 ? 9 * p.kp + (TAIL ? p.kpt : 0) : T3 ? 3 * p.kp : p.kp);      // bytes of a weight row
+    // TAIL: first row of the load tile.  The tail offsets of a DMA row are recomputed from it at issue (one multiply per row and tail step,
+    // no second set of row offsets); whether the row is below M is the centre bit of its tap bits.
+    [[maybe_unused]] int lrow0 = 0;
     auto init_load = [&](int t) {
         int tile_m, tile_n;
         tile_coords(t, ntiles, p.tiles_n, tile_m, tile_n);
+        if constexpr (TAIL) lrow0 = tile_m * TBM;
 #pragma unroll
         for (int i = 0; i < XROWS; ++i) {
             const int r = r0 + RSTEP * i;
@@ -274,11 +296,22 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
             if constexpr (C9) return ((vbits >> (VB * i + ky)) & (vbits >> (VB * i + 3 + kx)) & 1u) != 0u;
             else return ((vbits >> (VB * i + tap)) & 1u) != 0u;
         };
+        [[maybe_unused]] const int jt = kt - 9 * nk_tap;      // TAIL: K-step of the tail once the nine taps of every slab are through (uniform)
+        if (TAIL && jt >= 0) {
 #pragma unroll
-        for (int i = 0; i < XROWS; ++i) {
-            unsigned vo = xoff[i];
-            if constexpr (GATHER) vo = valid(i) ? vo + shift : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_a, (lds_ptr_t)(dx + RSTEP * i * KSTEP), 16, vo, soff_x, 0, 0);
+            for (int i = 0; i < XROWS; ++i) {
+                const int r = r0 + RSTEP * i;
+                const unsigned csrc = (unsigned)(chunk ^ ((r >> 1) & 7)) * 16u;
+                const unsigned vo = ((vbits >> (VB * i + 1)) & 1u) ? (unsigned)(lrow0 + r) * (unsigned)p.kpt + csrc : OOB;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_t, (lds_ptr_t)(dx + RSTEP * i * KSTEP), 16, vo, (unsigned)jt * KSTEP, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < XROWS; ++i) {
+                unsigned vo = xoff[i];
+                if constexpr (GATHER) vo = valid(i) ? vo + shift : OOB;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_a, (lds_ptr_t)(dx + RSTEP * i * KSTEP), 16, vo, soff_x, 0, 0);
+            }
         }
 #pragma unroll
         for (int i = 0; i < WROWS; ++i)
@@ -286,7 +319,10 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
         // the K-step's four scale bytes of every tile row: one dword per thread, lane-linear behind the wave's base
         unsigned* ds = sS + buf * SROWS + wave * 64;
         if constexpr (GATHER) {
-            if (scale_is_a) {
+            if (scale_is_a && TAIL && jt >= 0) {
+                const unsigned vo = ((vbits >> (VB * XROWS + 1)) & 1u) ? (unsigned)(lrow0 + tid) * (unsigned)(p.kpt >> 5) : OOB;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_ts, (lds_ptr_t)ds, 4, vo, (unsigned)jt * 4u, 0, 0);
+            } else if (scale_is_a) {
                 const unsigned vo = valid(XROWS) ? soff_v + sshift : OOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_as, (lds_ptr_t)ds, 4, vo, (unsigned)kk * 4u, 0, 0);
             } else {
@@ -309,7 +345,7 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #pragma unroll
         for (int b = 0; b < MFRAG; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = C9 ? 9 * nk_tap : T3 ? 3 * nk_tap : p.kp / KSTEP;
+    const int nk = C9 ? 9 * nk_tap + (TAIL ? p.kpt / KSTEP : 0) : T3 ? 3 * nk_tap : p.kp / KSTEP;
     [[maybe_unused]] int ltap = 0, lkk = 0;      // T3: tap and K-step inside the tap of the load side's lkt; C9: tap and slab
     int ltile = blockIdx.x, lkt = 0;
     int ctile = blockIdx.x, ckt = 0;
@@ -331,7 +367,7 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
                 lkk = 0;
                 ++ltap;
             }
-        } else if constexpr (C9) {
+        } else if constexpr (C9) {      // (TAIL: past the slabs tap and slab go on counting unused - a tail step is lkt - 9 nk_tap)
             if (++ltap == 9) {
                 ltap = 0;
                 ++lkk;
@@ -420,11 +456,11 @@ __global__ void __launch_bounds__(Cfg::THREADS, 2) gemm_mx_kernel(MxArgs p) {
 #endif
 }
 
-template <class Cfg, int EPI, int GM = 0>
+template <class Cfg, int EPI, int GM = 0, bool TAIL = false>
 int launch_mx(const MxArgs& a, hipStream_t s) {
     static VcxLdsAttr lds;
-    auto kern = gemm_mx_kernel<Cfg, EPI, GM>;
-    const char* name = GM == 2 ? "vcx_conv3x3_mxfp8" : GM == 1 ? "vcx_conv_t3_mxfp8" : "vcx_gemm_mxfp8";
+    auto kern = gemm_mx_kernel<Cfg, EPI, GM, TAIL>;
+    const char* name = TAIL ? "vcx_conv3x3_tail_mxfp8" : GM == 2 ? "vcx_conv3x3_mxfp8" : GM == 1 ? "vcx_conv_t3_mxfp8" : "vcx_gemm_mxfp8";
     if (!lds.ensure(reinterpret_cast<const void*>(kern), (int)Cfg::SMEM, name)) return VCX_ELAUNCH;
     const int nb = persistent_grid(a.tiles_m * a.tiles_n, 2);
     hipLaunchKernelGGL(kern, dim3(nb), dim3(Cfg::THREADS), Cfg::SMEM, s, a);
@@ -520,6 +556,21 @@ bool c9_takes(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int flags
     return true;
 }
 
+// vcx_conv3x3_tail_mxfp8: c9_takes' rules for the gathered part with the flags the tailed form has (bias required, COLSTATS optional; a
+// residual or a row addend is refused: the second convolution of a skip-convolution block has neither), plus the tail's own
+bool c9t_takes(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Ct, int64_t N, int flags, int64_t ldc, int64_t ldcs, int64_t cs_col, const char** why) {
+    *why = "flags: BIAS_N, optionally with COLSTATS (no RESIDUAL, no ROWADD on the tailed form)";
+    if (!(flags & VCX_GEMM_BIAS_N) || (flags & ~(VCX_GEMM_BIAS_N | VCX_GEMM_COLSTATS))) return false;
+    if (!c9_takes(n, H, W, Cin, N, flags, ldc, 0, ldcs, cs_col, 1, why)) return false;
+    *why = "need Ct > 0, Ct % 32 == 0, Ct < 2^31";
+    if (Ct <= 0 || Ct % MX_BLOCK != 0 || Ct >= (1ll << 31)) return false;
+    // 32-bit buffer offsets: the tail source reaches 127 rows past M, the weight rows are 9 Kp(Cin) + Kp(Ct) long and reach 127 rows past N
+    const unsigned long long M = (unsigned long long)(n * H * W), kp = (unsigned long long)mx_kp(Cin), kpt = (unsigned long long)mx_kp(Ct);
+    *why = "a tail or weight extent of 4 GiB or more (32-bit buffer offsets; tail: (M + 127) Kp(Ct), weights: (N + 127) (9 Kp(Cin) + Kp(Ct)))";
+    if ((M + 127) * kpt >= LIM || ((unsigned long long)N + 127) * (9 * kp + kpt) >= LIM) return false;
+    return true;
+}
+
 // The tile configuration of a call: 0 = Cfg128, 1 = Cfg160 (include/vcx.h vcx_gemm_mxfp8_cfg).  A function of N, the flag word and the gather
 // mode - never of M: a row's configuration cannot depend on the batch.  Cfg160 has the plain and the column-moment epilogue only.
 int mx_cfg_of(int64_t N, int flags, int gm) {
@@ -612,6 +663,66 @@ extern "C" int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void
     VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * 9.0 * Cin, (double)(M + 9 * N) * p.kp + 2.0 * M * N);
     if (flags & VCX_GEMM_COLSTATS) return cfg ? launch_mx<Cfg160, 3, 2>(p, s) : launch_mx<Cfg128, 3, 2>(p, s);
     return cfg ? launch_mx<Cfg160, 0, 2>(p, s) : launch_mx<Cfg128, 0, 2>(p, s);
+}
+
+extern "C" int vcx_conv3x3_tail_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Ct, int64_t N, int64_t ldc, int64_t ldcs, int64_t colstats_col,
+                                         int flags) {
+    const char* why;
+    if (c9t_takes(n, H, W, Cin, Ct, N, flags, ldc, ldcs, colstats_col, &why)) return 1;
+    vcx_set_error("vcx_conv3x3_tail_mxfp8_ok(n=%lld, H=%lld, W=%lld, Cin=%lld, Ct=%lld, N=%lld, ldc=%lld, ldcs=%lld, col=%lld, flags=0x%x): %s", (long long)n,
+                  (long long)H, (long long)W, (long long)Cin, (long long)Ct, (long long)N, (long long)ldc, (long long)ldcs, (long long)colstats_col, flags, why);
+    return 0;
+}
+
+extern "C" int vcx_conv3x3_tail_mxfp8(const void* a, const void* a_scales, const void* t, const void* t_scales, const void* w, const void* w_scales, void* out,
+                                      const float* bias, float* colstats, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Ct, int64_t N, int64_t ldc,
+                                      int64_t ldcs, int flags, void* stream) {
+    VCX_REQUIRE(a && a_scales && t && t_scales && w && w_scales && out && bias, "vcx_conv3x3_tail_mxfp8: null pointer");
+    VCX_REQUIRE(!(flags & VCX_GEMM_COLSTATS) || colstats, "vcx_conv3x3_tail_mxfp8: VCX_GEMM_COLSTATS needs a colstats buffer");
+    const char* why;
+    // (the moments' first column is in the pointer: its parity shows in the pointer's alignment, checked below)
+    VCX_REQUIRE(c9t_takes(n, H, W, Cin, Ct, N, flags, ldc, ldcs, 0, &why),
+                "vcx_conv3x3_tail_mxfp8(n=%lld, H=%lld, W=%lld, Cin=%lld, Ct=%lld, N=%lld, flags=0x%x, ldc=%lld, ldcs=%lld): %s", (long long)n, (long long)H,
+                (long long)W, (long long)Cin, (long long)Ct, (long long)N, flags, (long long)ldc, (long long)ldcs, why);
+    VCX_REQUIRE((((uintptr_t)a | (uintptr_t)t | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)colstats) & 15) == 0
+                    && (((uintptr_t)a_scales | (uintptr_t)t_scales | (uintptr_t)w_scales) & 3) == 0,
+                "vcx_conv3x3_tail_mxfp8: operands, output, bias and colstats must be 16-byte aligned, scale arrays 4-byte aligned");
+    const int64_t M = n * H * W;
+    MxArgs p{};
+    p.A = (const unsigned char*)a;
+    p.As = (const unsigned char*)a_scales;
+    p.Tl = (const unsigned char*)t;
+    p.Tls = (const unsigned char*)t_scales;
+    p.W = (const unsigned char*)w;
+    p.Ws = (const unsigned char*)w_scales;
+    p.C = out;
+    p.bias = bias;
+    p.M = (int)M;
+    p.N = (int)N;
+    p.kp = (int)mx_kp(Cin);
+    p.kpt = (int)mx_kp(Ct);
+    p.GH = (int)H;
+    p.GW = (int)W;
+    p.rowadd_div = 1;
+    p.ldc = (int)ldc;
+    p.flags = flags;
+    p.colstats = colstats;
+    p.ldcs = ldcs;
+    const int64_t wrow = 9ll * p.kp + p.kpt;      // bytes of a weight row
+    const int cfg = mx_cfg_launch(N, flags, 2, (unsigned long long)wrow);
+    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
+    p.tiles_n = (int)((N + (cfg ? Cfg160::TBN : Cfg128::TBN) - 1) / (cfg ? Cfg160::TBN : Cfg128::TBN));
+    p.a_bytes = (unsigned)(M * p.kp);
+    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
+    p.t_bytes = (unsigned)(M * p.kpt);
+    p.ts_bytes = (unsigned)(M * (p.kpt / MX_BLOCK));
+    p.w_bytes = (unsigned)(N * wrow);
+    p.ws_bytes = (unsigned)(N * (wrow / MX_BLOCK));
+    p.c_bytes = (unsigned)(2 * ((M - 1) * ldc + N));
+    hipStream_t s = (hipStream_t)stream;
+    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * (9.0 * Cin + Ct), (double)(M + N) * (double)wrow - 8.0 * M * p.kp + 2.0 * M * N);
+    if (flags & VCX_GEMM_COLSTATS) return cfg ? launch_mx<Cfg160, 3, 2, true>(p, s) : launch_mx<Cfg128, 3, 2, true>(p, s);
+    return cfg ? launch_mx<Cfg160, 0, 2, true>(p, s) : launch_mx<Cfg128, 0, 2, true>(p, s);
 }
 
 extern "C" int vcx_conv_t3_mxfp8_ok(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,

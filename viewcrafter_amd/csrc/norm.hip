@@ -254,8 +254,12 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ x, const half_t* __re
 // x2 != nullptr (vcx_groupnorm_apply2_mxfp8_f16): gn_apply_kernel's two-source addressing of a channel concat [x | x2] that is never
 // materialised (c1 % 8 == 0: a thread's chunk lies in one half; an MX block may straddle the halves - the quad maximum does not care
 // where its four chunks were read).
+// RAW (vcx_groupnorm_apply_mxfp8_raw_f16 / vcx_groupnorm_apply2_mxfp8_raw_f16): a second output (rq, rs) = vcx_quant_mxfp8_f16 of the loaded
+// rows themselves - for two sources the quantised channel concat, the dense MXFP8 image a skip convolution reads as the K tail of
+// vcx_conv3x3_tail_mxfp8 - from the same registers: a second quad maximum on the values before normalisation, padding as the first output's.
+template <bool RAW>
 __global__ void gn_apply_mx_kernel(const half_t* __restrict__ x, const half_t* __restrict__ x2, int c1, unsigned char* __restrict__ qo, unsigned char* __restrict__ so,
-                                   const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta, int64_t pixels,
+                                   [[maybe_unused]] unsigned char* __restrict__ rqo, [[maybe_unused]] unsigned char* __restrict__ rso, const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta, int64_t pixels,
                                    int C, int kp, int groups, float eps, int silu, int64_t pix_per_block, int cw, int pl) {
     using namespace vcxmx;
     const int tid = threadIdx.x;
@@ -285,6 +289,20 @@ __global__ void gn_apply_mx_kernel(const half_t* __restrict__ x, const half_t* _
     }
     const int kc = kp >> 3, ks = kp >> 5;       // chunks and scale bytes of a padded row
     auto emit = [&](h8 v, int64_t pix) {
+        const int64_t row = (int64_t)n * pixels + pix;
+        if constexpr (RAW) {
+            const unsigned rmax = mx_quad_max(mx_absmax_bits(v));
+            float rmul;
+            const unsigned rsb = mx_scale_byte(rmax, rmul);
+            unsigned char* qr = rqo + row * kp;
+            unsigned char* sr = rso + row * ks;
+            *reinterpret_cast<uint2*>(qr + c8 * 8) = mx_quant8(v, rsb, rmul);
+            if ((c8 & 3) == 0) sr[c8 >> 2] = (unsigned char)rsb;
+            for (int c = cw + c8; c < kc; c += cw) {
+                *reinterpret_cast<uint2*>(qr + c * 8) = make_uint2(0u, 0u);
+                if ((c & 3) == 0) sr[c >> 2] = (unsigned char)MX_SCALE_ONE;
+            }
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float f = __builtin_fmaf((float)v[e] - mn[e], sc[e], bt[e]);
@@ -294,7 +312,6 @@ __global__ void gn_apply_mx_kernel(const half_t* __restrict__ x, const half_t* _
         const unsigned hmax = mx_quad_max(mx_absmax_bits(v));
         float mul;
         const unsigned sb = mx_scale_byte(hmax, mul);
-        const int64_t row = (int64_t)n * pixels + pix;
         unsigned char* qr = qo + row * kp;
         unsigned char* sr = so + row * ks;
         *reinterpret_cast<uint2*>(qr + c8 * 8) = mx_quant8(v, sb, mul);
@@ -756,9 +773,11 @@ extern "C" int vcx_groupnorm_apply2_f16(const void* x1, int c1, const void* x2, 
     return gn_apply_launch(x1, x2, c1, y, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
 }
 
-static int gn_apply_mx_launch(const void* x, const void* x2, int c1, void* q, void* scales, const float* stats, const float* gamma, const float* beta,
-                              int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
+// rq / rscales: the raw second output of the _raw entry points (both or neither)
+static int gn_apply_mx_launch(const void* x, const void* x2, int c1, void* q, void* scales, void* rq, void* rscales, const float* stats, const float* gamma,
+                              const float* beta, int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
     VCX_REQUIRE(x && q && scales && stats && gamma && beta, "vcx_groupnorm_apply_mxfp8_f16: null pointer");
+    VCX_REQUIRE(((uintptr_t)rq & 15) == 0 && ((uintptr_t)rscales & 3) == 0, "vcx_groupnorm_apply_mxfp8_raw_f16: rq must be 16-byte aligned, rscales 4-byte aligned");
     VCX_REQUIRE(n_outer > 0 && pixels > 0 && C > 0 && C <= MAXC && groups > 0 && C % groups == 0 && C % 32 == 0,
                 "vcx_groupnorm_apply_mxfp8_f16: need C %% 32 == 0, C %% groups == 0, C <= %d (C=%d groups=%d)", MAXC, C, groups);
     VCX_REQUIRE((((uintptr_t)x | (uintptr_t)q) & 15) == 0 && ((uintptr_t)scales & 3) == 0,
@@ -771,21 +790,40 @@ static int gn_apply_mx_launch(const void* x, const void* x2, int c1, void* q, vo
     dim3 grid((unsigned)((pixels + ppb - 1) / ppb), n_outer);
     int cw, pl;
     gn_geometry(C, cw, pl);
-    hipLaunchKernelGGL(gn_apply_mx_kernel, grid, dim3(cw * pl), 0, s, (const half_t*)x, (const half_t*)x2, c1, (unsigned char*)q, (unsigned char*)scales, stats, gamma, beta,
-                       pixels, C, kp, groups, eps, silu, ppb, cw, pl);
-    return vcx_check_launch("vcx_groupnorm_apply_mxfp8_f16");
+    if (rq)
+        hipLaunchKernelGGL(gn_apply_mx_kernel<true>, grid, dim3(cw * pl), 0, s, (const half_t*)x, (const half_t*)x2, c1, (unsigned char*)q, (unsigned char*)scales,
+                           (unsigned char*)rq, (unsigned char*)rscales, stats, gamma, beta, pixels, C, kp, groups, eps, silu, ppb, cw, pl);
+    else
+        hipLaunchKernelGGL(gn_apply_mx_kernel<false>, grid, dim3(cw * pl), 0, s, (const half_t*)x, (const half_t*)x2, c1, (unsigned char*)q, (unsigned char*)scales,
+                           nullptr, nullptr, stats, gamma, beta, pixels, C, kp, groups, eps, silu, ppb, cw, pl);
+    return vcx_check_launch(rq ? "vcx_groupnorm_apply_mxfp8_raw_f16" : "vcx_groupnorm_apply_mxfp8_f16");
 }
 
 extern "C" int vcx_groupnorm_apply_mxfp8_f16(const void* x, void* q, void* scales, const float* stats, const float* gamma, const float* beta,
                                              int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
-    return gn_apply_mx_launch(x, nullptr, 0, q, scales, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
+    return gn_apply_mx_launch(x, nullptr, 0, q, scales, nullptr, nullptr, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
 }
 
 extern "C" int vcx_groupnorm_apply2_mxfp8_f16(const void* x1, int c1, const void* x2, void* q, void* scales, const float* stats, const float* gamma,
                                               const float* beta, int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
     VCX_REQUIRE(x2 && c1 > 0 && c1 < C && c1 % 8 == 0 && ((uintptr_t)x2 & 15) == 0,
                 "vcx_groupnorm_apply2_mxfp8_f16: need 0 < c1 < C, c1 %% 8 == 0, x2 16-byte aligned (c1=%d C=%d)", c1, C);
-    return gn_apply_mx_launch(x1, x2, c1, q, scales, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
+    return gn_apply_mx_launch(x1, x2, c1, q, scales, nullptr, nullptr, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
+}
+
+extern "C" int vcx_groupnorm_apply_mxfp8_raw_f16(const void* x, void* q, void* scales, void* rq, void* rscales, const float* stats, const float* gamma,
+                                                 const float* beta, int n_outer, int64_t pixels, int C, int groups, float eps, int silu, void* stream) {
+    VCX_REQUIRE(rq && rscales, "vcx_groupnorm_apply_mxfp8_raw_f16: null pointer");
+    return gn_apply_mx_launch(x, nullptr, 0, q, scales, rq, rscales, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
+}
+
+extern "C" int vcx_groupnorm_apply2_mxfp8_raw_f16(const void* x1, int c1, const void* x2, void* q, void* scales, void* rq, void* rscales, const float* stats,
+                                                  const float* gamma, const float* beta, int n_outer, int64_t pixels, int C, int groups, float eps, int silu,
+                                                  void* stream) {
+    VCX_REQUIRE(rq && rscales, "vcx_groupnorm_apply2_mxfp8_raw_f16: null pointer");
+    VCX_REQUIRE(x2 && c1 > 0 && c1 < C && c1 % 8 == 0 && ((uintptr_t)x2 & 15) == 0,
+                "vcx_groupnorm_apply2_mxfp8_raw_f16: need 0 < c1 < C, c1 %% 8 == 0, x2 16-byte aligned (c1=%d C=%d)", c1, C);
+    return gn_apply_mx_launch(x1, x2, c1, q, scales, rq, rscales, stats, gamma, beta, n_outer, pixels, C, groups, eps, silu, stream);
 }
 
 extern "C" int vcx_groupnorm_fold_linear_f16(const float* W, const float* bias, const float* gamma, const float* beta, const float* stats,

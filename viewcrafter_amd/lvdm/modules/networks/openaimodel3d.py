@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from .... import ops
-from ....packing import pack_conv, pack_conv3x3_mxfp8, pack_conv_t3_mxfp8, pack_conv_ups_folded
+from ....packing import pack_conv, pack_conv3x3_mxfp8, pack_conv3x3_tail_mxfp8, pack_conv_t3_mxfp8, pack_conv_ups_folded
 from ..attention import PackedModule, SpatialTransformer, TemporalTransformer, _f16, _f32
 from ..flow import CAT_SPLIT, GN_EPILOGUE_STATS, GN_STATS_LEVEL, CatTarget, Flow, out_kwargs as _out_kwargs
 
@@ -50,6 +50,13 @@ RESCONV_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_RESCONV_
 # first one is MX; 0 (default: the faster one in the isolated A/B, 1.22x / 1.29x against 1.06x / 1.11x, profiles/mxfp8_resconv.md) = the
 # second one is MX too and takes the separate fp16 skip convolution's result as its residual.
 RESCONV_MXFP8_KEEP_FOLD = os.environ.get("VCX_RESCONV_MXFP8_KEEP_FOLD", "0") == "1"
+# Opt-in (VCX_RESCONV_MXFP8_TAIL=1, default off; consulted only where VCX_RESCONV_MXFP8=1 is on, and VCX_RESCONV_MXFP8_KEEP_FOLD=1 wins over
+# it): a block with a 1x1 skip convolution - the split-concat blocks of the up path included - runs the skip as a linear K tail of its MX
+# second convolution (vcx_conv3x3_tail_mxfp8).  The quantising GroupNorm apply in front of the first convolution writes quant(x) beside
+# quant(SiLU(GN(x))) (vcx_groupnorm_apply(2)_mxfp8_raw_f16): a dense MXFP8 image of the block input, of the concat where the input is one, so
+# the tail has one source - no fp16 skip launch, no residual, no fp16 concat.  What was measured is in profiles/mxfp8_resconv_tail.md.  Off: no
+# new launch, no new allocation, every output bit as before.
+RESCONV_MXFP8_TAIL = os.environ.get("VCX_RESCONV_MXFP8_TAIL", "0") == "1"
 
 class TimestepBlock(nn.Module):
     """Marker: modules whose forward takes the timestep embedding (reference openaimodel3d.py:19-28)."""
@@ -354,6 +361,12 @@ class ResBlock(PackedModule, TimestepBlock):
                 self._mx[name] = tuple(t.to(device) for t in pack_conv3x3_mxfp8(conv.weight.detach()))
         return self._mx[name]
 
+    def _mx_tail_weight(self, device):
+        if "w2s" not in self._mx:
+            with torch.no_grad():
+                self._mx["w2s"] = tuple(t.to(device) for t in pack_conv3x3_tail_mxfp8(self.out_layers[3].weight.detach(), self.skip_connection.weight.detach()))
+        return self._mx["w2s"]
+
     def _forward_mx(self, x, emb, batch_size, want_colstats, colstats, target, x2):
         """RESCONV_MXFP8: the block with one or both 3x3 convolutions on the MX route, or None - the block stays on the fp16 route,
         nothing launched - where the library's predicate takes neither.  Each convolution is decided on its own, asked about ONE
@@ -362,7 +375,10 @@ class ResBlock(PackedModule, TimestepBlock):
         for where the host graph's rule allows them: whole 64-row strips per statistics unit.  A block with a skip convolution keeps
         its second convolution on the fp16 engine with the folded K tail under RESCONV_MXFP8_KEEP_FOLD, and wherever the skip's input
         is a split concat read in place (the K tail takes two sources, a separate skip convolution does not); otherwise the second
-        convolution is MX with the fp16 skip convolution's result as its residual."""
+        convolution is MX with the fp16 skip convolution's result as its residual.  RESCONV_MXFP8_TAIL (KEEP_FOLD off): a block with a
+        skip convolution whose first convolution is MX and whose tailed second convolution the library takes with the call's keywords
+        runs the skip as the K tail of the MX second convolution, fed by the raw output of the quantising apply in front of the first -
+        over both halves where the concat is read in place; decided, like everything here, before anything is launched."""
         n, H, W, c1 = x.shape
         cin = c1 + (0 if x2 is None else x2.shape[-1])
         cout = self.out_channels
@@ -389,13 +405,19 @@ class ResBlock(PackedModule, TimestepBlock):
         mx2 = (not has_skip or (not RESCONV_MXFP8_KEEP_FOLD and not inplace)) and all(
             ops.conv3x3_mxfp8_ok(f, H, W, cout, cout, residual=True, ldr=cout, ldc=kw2.get("ldc"), colstats="colstats" in kw2,
                                  colstats_ld=kw2.get("colstats_ld"), colstats_col=kw2.get("colstats_col", 0)) for f in frames)
+        tail = RESCONV_MXFP8_TAIL and has_skip and not RESCONV_MXFP8_KEEP_FOLD and mx1 and all(
+            ops.conv3x3_tail_mxfp8_ok(f, H, W, cout, cin, cout, ldc=kw2.get("ldc"), colstats="colstats" in kw2, colstats_ld=kw2.get("colstats_ld"),
+                                      colstats_col=kw2.get("colstats_col", 0)) for f in frames)
         if not (mx1 or mx2):
             return None
         if x2 is not None and not inplace:
             x, x2 = ops.concat_channels(x.reshape(M, c1), x2.reshape(M, cin - c1)).view(n, H, W, -1), None      # the materialised concat
         stats_in = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, H * W, cin)
         xin, x2in = x.view(n, H * W, -1), None if x2 is None else x2.view(n, H * W, -1)
-        a = (ops.group_norm_mxfp8 if mx1 else ops.group_norm)(xin, *pk["g1"], True, stats=stats_in, x2=x2in)
+        if tail:
+            a, xq = ops.group_norm_mxfp8_raw(xin, *pk["g1"], True, stats=stats_in, x2=x2in)
+        else:
+            a = (ops.group_norm_mxfp8 if mx1 else ops.group_norm)(xin, *pk["g1"], True, stats=stats_in, x2=x2in)
         emb_out = self._emb_all[:B] if self._emb_all is not None else ops.linear(emb, pk["we"], pk["be"], out_f32=True)
         if mx1:
             cs1 = ops.colstats_buffer(M, cout, x.device) if cs1_mx else None
@@ -405,7 +427,14 @@ class ResBlock(PackedModule, TimestepBlock):
             cs1 = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and ops.colstats_ok(M, H * W, cin, cout, in_rows=M)) else None
             h = ops.conv2d(a.view(n, H, W, cin), pk["w1"], pk["b1"], kh=3, kw=3, rowadd=emb_out, rowadd_div=fpv * H * W, colstats=cs1)
         stats = None if cs1 is None else ops.group_norm_stats_from_colstats(cs1, n, H * W, cout)
-        if mx2:
+        if tail:
+            a = ops.group_norm_mxfp8(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
+            kw2 = dict(kw2)
+            if kw2.get("colstats") is True:
+                kw2["colstats"] = ops.colstats_buffer(M, cout, x.device)
+            cs_out = kw2.get("colstats")
+            h = ops.conv3x3_tail_mxfp8(a, tail=xq, w=self._mx_tail_weight(x.device), bias=pk["b2s"], n=n, H=H, W=W, cin=cout, ct=cin, **kw2)
+        elif mx2:
             a = ops.group_norm_mxfp8(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
             residual = ops.conv2d(x, pk["ws"], pk["bs"], kh=1, kw=1).view(M, cout) if has_skip else x.reshape(M, cout)
             kw2 = dict(kw2)

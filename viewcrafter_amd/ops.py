@@ -605,6 +605,38 @@ def _group_norm2_mxfp8(x1, x2, gamma, beta, eps, silu, groups, stats):
     return q, sc
 
 
+def group_norm_mxfp8_raw(x, gamma, beta, eps, silu, groups=32, stats=None, x2=None):
+    """group_norm_mxfp8 with a second, raw output from the same pass: -> ((q, scales), (rq, rscales)), the first pair byte for byte
+    group_norm_mxfp8's, the second byte for byte quant_mxfp8 of the input rows themselves - with x2 of the channel concat [x | x2], which is
+    never materialised (vcx_groupnorm_apply_mxfp8_raw_f16 / vcx_groupnorm_apply2_mxfp8_raw_f16).  The raw pair is the tail operand of
+    conv3x3_tail_mxfp8.  Arguments as group_norm_mxfp8 (`stats` required with x2)."""
+    n_outer, pixels, c1 = x.shape
+    C = c1 + (0 if x2 is None else x2.shape[2])
+    _dev16(x, x2)
+    _dev32(gamma, beta, stats)
+    if not x.is_contiguous():
+        raise VcxError("group_norm_mxfp8_raw: a contiguous [n_outer, pixels, C] tensor needed")
+    if x2 is not None and (stats is None or tuple(x2.shape[:2]) != (n_outer, pixels) or c1 % 8 != 0 or C % 32 != 0 or not x2.is_contiguous()):
+        raise VcxError(f"group_norm_mxfp8_raw over a split concat needs statistics, contiguous halves, c1 % 8 == 0 and C % 32 == 0 "
+                       f"(x1 {tuple(x.shape)}, x2 {tuple(x2.shape)})")
+    L = lib()
+    s = _stream()
+    if stats is None:
+        stats = torch.empty((n_outer, groups, 2), dtype=_f32, device=x.device)
+        ws = torch.empty((L.vcx_groupnorm_ws_bytes(n_outer, pixels, groups),), dtype=torch.uint8, device=x.device)
+        check(L.vcx_groupnorm_stats_f16(x.data_ptr(), stats.data_ptr(), ws.data_ptr(), n_outer, pixels, C, groups, s), "groupnorm_stats")
+    q, sc = _mx_buffers(n_outer * pixels, C, x.device)
+    rq, rsc = _mx_buffers(n_outer * pixels, C, x.device)
+    if x2 is None:
+        check(L.vcx_groupnorm_apply_mxfp8_raw_f16(x.data_ptr(), q.data_ptr(), sc.data_ptr(), rq.data_ptr(), rsc.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
+                                                  beta.data_ptr(), n_outer, pixels, C, groups, eps, 1 if silu else 0, s), "groupnorm_apply_mxfp8_raw")
+    else:
+        check(L.vcx_groupnorm_apply2_mxfp8_raw_f16(x.data_ptr(), c1, x2.data_ptr(), q.data_ptr(), sc.data_ptr(), rq.data_ptr(), rsc.data_ptr(), stats.data_ptr(),
+                                                   gamma.data_ptr(), beta.data_ptr(), n_outer, pixels, C, groups, eps, 1 if silu else 0, s),
+              "groupnorm_apply2_mxfp8_raw")
+    return (q, sc), (rq, rsc)
+
+
 def _t3_flags(residual, colstats):
     return GEMM_BIAS_N | (GEMM_RESIDUAL if residual else 0) | (GEMM_COLSTATS if colstats else 0)
 
@@ -718,6 +750,55 @@ def conv3x3_mxfp8(a, w, bias, *, n, H, W, cin, rowadd=None, rowadd_div=0, residu
     check(lib().vcx_conv3x3_mxfp8(a[0].data_ptr(), a[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(), out.data_ptr(), bias.data_ptr(), _ptr(rowadd),
                                   _ptr(residual), cs_ptr, n, H, W, cin, cout, ldc, ldr or 0, cld, rld, rowadd_div if rowadd is not None else 0,
                                   _c9_flags(rowadd is not None, residual is not None, colstats is not None), _stream()), "conv3x3_mxfp8")
+    return out.view(n, H, W, -1)
+
+
+def conv3x3_tail_mxfp8_ok(n, H, W, cin, ct, cout, *, rowadd=False, residual=False, bias=True, ldc=None, colstats=False, colstats_ld=None, colstats_col=0):
+    """Does vcx_conv3x3_tail_mxfp8 take a 3x3 / padding-1 convolution of n frames x H x W pixels x cin channels plus a 1x1 convolution of
+    a ct-channel tail onto cout channels with these keywords (those of conv3x3_tail_mxfp8, `colstats` as a boolean)?  `rowadd` / `residual`
+    / `bias` exist to be asked about: the tailed form refuses a row addend, a residual and a missing bias.  The library's answer - shape,
+    flags, alignment, 32-bit extents; the reason of a refusal is in vcx_last_error()."""
+    ldc = cout if ldc is None else ldc
+    ldcs = (cout if colstats_ld is None else colstats_ld) if colstats else 0
+    flags = _c9_flags(rowadd, residual, colstats) & ~(0 if bias else GEMM_BIAS_N)
+    return lib().vcx_conv3x3_tail_mxfp8_ok(n, H, W, cin, ct, cout, ldc, ldcs, colstats_col if colstats else 0, flags) == 1
+
+
+def conv3x3_tail_mxfp8(a, tail, w, bias, *, n, H, W, cin, ct, out=None, ldc=None, colstats=None, colstats_ld=None, colstats_col=0):
+    """conv3x3_mxfp8 with a 1x1 convolution of a second MXFP8 source as a linear K tail - a ResBlock's second convolution and its skip
+    convolution in one accumulation: a = the pair of the activation [n * H * W, cin], tail = the pair of the block input [n * H * W, ct]
+    (group_norm_mxfp8_raw's second output), w = the pair packing.pack_conv3x3_tail_mxfp8 made of the two weights, bias = the two biases
+    summed.  Returns fp16 [n, H, W, cout] (or [.., ldc] when written into `out`); out / ldc / colstats* as in conv3x3_mxfp8; no rowadd, no
+    residual.  Shapes: conv3x3_tail_mxfp8_ok - a call the kernel does not take is an error here, not a fall-back."""
+    M = n * H * W
+    kw = 9 * mx_kp(cin) + mx_kp(ct)
+    cout = w[0].shape[0]
+    _dev_mx(a, M, cin, "conv3x3_tail_mxfp8 a")
+    _dev_mx(tail, M, ct, "conv3x3_tail_mxfp8 tail")
+    for t, shape in ((w[0], (cout, kw)), (w[1], (cout, kw // 32))):
+        if t.dtype is not _u8 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
+            raise VcxError(f"conv3x3_tail_mxfp8 w: expected contiguous GPU uint8 {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    _dev32(bias)
+    _dev16(out)
+    if bias is None or bias.numel() != cout or not bias.is_contiguous():
+        raise VcxError(f"conv3x3_tail_mxfp8: a contiguous fp32 bias [N = {cout}] is required")
+    if out is None:
+        out = torch.empty((M, cout), dtype=_f16, device=a[0].device)
+        ldc = cout
+    elif ldc is None:
+        ldc = out.stride(0)
+    if out.numel() < (M - 1) * ldc + cout:
+        raise VcxError(f"conv3x3_tail_mxfp8: out holds {out.numel()} elements, [{M}] rows of pitch {ldc} need {(M - 1) * ldc + cout}")
+    cs_ptr, cld = None, 0
+    if colstats is not None:
+        _dev32(colstats)
+        cld = cout if colstats_ld is None else int(colstats_ld)
+        if colstats.numel() != (M // 64) * cld * 2 or colstats_col < 0 or colstats_col + cout > cld:
+            raise VcxError(f"colstats must hold [M / 64, {cld}, 2] floats (M={M}, N={cout}, first column {colstats_col}), got {tuple(colstats.shape)}")
+        cs_ptr = colstats.data_ptr() + 8 * int(colstats_col)
+    check(lib().vcx_conv3x3_tail_mxfp8(a[0].data_ptr(), a[1].data_ptr(), tail[0].data_ptr(), tail[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(),
+                                       out.data_ptr(), bias.data_ptr(), cs_ptr, n, H, W, cin, ct, cout, ldc, cld,
+                                       _c9_flags(False, False, colstats is not None), _stream()), "conv3x3_tail_mxfp8")
     return out.view(n, H, W, -1)
 
 

@@ -148,3 +148,18 @@ def pack_conv3x3_mxfp8(weight):
     q = q.view(cout, 9, slabs, 128).permute(0, 2, 1, 3).reshape(cout, -1).contiguous()
     s = s.view(cout, 9, slabs, 4).permute(0, 2, 1, 3).reshape(cout, -1).contiguous()
     return q, s
+
+
+def pack_conv3x3_tail_mxfp8(weight3x3, weight1x1):
+    """Conv2d weights [Cout, Cin, 3, 3] and [Cout, Ct, 1, 1] (Cin % 32 == 0, Ct % 32 == 0) -> (element bytes uint8 [Cout, 9 Kp(Cin) + Kp(Ct)],
+    scale bytes uint8 [Cout, (9 Kp(Cin) + Kp(Ct)) / 32]): the weight operand of vcx_conv3x3_tail_mxfp8 (include/vcx.h), a ResBlock's second
+    convolution with its 1x1 skip convolution as a linear K tail.  The main columns are exactly pack_conv3x3_mxfp8(weight3x3), the tail
+    columns pack_mxfp8 of the 1x1 weight rounded to fp16: the tail is quantised and padded on its own, so no MX block and no K-step
+    straddles main and tail.  (The two biases are summed by the caller.)"""
+    if weight1x1.dim() != 4 or tuple(weight1x1.shape[2:]) != (1, 1) or weight1x1.shape[1] % 32 != 0:
+        raise ValueError(f"pack_conv3x3_tail_mxfp8: need a Conv2d weight [Cout, Ct, 1, 1] with Ct % 32 == 0 as the tail, got {tuple(weight1x1.shape)}")
+    q, s = pack_conv3x3_mxfp8(weight3x3)
+    if weight1x1.shape[0] != q.shape[0]:
+        raise ValueError(f"pack_conv3x3_tail_mxfp8: {q.shape[0]} output channels in the 3x3 weight, {weight1x1.shape[0]} in the 1x1 weight")
+    tq, ts = pack_mxfp8(weight1x1.detach().reshape(weight1x1.shape[0], -1).to(torch.float16).contiguous())
+    return torch.cat([q, tq.to(q.device)], dim=1).contiguous(), torch.cat([s, ts.to(s.device)], dim=1).contiguous()
