@@ -17,6 +17,9 @@ A variant is  name:key=value,key=value  with keys
     tattnskip widths joined by '+' that keep fp16 with tattn=1 (attention.TATTN_MXFP8_SKIP_DIMS), e.g. tattnskip=320; tattnskip= for none
     sattn    0 | 1   spatial attention on the MXFP8 route (attention.SATTN_MXFP8; off by default)
     sattnskip widths joined by '+' that keep fp16 with sattn=1 (attention.SATTN_MXFP8_SKIP_DIMS), e.g. sattnskip=320; sattnskip= for none
+    kvpool   0 | mean | nearest   spatial self-attention over 2x2-pooled keys and values (attention.SATTN_KV_POOL; off by default), with
+             kvpoolmin = tokens a frame from which a level pools (attention.SATTN_KV_POOL_MIN_TOKENS, default 4096: level 0 of 576x1024 only),
+             e.g.  off:kvpool=0  mean:kvpool=mean  mean2:kvpool=mean,kvpoolmin=2048
     ff / tconv / resconv  0 | 1   the feed-forward pair / TemporalConvBlock / ResBlock convolutions on the MXFP8 route (attention.FF_MXFP8,
              openaimodel3d.TCONV_MXFP8 / RESCONV_MXFP8; off by default), with ffmxskip / tconvskip / resconvskip = widths joined by '+' that keep
              fp16 (the *_SKIP_DIMS lists; `tconvskip=` for none)
@@ -88,6 +91,7 @@ def main():
     default_ffskip = attention.FF_OUT_FOLD_SKIP_DIMS
     default_tattn = attention.TATTN_MXFP8, attention.TATTN_MXFP8_SKIP_DIMS
     default_sattn = attention.SATTN_MXFP8, attention.SATTN_MXFP8_SKIP_DIMS
+    default_kvpool = attention.SATTN_KV_POOL, attention.SATTN_KV_POOL_MIN_TOKENS
 
     mx_switches = {"ff": (attention, "FF_MXFP8", "ffmxskip"), "tconv": (openaimodel3d, "TCONV_MXFP8", "tconvskip"),
                    "resconv": (openaimodel3d, "RESCONV_MXFP8", "resconvskip")}
@@ -120,6 +124,8 @@ def main():
         attention.TATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in settings["tattnskip"].split("+") if v) if "tattnskip" in settings else default_tattn[1]
         attention.SATTN_MXFP8 = settings["sattn"] != "0" if "sattn" in settings else default_sattn[0]
         attention.SATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in settings["sattnskip"].split("+") if v) if "sattnskip" in settings else default_sattn[1]
+        attention.SATTN_KV_POOL = attention._parse_kv_pool(settings["kvpool"]) if "kvpool" in settings else default_kvpool[0]
+        attention.SATTN_KV_POOL_MIN_TOKENS = int(settings["kvpoolmin"]) if "kvpoolmin" in settings else default_kvpool[1]
 
     def run(settings, steps, profile):
         apply(settings)
@@ -145,12 +151,16 @@ def main():
     finals = {}
     for name, st in variants:                        # warm-up of every variant
         run(st, 1, False)
-    for r in range(args.rounds):
-        for name, st in variants:
-            ms, prof, x = run(st, args.steps, True)
-            fam = {k: round(v["ms"] / args.steps, 2) for k, v in prof.items()}
-            print(f"round {r} {name:10s} {ms:8.2f} ms/step  {fam}  launches {sum(v['launches'] for v in prof.values()) // args.steps}", flush=True)
-            finals[name] = x
+    from tools.telemetry import Telemetry
+    with Telemetry(device_index=0, period_s=0.05) as tm:
+        for r in range(args.rounds):
+            for name, st in variants:
+                ms, prof, x = run(st, args.steps, True)
+                fam = {k: round(v["ms"] / args.steps, 2) for k, v in prof.items()}
+                print(f"round {r} {name:10s} {ms:8.2f} ms/step  {fam}  launches {sum(v['launches'] for v in prof.values()) // args.steps}", flush=True)
+                finals[name] = x
+    tel = tm.summary()
+    print("telemetry over the rounds: " + ", ".join(f"{k} {v}" for k, v in tel.items() if k in ("sclk_mhz", "power_w", "source", "samples")), flush=True)
     names = list(finals)
     for n in names[1:]:
         a, b = finals[names[0]].float(), finals[n].float()

@@ -26,6 +26,10 @@ SYMBOLS = [
     "vcx_dpmpp2m_step_f32", "vcx_profile_begin", "vcx_profile_end", "vcx_tune_set", "vcx_tune_get",
 ]
 
+# the additive extension include/vcx_pool.h declares on top of that (tests/test_sattn_kv_pool_cpu.py checks these the same way); the ABI
+# number and vcx.h's own list stay as they are
+EXT_SYMBOLS = ["vcx_layernorm_pool2x2_f16", "vcx_layernorm_pool2x2_ok"]
+
 ABI_VERSION = 18         # include/vcx.h VCX_ABI_VERSION
 # experiment knobs (include/vcx.h VCX_TUNE_*): name -> (index, default)
 TUNE = {"GEMM_CFG": (0, -1), "GEMM_DMA": (1, 1), "FLASH_QB": (2, 0), "XATTN_RESIDENT": (3, 1), "FLASH_IMPL": (4, 0), "EXP0": (5, 0),
@@ -165,7 +169,12 @@ def lib():
     L.vcx_profile_end.argtypes = [POINTER(c_double)]
     L.vcx_tune_set.argtypes = [c_int, c_int]
     L.vcx_tune_get.argtypes = [c_int]
-    for name in SYMBOLS:
+    for name in EXT_SYMBOLS:
+        if not hasattr(L, name):
+            raise VcxError(f"libvcx.so does not export {name} (include/vcx_pool.h); rebuild the library (make -C viewcrafter_amd/csrc)")
+    L.vcx_layernorm_pool2x2_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]
+    L.vcx_layernorm_pool2x2_ok.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    for name in SYMBOLS + EXT_SYMBOLS:
         fn = getattr(L, name)
         if name == "vcx_groupnorm_ws_bytes":
             fn.restype = ctypes.c_size_t

@@ -1,6 +1,7 @@
 // GroupNorm (+SiLU) and LayerNorm on channels-last fp16 with fp32 statistics (HBM-bound).
 #include <type_traits>
 #include "mx_format.h"
+#include "../../include/vcx_pool.h"
 
 namespace {
 
@@ -489,6 +490,66 @@ __global__ void __launch_bounds__(256) layernorm_mx_kernel(const half_t* __restr
         }
 }
 
+// LayerNorm + 2x2 token pool in one pass (vcx_layernorm_pool2x2_f16): x [n][H][W][C] token rows -> y [n][H/2][W/2][C].  layernorm_kernel's lane
+// geometry and its two helpers, but a lane group owns one OUTPUT row and walks the source rows of its window: each is loaded, its statistics
+// summed and its chunks normalised and rounded to fp16 exactly as layernorm_kernel stores them, and (MEAN) the four rounded rows are summed in
+// fp32 registers in avgpool2x2_kernel's order - (2y, 2x), (2y, 2x + 1), (2y + 1, 2x), (2y + 1, 2x + 1), times 0.25, one rounding:
+// vcx_avgpool2x2_f16(vcx_layernorm_f16(x)) byte for byte without the normalised image in memory.  !MEAN: row (2y, 2x) only - the other three
+// rows of a window are never read.  64-bit row arithmetic throughout.
+template <int LPR, int CPL, bool MEAN>
+__global__ void __launch_bounds__(256) layernorm_pool_kernel(const half_t* __restrict__ x, half_t* __restrict__ y, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, int64_t orows, int H, int W, int C, float eps) {
+#pragma clang fp reassociate(off)                  // the window sum keeps avgpool2x2_kernel's order (the library is built with -ffast-math)
+    constexpr int RPB = 256 / LPR;                 // output rows per block
+    const int sub = threadIdx.x % LPR;
+    const int64_t orow = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+    const bool rvalid = orow < orows;
+    const int nc8 = C >> 3, Ho = H >> 1, Wo = W >> 1;
+    int64_t r = rvalid ? orow : 0;
+    const int xo = (int)(r % Wo);
+    r /= Wo;
+    const int yo = (int)(r % Ho);
+    const int64_t src0 = ((r / Ho) * H + 2 * yo) * W + 2 * xo;      // source row (2 yo, 2 xo) of the window's frame
+    half_t* yr = y + (rvalid ? orow : 0) * C;
+    h8 v[CPL];
+    float mean, rstd;
+    if constexpr (!MEAN) {
+        ln_row_stats<LPR, CPL>(x + src0 * C, sub, C, eps, v, mean, rstd);
+        if (!rvalid) return;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const int c = sub + j * LPR;
+            if (c < nc8) *reinterpret_cast<h8*>(yr + c * 8) = ln_normalise8(v[j], mean, rstd, gamma, beta, c);
+        }
+    } else {
+        float acc[CPL][8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            ln_row_stats<LPR, CPL>(x + (src0 + (k & 1) + (int64_t)(k >> 1) * W) * C, sub, C, eps, v, mean, rstd);
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) {
+                const int c = sub + j * LPR;
+                if (c < nc8) {
+                    const h8 o = ln_normalise8(v[j], mean, rstd, gamma, beta, c);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[j][e] = k == 0 ? (float)o[e] : acc[j][e] + (float)o[e];
+                }
+            }
+        }
+        if (!rvalid) return;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const int c = sub + j * LPR;
+            if (c < nc8) {
+                h8 o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = (half_t)(acc[j][e] * 0.25f);
+                *reinterpret_cast<h8*>(yr + c * 8) = o;
+            }
+        }
+    }
+}
+
 // thread geometry shared by the two GroupNorm kernels: cw channel chunks x pl pixel lanes, ~320 threads
 void gn_geometry(int C, int& cw, int& pl) {
     cw = C >> 3;
@@ -869,6 +930,43 @@ extern "C" int vcx_layernorm_mxfp8_f16(const void* x, void* q, void* scales, con
                            (unsigned char*)q, (unsigned char*)scales, gamma, beta, rows, C, kp, eps);
     });
     return vcx_check_launch("vcx_layernorm_mxfp8_f16");
+}
+
+// the geometry vcx_layernorm_pool2x2_f16 takes: 0, or the text of the first requirement that fails
+static const char* ln_pool_refusal(int n, int H, int W, int C, int mode) {
+    if (n <= 0 || H <= 0 || W <= 0 || C <= 0) return "need n, H, W, C > 0";
+    if ((H | W) & 1) return "need even H and W";
+    if (C % 8 != 0 || C > 8192) return "need C % 8 == 0 and C <= 8192";      // (an argument of %s below, not a format)
+    if ((int64_t)n * H * W >= (1ll << 31)) return "too many rows (n H W >= 2^31)";
+    if (mode != VCX_POOL_MEAN && mode != VCX_POOL_NEAREST) return "mode must be VCX_POOL_MEAN (0) or VCX_POOL_NEAREST (1)";
+    return nullptr;
+}
+
+extern "C" int vcx_layernorm_pool2x2_ok(int n, int H, int W, int C, int mode) {
+    const char* why = ln_pool_refusal(n, H, W, C, mode);
+    if (why) vcx_set_error("vcx_layernorm_pool2x2_f16: %s (n=%d H=%d W=%d C=%d mode=%d)", why, n, H, W, C, mode);
+    return why ? 0 : 1;
+}
+
+extern "C" int vcx_layernorm_pool2x2_f16(const void* x, void* y, const float* gamma, const float* beta, int n, int H, int W, int C, float eps,
+                                         int mode, void* stream) {
+    VCX_REQUIRE(x && y && gamma && beta, "vcx_layernorm_pool2x2_f16: null pointer");
+    if (!vcx_layernorm_pool2x2_ok(n, H, W, C, mode)) return VCX_EINVAL;
+    VCX_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0,
+                "vcx_layernorm_pool2x2_f16: pointers must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t orows = (int64_t)n * (H / 2) * (W / 2);
+    // mean: all four rows of a window are read; nearest: one of them
+    VcxProfScope prof(VCX_FAM_LN, s, 0.0, 2.0 * (double)orows * C * (mode == VCX_POOL_MEAN ? 5.0 : 2.0));
+    with_ln_geometry(C, [&](auto lpr, auto cpl) {
+        constexpr int LPR = decltype(lpr)::value, CPL = decltype(cpl)::value;
+        const dim3 grid((unsigned)((orows + 256 / LPR - 1) / (256 / LPR)));
+        if (mode == VCX_POOL_MEAN)
+            hipLaunchKernelGGL((layernorm_pool_kernel<LPR, CPL, true>), grid, dim3(256), 0, s, (const half_t*)x, (half_t*)y, gamma, beta, orows, H, W, C, eps);
+        else
+            hipLaunchKernelGGL((layernorm_pool_kernel<LPR, CPL, false>), grid, dim3(256), 0, s, (const half_t*)x, (half_t*)y, gamma, beta, orows, H, W, C, eps);
+    });
+    return vcx_check_launch("vcx_layernorm_pool2x2_f16");
 }
 
 extern "C" int vcx_rowstats_f16(const void* x, float* stats, int64_t rows, int C, float eps, void* stream) {

@@ -77,6 +77,41 @@ SATTN_MXFP8 = os.environ.get("VCX_SATTN_MXFP8", "0") == "1"
 # attentions of a 320-wide block are 0.94x of fp16 on MX (Kp = 384 pads a sixth of K; to_out 0.74x, q|k 0.91x), 640 / 1280 are 1.04x / 1.15x
 # against a spread of 0.2 - 0.7 % (profiles/mxfp8_sattn.md).  VCX_SATTN_MXFP8_SKIP_DIMS="" puts every width on MX.
 SATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_SATTN_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+# Opt-in (VCX_SATTN_KV_POOL=mean | nearest, default off): the spatial self-attention keeps every query but takes its keys and values from
+# the 2x2-pooled token grid of the frame (token downsampling: "ToDo", Smith et al. 2024; the spatial-reduction attention of PVT; training-
+# free) - a quarter of the key tiles, K and V^T projected from a quarter of the rows.  The pooled operand is LayerNorm + pool in one pass
+# (vcx_layernorm_pool2x2_f16: the mean of the window, or its row (2y, 2x)); Q is its own folded projection, K and V^T plain projections
+# of the pooled rows; the attention kernel is the fp16 flash kernel with nq = 4 nk.  Which calls pool: kv_pool_plan.  An approximation:
+# accuracy with a real checkpoint is unmeasured; what was measured is in profiles/sattn_kv_pool.md.  Off: no new launch, no new
+# allocation, every output bit as before.
+_KV_POOL_MODES = {"mean": ops.POOL_MEAN, "nearest": ops.POOL_NEAREST}
+
+
+def _parse_kv_pool(value):
+    if value in ("", "0"):
+        return None
+    if value not in _KV_POOL_MODES:
+        raise ValueError(f"VCX_SATTN_KV_POOL={value!r}: expected 0 (off), mean or nearest")
+    return value
+
+
+SATTN_KV_POOL = _parse_kv_pool(os.environ.get("VCX_SATTN_KV_POOL", "0"))
+# Frames with fewer tokens keep the un-pooled attention.  4096: level 0 of 576x1024 (9216 tokens a frame) pools, its deeper levels (2304,
+# 576, 144) and every level of 320x512 (2560 at most) do not, until this is lowered.
+SATTN_KV_POOL_MIN_TOKENS = int(os.environ.get("VCX_SATTN_KV_POOL_MIN_TOKENS", "4096"))
+
+
+def kv_pool_plan(H, W, C):
+    """SATTN_KV_POOL: the pooled token grid (H/2, W/2) the self-attention of a SpatialTransformer over H x W tokens of C channels a frame
+    takes its keys and values from, or None: the call keeps today's route.  From ONE frame's geometry only - a frame's route must not
+    depend on the batch it runs in (B = 2 against two B = 1, the shared CFG prefix against the replicated batch).  Pools iff the switch is
+    on, H and W are even, the frame has at least SATTN_KV_POOL_MIN_TOKENS tokens, the pooled count is a multiple of 8 (the attention
+    kernels address a frame's keys at 16-byte granularity; it makes H W a multiple of 8 too: no padded rows) and the library takes it."""
+    if SATTN_KV_POOL is None or H % 2 or W % 2 or H * W < SATTN_KV_POOL_MIN_TOKENS or (H // 2) * (W // 2) % 8:
+        return None
+    if not ops.layer_norm_pool2x2_ok(1, H, W, C, _KV_POOL_MODES[SATTN_KV_POOL]):
+        return None
+    return H // 2, W // 2
 
 # A transformer's last two linear layers - ff.net[2] + block residual, then proj_out + transformer residual - have nothing between them
 # and the token stream between them has no other reader (depth 1; proj_out follows the last block), so they run as ONE GEMM over
@@ -322,6 +357,19 @@ class CrossAttention(PackedModule):
                 pk["mx"] = dict(mx, wo=pack_mxfp8(pk["wo"]), bo=pk["bo"])
         return pk["mx"]
 
+    def kv_pool_packed(self):
+        """SATTN_KV_POOL (spatial self-attention): Q alone in the form today's Q|K pack has - folded where that is folded, carrying
+        sqrt(scale log2 e) - and the plain fp16 weights of K and V, which project the pooled, already normalised rows.  Built at first use
+        of the route, inside the pack: dropped with it."""
+        pk = self.packed()
+        if "kv_pool" not in pk:
+            with torch.no_grad():
+                ln = self._pre_norm[0] if pk["qk"]["colsum"] is not None else None
+                pv = pk["v"]
+                pk["kv_pool"] = dict(q=_ln_projection(self.to_q.weight.detach(), ln, alpha=math.sqrt(self.scale * ops.LOG2E)),
+                                     wk=_f16(self.to_k.weight), wv=pv["w"] if pv["colsum"] is None else _plain_of(pv)[0])
+        return pk["kv_pool"]
+
     def forward(self, *args, **kwargs):
         raise RuntimeError("CrossAttention is driven by SpatialTransformer/TemporalTransformer in this package")
 
@@ -521,13 +569,15 @@ class SpatialTransformer(PackedModule):
     def project_context(self, ctx):
         return [project_context(blk.attn2, ctx) for blk in self.transformer_blocks]
 
-    def _mx_route(self, x, context_kv, frames_per_video, cfg_repeat, N, D):
+    def _mx_route(self, x, context_kv, frames_per_video, cfg_repeat, N, D, pool=None):
         """SATTN_MXFP8: do the attentions of every block of this call run on the MX route?  Decided once per call, before anything runs:
         width not skipped, GPU tensors, and every predicate of the library - asked about the frames of ONE video (a row's route must not
         depend on the batch it runs in: B = 2 against two B = 1, the shared CFG prefix against the replicated batch) and about the call
         itself, before and behind the CFG replication (only the 32-bit extents depend on the batch).  Any refusal keeps the fp16 calls
-        for the whole transformer."""
+        for the whole transformer.  None for a call that kv_pool_plan accepts (`pool`): its self-attention runs the pooled fp16 route."""
         n, H, W, _ = x.shape
+        if pool is not None:
+            return None
         if not SATTN_MXFP8 or D in SATTN_MXFP8_SKIP_DIMS:
             return False
         attns = [a for blk in self.transformer_blocks for a in (blk.attn1, blk.attn2)]
@@ -565,7 +615,8 @@ class SpatialTransformer(PackedModule):
         n, H, W, C = x.shape
         N_img = H * W
         pk = self.packed()
-        mx = self._mx_route(x, context_kv, frames_per_video, cfg_repeat, (N_img + 7) // 8 * 8, pk["win"].shape[0])      # SATTN_MXFP8, decided before anything runs
+        pool = kv_pool_plan(H, W, pk["win"].shape[0])      # SATTN_KV_POOL, decided before anything runs
+        mx = self._mx_route(x, context_kv, frames_per_video, cfg_repeat, (N_img + 7) // 8 * 8, pk["win"].shape[0], pool)      # SATTN_MXFP8, likewise
         # colstats: column moments of x from the convolution that produced it (ResBlock): the norm then needs no statistics pass
         stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, N_img, C)
         D_in = pk["win"].shape[0]
@@ -597,7 +648,8 @@ class SpatialTransformer(PackedModule):
         rs = None
         video_rows = frames_per_video * N
         # (no row statistics on the MX route: the quantising LayerNorm computes its own)
-        if not mx and _folded(blk0.attn1.packed()["qk"], tokens, D_in, D_in) and ops.rowstats_ok(tokens, D_in, C, lda=C, unit_rows=N_img if fold else None,
+        p1 = blk0.attn1.kv_pool_packed()["q"] if pool is not None else blk0.attn1.packed()["qk"]      # the projection that reads norm1's statistics
+        if not mx and _folded(p1, tokens, D_in, D_in) and ops.rowstats_ok(tokens, D_in, C, lda=C, unit_rows=N_img if fold else None,
                                                                                       video_rows=video_rows):
             rs = ops.rowstats_buffer(tokens, x.device)
         if fold:
@@ -617,14 +669,17 @@ class SpatialTransformer(PackedModule):
             # scale * log2(e) rides in the projections (sqrt of it on Q and on K: one fp16 rounding each, as without it), so the
             # attention kernel gets base-2 logits and its running max can live in the MFMA accumulator (VCX_ATTN_LOG2_LOGITS)
             pqk, pv, qk_alpha = a1["qk"], a1["v"], math.sqrt(blk.attn1.scale * ops.LOG2E)
-            # norm1 folded into both projections (they read the token stream itself) wherever the pack is folded and the kernel
-            # takes the shape; layer_norm + plain projections otherwise (ln_linear / ln_linear_t)
-            st = rs if (bi == 0 and rs is not None) else (ops.row_stats(t, ln[0][2]) if pqk["colsum"] is not None else None)
-            qk = ln_linear(t, pqk, ln[0], alpha=qk_alpha, stats=st)                 # [tokens, 2D]
-            vt = ln_linear_t(t, pv, ln[0], stats=st)                                # [D, tokens]
-            o = torch.empty((tokens, D), dtype=torch.float16, device=x.device)
-            ops.flash_attn(qk, qk[:, D:], vt, o, n_groups=n, heads=heads, nq=N, nk=N_img, kv_rows=N, kv_div=1, ldq=2 * D,
-                           ldk=2 * D, ldvt=tokens, ldo=D, scale=blk.attn1.scale, log2_logits=True)
+            if pool is not None:        # SATTN_KV_POOL: every query, keys and values of the 2x2-pooled tokens
+                o = _sattn_kv_pool(blk, ln[0], t, n, H, W, pool, heads, rs if bi == 0 else None)
+            else:
+                # norm1 folded into both projections (they read the token stream itself) wherever the pack is folded and the kernel
+                # takes the shape; layer_norm + plain projections otherwise (ln_linear / ln_linear_t)
+                st = rs if (bi == 0 and rs is not None) else (ops.row_stats(t, ln[0][2]) if pqk["colsum"] is not None else None)
+                qk = ln_linear(t, pqk, ln[0], alpha=qk_alpha, stats=st)                 # [tokens, 2D]
+                vt = ln_linear_t(t, pv, ln[0], stats=st)                                # [D, tokens]
+                o = torch.empty((tokens, D), dtype=torch.float16, device=x.device)
+                ops.flash_attn(qk, qk[:, D:], vt, o, n_groups=n, heads=heads, nq=N, nk=N_img, kv_rows=N, kv_div=1, ldq=2 * D,
+                               ldk=2 * D, ldvt=tokens, ldo=D, scale=blk.attn1.scale, log2_logits=True)
             st2 = ops.rowstats_buffer(tokens, x.device) if (_folded(a2["q"], tokens, D, D) and ops.rowstats_ok(tokens, D, D, ldr=D, video_rows=video_rows)) else None
             t = ops.linear(o, a1["wo"], a1["bo"], residual=t, rowstats=st2, rowstats_eps=ln[1][2])
             # ---- cross-attention: softmax(Q K_txt) V_txt + softmax(Q K_img) V_img
@@ -654,6 +709,23 @@ class SpatialTransformer(PackedModule):
             ops.copy2d(out, unpadded, n, N_img * C, N * C, N_img * C)
             out = unpadded
         return out.view(n, H, W, C), cs_out
+
+
+def _sattn_kv_pool(blk, lnp, t, n, H, W, pool, heads, rs):
+    """The self-attention of one SpatialTransformer block on the SATTN_KV_POOL route, up to its output projection: five calls (six where
+    the folded Q projection has no row statistics from its producer, `rs`), in this order.  lnp = (gamma, beta, eps) of norm1; t
+    [n H W, D] (kv_pool_plan: no padded rows).  -> the attention output [n H W, D]."""
+    pp = blk.attn1.kv_pool_packed()
+    tokens, D = t.shape
+    N, Np = H * W, pool[0] * pool[1]
+    alpha = math.sqrt(blk.attn1.scale * ops.LOG2E)
+    q = ln_linear(t, pp["q"], lnp, alpha=alpha, stats=rs)                                        # [tokens, D], every query
+    p = ops.layer_norm_pool2x2(t, *lnp, n, H, W, _KV_POOL_MODES[SATTN_KV_POOL])                   # [n Np, D], normalised and pooled
+    k = ops.linear(p, pp["wk"], None, alpha=alpha)                                               # [n Np, D]
+    vt = ops.gemm(pp["wv"], p, M=D, N=n * Np, K=D, lda=D)                                        # [D, n Np]
+    o = torch.empty((tokens, D), dtype=torch.float16, device=t.device)
+    return ops.flash_attn(q, k, vt, o, n_groups=n, heads=heads, nq=N, nk=Np, kv_rows=Np, kv_div=1, ldq=D, ldk=D, ldvt=n * Np, ldo=D,
+                          scale=blk.attn1.scale, log2_logits=True)
 
 
 def _sattn_mx_block(blk, kv, ln, t, xin, n, N, N_img, D, heads, frames_per_video, cfg_repeat):

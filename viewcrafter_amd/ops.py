@@ -445,6 +445,28 @@ def layer_norm(x, gamma, beta, eps=1e-5):
     return out
 
 
+POOL_MEAN, POOL_NEAREST = 0, 1      # include/vcx_pool.h VCX_POOL_*
+
+
+def layer_norm_pool2x2_ok(n, H, W, C, mode):
+    """Does vcx_layernorm_pool2x2_f16 take n frames of H x W tokens with C channels in this mode?  The library's answer (no device needed)."""
+    return lib().vcx_layernorm_pool2x2_ok(n, H, W, C, mode) == 1
+
+
+def layer_norm_pool2x2(x, gamma, beta, eps, n, H, W, mode):
+    """x [n H W, C] dense token rows, row-major over (frame, y, x) -> [n (H/2) (W/2), C]: avgpool2x2(layer_norm(x) viewed [n, H, W, C]) for
+    POOL_MEAN, the rows (2y, 2x) of layer_norm(x) for POOL_NEAREST - byte for byte, in one pass; the normalised rows are never written."""
+    rows, C = x.shape
+    _dev16(x)
+    _dev32(gamma, beta)
+    if rows != n * H * W or not x.is_contiguous():
+        raise VcxError(f"layer_norm_pool2x2: dense rows [n H W, C] needed (rows={rows} n={n} H={H} W={W})")
+    out = torch.empty((n * (H // 2) * (W // 2), C), dtype=_f16, device=x.device)
+    check(lib().vcx_layernorm_pool2x2_f16(x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), n, H, W, C, eps, mode, _stream()),
+          "layernorm_pool2x2")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # MXFP8 operands (include/vcx.h "MXFP8 operands"; opt-in: the GEGLU feed-forward under VCX_FF_MXFP8=1, the TemporalConvBlock convolutions
 # under VCX_TCONV_MXFP8=1, the ResBlock 3x3 convolutions under VCX_RESCONV_MXFP8=1)
