@@ -480,96 +480,106 @@ int epi_of(int flags) {
     return -1;
 }
 
-// shape rules and extents of a call with the given row pitches (elements of the output / residual); `why` gets the reason of a refusal
-bool mx_takes(int64_t M, int64_t N, int64_t K, int flags, int64_t ldc, int64_t ldr, const char** why) {
-    const int epi = epi_of(flags);
-    *why = "flags: BIAS_N, BIAS_N | RESIDUAL, BIAS_N | GEGLU or BIAS_N | GEGLU | MXFP8_OUT";
-    if (epi < 0) return false;
-    *why = "need M, N, K > 0, K % 32 == 0, N % 8 == 0 (GEGLU: N % 64 == 0, whole packed blocks; MXFP8 out: N / 2 % 32 == 0)";
-    if (M <= 0 || N <= 0 || K <= 0 || K % MX_BLOCK != 0 || N % 8 != 0 || (epi && N % 64 != 0)) return false;
-    if (M >= (1ll << 31) || N >= (1ll << 31) || K >= (1ll << 31)) return false;
-    const unsigned long long kp = (unsigned long long)mx_kp(K), nout = epi ? N / 2 : N, kpo = (unsigned long long)mx_kp((int64_t)nout);
-    *why = "an operand, output or residual extent of 4 GiB or more (32-bit buffer offsets)";
-    if ((unsigned long long)M * kp >= LIM || (unsigned long long)N * kp >= LIM) return false;
-    // the tile grid reaches up to 127 rows past M: their offsets must not wrap back into the buffer
-    const unsigned long long mt = (unsigned long long)(M + 127) / 128 * 128;
-    if (mt * kp >= (1ull << 32)) return false;
-    if (epi == 2) return mt * kpo < LIM;
-    if (ldc < (int64_t)nout || mt * (unsigned long long)ldc * 2 >= LIM) return false;
-    if ((flags & VCX_GEMM_RESIDUAL) && (ldr < (int64_t)nout || mt * (unsigned long long)ldr * 2 >= LIM)) return false;
+// What the four entry points differ in, host side only: one value per call, read by the shape predicate and by the launcher.
+struct MxCall {
+    int gm;                            // gather mode (gemm_mx_kernel's GM)
+    bool tail;                         // the linear K tail behind the gathered K-steps (GM = 2)
+    int taps;                          // 1, 3 or 9: a weight row is taps x Kp(Cin) (+ Kp(Ct)) bytes
+    int may;                           // flags a gathered form permits beside BIAS_N
+    const char *dims, *rows;           // the factors of M as the messages name them ("B, T, P" / "B T P")
+    const char* reach_name;            // ... and the reach ("P", "W + 1")
+    const char* flag_rule;             // the reason of a refused flag word
+    int64_t outer, in1, in2;           // M = outer x in1 x in2: (B, T, P), (n, H, W) or (M, 1, 1)
+    unsigned long long reach;          // rows the farthest tap reads past a row: 0, P or W + 1
+    int64_t Cin, Ct, N;
+    int flags;
+    int64_t ldc, ldr, ldcs, cs_col;    // cs_col: first column of the moments inside their [strips][ldcs] buffer (a launcher's pointer already
+                                       // points there and shows its parity in its alignment: the launchers pass 0)
+    int64_t rowadd_ld, rowadd_div;
+    int64_t M() const { return outer * in1 * in2; }      // (after the predicate's 2^31 product checks)
+    int epi() const { return gm == 0 ? epi_of(flags) : (flags & VCX_GEMM_COLSTATS) ? 3 : 0; }
+};
+
+MxCall mx_linear(int64_t M, int64_t N, int64_t K, int64_t ldc, int64_t ldr, int flags) {
+    return {0, false, 1, 0, "M", "M", "", "", M, 1, 1, 0, K, 0, N, flags, ldc, ldr, 0, 0, 0, 0};
+}
+
+MxCall mx_t3(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t cs_col, int flags) {
+    return {1, false, 3, VCX_GEMM_RESIDUAL | VCX_GEMM_COLSTATS, "B, T, P", "B T P", "P", "flags: BIAS_N, optionally with RESIDUAL and / or COLSTATS",
+            B, T, P, (unsigned long long)P, Cin, 0, N, flags, ldc, ldr, ldcs, cs_col, 0, 0};
+}
+
+// the 3x3 form, and with `tail` its K-tailed form: bias required, COLSTATS optional; a residual or a row addend is refused there (the second
+// convolution of a skip-convolution block has neither)
+MxCall mx_c9(int64_t n, int64_t H, int64_t W, int64_t Cin, bool tail, int64_t Ct, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t cs_col,
+             int64_t rowadd_ld, int64_t rowadd_div, int flags) {
+    return {2, tail, 9, tail ? VCX_GEMM_COLSTATS : VCX_GEMM_ROWADD | VCX_GEMM_RESIDUAL | VCX_GEMM_COLSTATS, "n, H, W", "n H W", "W + 1",
+            tail ? "flags: BIAS_N, optionally with COLSTATS (no RESIDUAL, no ROWADD on the tailed form)"
+                 : "flags: BIAS_N, optionally with ROWADD, RESIDUAL and / or COLSTATS",
+            n, H, W, (unsigned long long)W + 1, Cin, Ct, N, flags, ldc, ldr, ldcs, cs_col, rowadd_ld, rowadd_div};
+}
+
+typedef char MxWhy[256];      // the reason of a refusal
+#define MX_NEED(cond, ...)                             \
+    do {                                               \
+        if (!(cond)) {                                 \
+            snprintf(why, sizeof(MxWhy), __VA_ARGS__); \
+            return false;                              \
+        }                                              \
+    } while (0)
+
+// 32-bit buffer offsets of fp16 rows of pitch ld (output, residual): the tile grid reaches up to 127 rows past M, and those rows' offsets must
+// not wrap back into the buffer
+unsigned long long mx_mt(unsigned long long M) { return (M + 127) / 128 * 128; }
+bool mx_f16_fits(unsigned long long M, int64_t ld) { return mx_mt(M) * (unsigned long long)ld * 2 < LIM; }
+
+// vcx_gemm_mxfp8: shape rules and extents of a call with the given row pitches (elements of the output / residual; their alignment is the
+// entry point's business); `why` gets the reason of a refusal
+bool mx_takes(const MxCall& c, MxWhy& why) {
+    const int64_t M = c.outer, N = c.N, K = c.Cin;
+    const int epi = c.epi();
+    MX_NEED(epi >= 0, "flags: BIAS_N, BIAS_N | RESIDUAL, BIAS_N | GEGLU or BIAS_N | GEGLU | MXFP8_OUT");
+    MX_NEED(M > 0 && N > 0 && K > 0 && K % MX_BLOCK == 0 && N % 8 == 0 && !(epi && N % 64 != 0) && M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31),
+            "need M, N, K > 0, K %% 32 == 0, N %% 8 == 0 (GEGLU: N %% 64 == 0, whole packed blocks; MXFP8 out: N / 2 %% 32 == 0)");
+    const int64_t nout = epi ? N / 2 : N;
+    const unsigned long long kp = (unsigned long long)mx_kp(K), kpo = (unsigned long long)mx_kp(nout);
+    bool fits = (unsigned long long)M * kp < LIM && (unsigned long long)N * kp < LIM && mx_mt(M) * kp < (1ull << 32);
+    if (epi == 2) fits = fits && mx_mt(M) * kpo < LIM;
+    else fits = fits && c.ldc >= nout && mx_f16_fits(M, c.ldc) && (!(c.flags & VCX_GEMM_RESIDUAL) || (c.ldr >= nout && mx_f16_fits(M, c.ldr)));
+    MX_NEED(fits, "an operand, output or residual extent of 4 GiB or more (32-bit buffer offsets)");
     return true;
 }
 
-// vcx_conv_t3_mxfp8: shape, flag, pitch and extent rules; `why` gets the reason of a refusal.  cs_col = first column of the moments inside
-// their [strips][ldcs] buffer (the caller's pointer already points there: only its alignment is this function's business).
-bool t3_takes(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int flags, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t cs_col, const char** why) {
-    *why = "flags: BIAS_N, optionally with RESIDUAL and / or COLSTATS";
-    if (!(flags & VCX_GEMM_BIAS_N) || (flags & ~(VCX_GEMM_BIAS_N | VCX_GEMM_RESIDUAL | VCX_GEMM_COLSTATS))) return false;
-    *why = "need B, T, P, Cin, N > 0, Cin % 32 == 0, N % 8 == 0";
-    if (B <= 0 || T <= 0 || P <= 0 || Cin <= 0 || N <= 0 || Cin % MX_BLOCK != 0 || N % 8 != 0) return false;
-    *why = "a dimension of 2^31 or more";
+// vcx_conv_t3_mxfp8, vcx_conv3x3_mxfp8, vcx_conv3x3_tail_mxfp8: shape, flag, pitch and extent rules; the first failing rule decides the reason
+bool mx_gather_takes(const MxCall& c, MxWhy& why) {
     constexpr int64_t I31 = 1ll << 31;
-    if (B >= I31 || T >= I31 || P >= I31 || Cin >= I31 || N >= I31 || ldc >= I31 || ldr >= I31 || ldcs >= I31) return false;
-    if (B * T >= I31 || B * T * P >= I31) return false;
-    const unsigned long long M = (unsigned long long)(B * T * P), kp = (unsigned long long)mx_kp(Cin);
-    *why = "row pitches: ldc >= N, ldc % 8 == 0; with RESIDUAL ldr >= N, ldr % 8 == 0";
-    if (ldc < N || ldc % 8 != 0) return false;
-    if ((flags & VCX_GEMM_RESIDUAL) && (ldr < N || ldr % 8 != 0)) return false;
-    *why = "COLSTATS: B T P % 64 == 0, ldcs >= first column + N, ldcs and the first column even (16-byte aligned moment pairs)";
-    if ((flags & VCX_GEMM_COLSTATS) && (M % 64 != 0 || cs_col < 0 || ldcs < cs_col + N || ldcs % 2 != 0 || cs_col % 2 != 0)) return false;
-    // 32-bit buffer offsets.  The tile grid reaches up to 127 rows past M and a tap up to P rows further: (M + 127 + P) Kp must not wrap
-    // for the activation (its scale array is 1/32 of it); the weight rows are 3 Kp long and reach 127 rows past N.
-    *why = "an operand, output or residual extent of 4 GiB or more (32-bit buffer offsets; activations: (M + 127 + P) Kp)";
-    if ((M + 127 + (unsigned long long)P) * kp >= LIM || ((unsigned long long)N + 127) * 3 * kp >= LIM) return false;
-    const unsigned long long mt = (M + 127) / 128 * 128;
-    if (mt * (unsigned long long)ldc * 2 >= LIM) return false;
-    if ((flags & VCX_GEMM_RESIDUAL) && mt * (unsigned long long)ldr * 2 >= LIM) return false;
+    const int64_t N = c.N, Cin = c.Cin;
+    const bool res = c.flags & VCX_GEMM_RESIDUAL;
+    MX_NEED((c.flags & VCX_GEMM_BIAS_N) && !(c.flags & ~(VCX_GEMM_BIAS_N | c.may)), "%s", c.flag_rule);
+    MX_NEED(c.outer > 0 && c.in1 > 0 && c.in2 > 0 && Cin > 0 && N > 0 && Cin % MX_BLOCK == 0 && N % 8 == 0, "need %s, Cin, N > 0, Cin %% 32 == 0, N %% 8 == 0",
+            c.dims);
+    MX_NEED(c.outer < I31 && c.in1 < I31 && c.in2 < I31 && Cin < I31 && N < I31 && c.ldc < I31 && c.ldr < I31 && c.ldcs < I31 && c.rowadd_div < I31
+                && c.outer * c.in1 < I31 && c.outer * c.in1 * c.in2 < I31,
+            "a dimension of 2^31 or more");
+    const unsigned long long M = (unsigned long long)c.M(), kp = (unsigned long long)mx_kp(Cin);
+    MX_NEED(c.ldc >= N && c.ldc % 8 == 0 && (!res || (c.ldr >= N && c.ldr % 8 == 0)),
+            "row pitches: ldc >= N, ldc %% 8 == 0; with RESIDUAL ldr >= N, ldr %% 8 == 0");
+    MX_NEED(!(c.flags & VCX_GEMM_COLSTATS) || (M % 64 == 0 && c.cs_col >= 0 && c.ldcs >= c.cs_col + N && c.ldcs % 2 == 0 && c.cs_col % 2 == 0),
+            "COLSTATS: %s %% 64 == 0, ldcs >= first column + N, ldcs and the first column even (16-byte aligned moment pairs)", c.rows);
+    MX_NEED(!(c.flags & VCX_GEMM_ROWADD) || c.rowadd_div > 0, "ROWADD: rowadd_div > 0 (output rows per row of the addend)");
+    // 32-bit buffer offsets.  The tile grid reaches up to 127 rows past M and the farthest tap `reach` rows further: (M + 127 + reach) Kp must
+    // not wrap for the activation (its scale array is 1/32 of it); the weight rows are taps x Kp long and reach 127 rows past N.
+    MX_NEED((M + 127 + c.reach) * kp < LIM && ((unsigned long long)N + 127) * c.taps * kp < LIM && mx_f16_fits(M, c.ldc) && (!res || mx_f16_fits(M, c.ldr)),
+            "an operand, output or residual extent of 4 GiB or more (32-bit buffer offsets; activations: (M + 127 + %s) Kp)", c.reach_name);
+    if (!c.tail) return true;
+    MX_NEED(c.Ct > 0 && c.Ct % MX_BLOCK == 0 && c.Ct < I31, "need Ct > 0, Ct %% 32 == 0, Ct < 2^31");
+    // the tail source reaches 127 rows past M, the weight rows are taps x Kp(Cin) + Kp(Ct) long and reach 127 rows past N
+    const unsigned long long kpt = (unsigned long long)mx_kp(c.Ct);
+    MX_NEED((M + 127) * kpt < LIM && ((unsigned long long)N + 127) * (c.taps * kp + kpt) < LIM,
+            "a tail or weight extent of 4 GiB or more (32-bit buffer offsets; tail: (M + 127) Kp(Ct), weights: (N + 127) (9 Kp(Cin) + Kp(Ct)))");
     return true;
 }
-
-// vcx_conv3x3_mxfp8: shape, flag, pitch and extent rules; `why` gets the reason of a refusal (cs_col as in t3_takes)
-bool c9_takes(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int flags, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t cs_col, int64_t rowadd_div,
-              const char** why) {
-    *why = "flags: BIAS_N, optionally with ROWADD, RESIDUAL and / or COLSTATS";
-    if (!(flags & VCX_GEMM_BIAS_N) || (flags & ~(VCX_GEMM_BIAS_N | VCX_GEMM_ROWADD | VCX_GEMM_RESIDUAL | VCX_GEMM_COLSTATS))) return false;
-    *why = "need n, H, W, Cin, N > 0, Cin % 32 == 0, N % 8 == 0";
-    if (n <= 0 || H <= 0 || W <= 0 || Cin <= 0 || N <= 0 || Cin % MX_BLOCK != 0 || N % 8 != 0) return false;
-    *why = "a dimension of 2^31 or more";
-    constexpr int64_t I31 = 1ll << 31;
-    if (n >= I31 || H >= I31 || W >= I31 || Cin >= I31 || N >= I31 || ldc >= I31 || ldr >= I31 || ldcs >= I31 || rowadd_div >= I31) return false;
-    if (n * H >= I31 || n * H * W >= I31) return false;
-    const unsigned long long M = (unsigned long long)(n * H * W), kp = (unsigned long long)mx_kp(Cin);
-    *why = "row pitches: ldc >= N, ldc % 8 == 0; with RESIDUAL ldr >= N, ldr % 8 == 0";
-    if (ldc < N || ldc % 8 != 0) return false;
-    if ((flags & VCX_GEMM_RESIDUAL) && (ldr < N || ldr % 8 != 0)) return false;
-    *why = "COLSTATS: n H W % 64 == 0, ldcs >= first column + N, ldcs and the first column even (16-byte aligned moment pairs)";
-    if ((flags & VCX_GEMM_COLSTATS) && (M % 64 != 0 || cs_col < 0 || ldcs < cs_col + N || ldcs % 2 != 0 || cs_col % 2 != 0)) return false;
-    *why = "ROWADD: rowadd_div > 0 (output rows per row of the addend)";
-    if ((flags & VCX_GEMM_ROWADD) && rowadd_div <= 0) return false;
-    // 32-bit buffer offsets.  The tile grid reaches up to 127 rows past M and the farthest tap W + 1 rows further: (M + 127 + W + 1) Kp must
-    // not wrap for the activation (its scale array is 1/32 of it); the weight rows are 9 Kp long and reach 127 rows past N.
-    *why = "an operand, output or residual extent of 4 GiB or more (32-bit buffer offsets; activations: (M + 127 + W + 1) Kp)";
-    if ((M + 127 + (unsigned long long)W + 1) * kp >= LIM || ((unsigned long long)N + 127) * 9 * kp >= LIM) return false;
-    const unsigned long long mt = (M + 127) / 128 * 128;
-    if (mt * (unsigned long long)ldc * 2 >= LIM) return false;
-    if ((flags & VCX_GEMM_RESIDUAL) && mt * (unsigned long long)ldr * 2 >= LIM) return false;
-    return true;
-}
-
-// vcx_conv3x3_tail_mxfp8: c9_takes' rules for the gathered part with the flags the tailed form has (bias required, COLSTATS optional; a
-// residual or a row addend is refused: the second convolution of a skip-convolution block has neither), plus the tail's own
-bool c9t_takes(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Ct, int64_t N, int flags, int64_t ldc, int64_t ldcs, int64_t cs_col, const char** why) {
-    *why = "flags: BIAS_N, optionally with COLSTATS (no RESIDUAL, no ROWADD on the tailed form)";
-    if (!(flags & VCX_GEMM_BIAS_N) || (flags & ~(VCX_GEMM_BIAS_N | VCX_GEMM_COLSTATS))) return false;
-    if (!c9_takes(n, H, W, Cin, N, flags, ldc, 0, ldcs, cs_col, 1, why)) return false;
-    *why = "need Ct > 0, Ct % 32 == 0, Ct < 2^31";
-    if (Ct <= 0 || Ct % MX_BLOCK != 0 || Ct >= (1ll << 31)) return false;
-    // 32-bit buffer offsets: the tail source reaches 127 rows past M, the weight rows are 9 Kp(Cin) + Kp(Ct) long and reach 127 rows past N
-    const unsigned long long M = (unsigned long long)(n * H * W), kp = (unsigned long long)mx_kp(Cin), kpt = (unsigned long long)mx_kp(Ct);
-    *why = "a tail or weight extent of 4 GiB or more (32-bit buffer offsets; tail: (M + 127) Kp(Ct), weights: (N + 127) (9 Kp(Cin) + Kp(Ct)))";
-    if ((M + 127) * kpt >= LIM || ((unsigned long long)N + 127) * (9 * kp + kpt) >= LIM) return false;
-    return true;
-}
+#undef MX_NEED
 
 // The tile configuration of a call: 0 = Cfg128, 1 = Cfg160 (include/vcx.h vcx_gemm_mxfp8_cfg).  A function of N, the flag word and the gather
 // mode - never of M: a row's configuration cannot depend on the batch.  Cfg160 has the plain and the column-moment epilogue only.
@@ -594,6 +604,84 @@ int mx_cfg_launch(int64_t N, int flags, int gm, unsigned long long row_bytes) {
     return cfg;
 }
 
+// every kernel there is: [GM + TAIL][EPI][configuration], null where the family has none (Cfg160: plain and column-moment epilogues only; the
+// GEGLU epilogues: the linear form only; column moments: the gathered forms only)
+typedef int (*MxLaunch)(const MxArgs&, hipStream_t);
+constexpr MxLaunch MX_KERNELS[4][4][2] = {
+    {{launch_mx<Cfg128, 0>, launch_mx<Cfg160, 0>}, {launch_mx<Cfg128, 1>, nullptr}, {launch_mx<Cfg128, 2>, nullptr}, {nullptr, nullptr}},
+    {{launch_mx<Cfg128, 0, 1>, launch_mx<Cfg160, 0, 1>}, {nullptr, nullptr}, {nullptr, nullptr}, {launch_mx<Cfg128, 3, 1>, launch_mx<Cfg160, 3, 1>}},
+    {{launch_mx<Cfg128, 0, 2>, launch_mx<Cfg160, 0, 2>}, {nullptr, nullptr}, {nullptr, nullptr}, {launch_mx<Cfg128, 3, 2>, launch_mx<Cfg160, 3, 2>}},
+    {{launch_mx<Cfg128, 0, 2, true>, launch_mx<Cfg160, 0, 2, true>}, {nullptr, nullptr}, {nullptr, nullptr},
+     {launch_mx<Cfg128, 3, 2, true>, launch_mx<Cfg160, 3, 2, true>}},
+};
+
+// a call's operands, in the order the entry points name them; null where a form has none
+struct MxPtrs {
+    const void *a, *a_scales, *t, *t_scales, *w, *w_scales;
+    void *out, *out_scales;
+    const float *bias, *rowadd;
+    const void* residual;
+    float* colstats;
+};
+
+// fills the kernel's arguments for a call its predicate took, and launches it
+int mx_launch(const MxCall& c, const MxPtrs& o, void* stream) {
+    const int64_t M = c.M(), N = c.N;
+    const int epi = c.epi();
+    const int64_t nout = epi == 1 || epi == 2 ? N / 2 : N;
+    const bool radd = c.flags & VCX_GEMM_ROWADD;
+    MxArgs p{};
+    p.A = (const unsigned char*)o.a;
+    p.As = (const unsigned char*)o.a_scales;
+    p.Tl = (const unsigned char*)o.t;
+    p.Tls = (const unsigned char*)o.t_scales;
+    p.W = (const unsigned char*)o.w;
+    p.Ws = (const unsigned char*)o.w_scales;
+    p.C = o.out;
+    p.Cs = (unsigned char*)o.out_scales;
+    p.bias = o.bias;
+    p.R = (const half_t*)o.residual;
+    p.M = (int)M;
+    p.N = (int)N;
+    p.kp = (int)mx_kp(c.Cin);
+    p.kpt = c.tail ? (int)mx_kp(c.Ct) : 0;
+    p.kpo = (int)mx_kp(nout);
+    if (c.gm == 1) {
+        p.T = (int)c.in1;
+        p.P = (int)c.in2;
+    } else if (c.gm == 2) {
+        p.GH = (int)c.in1;
+        p.GW = (int)c.in2;
+    }
+    p.rowadd = radd ? o.rowadd : nullptr;
+    p.rowadd_ld = radd ? (int)c.rowadd_ld : 0;
+    p.rowadd_div = radd ? (int)c.rowadd_div : 1;      // (the 3x3 epilogue divides by it with or without the flag)
+    p.ldc = (int)c.ldc;
+    p.ldr = (int)c.ldr;
+    p.flags = c.flags;
+    p.colstats = o.colstats;
+    p.ldcs = c.ldcs;
+    const int64_t wrow = (int64_t)c.taps * p.kp + p.kpt;      // bytes of a weight row
+    const int cfg = mx_cfg_launch(N, c.flags, c.gm, (unsigned long long)wrow);
+    const int tbn = cfg ? Cfg160::TBN : Cfg128::TBN;
+    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
+    p.tiles_n = epi == 2 ? 2 * p.kpo / Cfg128::TBN : (int)((N + tbn - 1) / tbn);
+    p.a_bytes = (unsigned)(M * p.kp);
+    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
+    p.t_bytes = (unsigned)(M * p.kpt);
+    p.ts_bytes = (unsigned)(M * (p.kpt / MX_BLOCK));
+    p.w_bytes = (unsigned)(N * wrow);
+    p.ws_bytes = (unsigned)(N * (wrow / MX_BLOCK));
+    p.c_bytes = epi == 2 ? (unsigned)(M * p.kpo) : (unsigned)(2 * ((M - 1) * c.ldc + nout));
+    p.cs_bytes = epi == 2 ? (unsigned)(M * (p.kpo / MX_BLOCK)) : 0u;
+    p.r_bytes = (c.flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * c.ldr + nout)) : 0u;
+    const MxLaunch launch = MX_KERNELS[c.gm + c.tail][epi][cfg];
+    VCX_REQUIRE(launch, "gemm_mx: no kernel for gather mode %d%s, epilogue %d, configuration %d", c.gm, c.tail ? " (tailed)" : "", epi, cfg);
+    hipStream_t s = (hipStream_t)stream;
+    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * ((double)c.taps * c.Cin + c.Ct), (double)M * (p.kp + p.kpt) + (double)N * wrow + 2.0 * M * nout);
+    return launch(p, s);
+}
+
 }  // namespace
 
 extern "C" int vcx_gemm_mxfp8_cfg(int64_t N, int flags, int gather_mode) {
@@ -603,8 +691,8 @@ extern "C" int vcx_gemm_mxfp8_cfg(int64_t N, int flags, int gather_mode) {
 
 extern "C" int vcx_conv3x3_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
                                     int64_t rowadd_div, int flags) {
-    const char* why;
-    if (c9_takes(n, H, W, Cin, N, flags, ldc, ldr, ldcs, colstats_col, rowadd_div, &why)) return 1;
+    MxWhy why;
+    if (mx_gather_takes(mx_c9(n, H, W, Cin, false, 0, N, ldc, ldr, ldcs, colstats_col, 0, rowadd_div, flags), why)) return 1;
     vcx_set_error("vcx_conv3x3_mxfp8_ok(n=%lld, H=%lld, W=%lld, Cin=%lld, N=%lld, ldc=%lld, ldr=%lld, ldcs=%lld, col=%lld, rowadd_div=%lld, flags=0x%x): %s",
                   (long long)n, (long long)H, (long long)W, (long long)Cin, (long long)N, (long long)ldc, (long long)ldr, (long long)ldcs, (long long)colstats_col,
                   (long long)rowadd_div, flags, why);
@@ -618,9 +706,9 @@ extern "C" int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void
     VCX_REQUIRE(!(flags & VCX_GEMM_ROWADD) || rowadd, "vcx_conv3x3_mxfp8: VCX_GEMM_ROWADD needs a rowadd");
     VCX_REQUIRE(!(flags & VCX_GEMM_RESIDUAL) || residual, "vcx_conv3x3_mxfp8: VCX_GEMM_RESIDUAL needs a residual");
     VCX_REQUIRE(!(flags & VCX_GEMM_COLSTATS) || colstats, "vcx_conv3x3_mxfp8: VCX_GEMM_COLSTATS needs a colstats buffer");
-    const char* why;
-    // (the moments' first column is in the pointer: its parity shows in the pointer's alignment, checked below)
-    VCX_REQUIRE(c9_takes(n, H, W, Cin, N, flags, ldc, ldr, ldcs, 0, rowadd_div, &why),
+    const MxCall c = mx_c9(n, H, W, Cin, false, 0, N, ldc, ldr, ldcs, 0, rowadd_ld, rowadd_div, flags);
+    MxWhy why;
+    VCX_REQUIRE(mx_gather_takes(c, why),
                 "vcx_conv3x3_mxfp8(n=%lld, H=%lld, W=%lld, Cin=%lld, N=%lld, flags=0x%x, ldc=%lld, ldr=%lld, ldcs=%lld, rowadd_div=%lld): %s", (long long)n,
                 (long long)H, (long long)W, (long long)Cin, (long long)N, flags, (long long)ldc, (long long)ldr, (long long)ldcs, (long long)rowadd_div, why);
     VCX_REQUIRE(!(flags & VCX_GEMM_ROWADD) || (rowadd_ld >= N && rowadd_ld % 4 == 0 && rowadd_ld < (1ll << 31)),
@@ -628,47 +716,13 @@ extern "C" int vcx_conv3x3_mxfp8(const void* a, const void* a_scales, const void
     VCX_REQUIRE((((uintptr_t)a | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)rowadd | (uintptr_t)residual | (uintptr_t)colstats) & 15) == 0
                     && (((uintptr_t)a_scales | (uintptr_t)w_scales) & 3) == 0,
                 "vcx_conv3x3_mxfp8: operands, output, bias, rowadd, residual and colstats must be 16-byte aligned, scale arrays 4-byte aligned");
-    const int64_t M = n * H * W;
-    MxArgs p{};
-    p.A = (const unsigned char*)a;
-    p.As = (const unsigned char*)a_scales;
-    p.W = (const unsigned char*)w;
-    p.Ws = (const unsigned char*)w_scales;
-    p.C = out;
-    p.bias = bias;
-    p.R = (const half_t*)residual;
-    p.M = (int)M;
-    p.N = (int)N;
-    p.kp = (int)mx_kp(Cin);
-    p.GH = (int)H;
-    p.GW = (int)W;
-    p.rowadd = (flags & VCX_GEMM_ROWADD) ? rowadd : nullptr;
-    p.rowadd_ld = (flags & VCX_GEMM_ROWADD) ? (int)rowadd_ld : 0;
-    p.rowadd_div = (flags & VCX_GEMM_ROWADD) ? (int)rowadd_div : 1;
-    p.ldc = (int)ldc;
-    p.ldr = (int)ldr;
-    p.flags = flags;
-    p.colstats = colstats;
-    p.ldcs = ldcs;
-    const int cfg = mx_cfg_launch(N, flags, 2, 9ull * (unsigned long long)p.kp);
-    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
-    p.tiles_n = (int)((N + (cfg ? Cfg160::TBN : Cfg128::TBN) - 1) / (cfg ? Cfg160::TBN : Cfg128::TBN));
-    p.a_bytes = (unsigned)(M * p.kp);
-    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
-    p.w_bytes = (unsigned)(N * 9 * p.kp);
-    p.ws_bytes = (unsigned)(N * 9 * (p.kp / MX_BLOCK));
-    p.c_bytes = (unsigned)(2 * ((M - 1) * ldc + N));
-    p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + N)) : 0u;
-    hipStream_t s = (hipStream_t)stream;
-    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * 9.0 * Cin, (double)(M + 9 * N) * p.kp + 2.0 * M * N);
-    if (flags & VCX_GEMM_COLSTATS) return cfg ? launch_mx<Cfg160, 3, 2>(p, s) : launch_mx<Cfg128, 3, 2>(p, s);
-    return cfg ? launch_mx<Cfg160, 0, 2>(p, s) : launch_mx<Cfg128, 0, 2>(p, s);
+    return mx_launch(c, {a, a_scales, nullptr, nullptr, w, w_scales, out, nullptr, bias, rowadd, residual, colstats}, stream);
 }
 
 extern "C" int vcx_conv3x3_tail_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Ct, int64_t N, int64_t ldc, int64_t ldcs, int64_t colstats_col,
                                          int flags) {
-    const char* why;
-    if (c9t_takes(n, H, W, Cin, Ct, N, flags, ldc, ldcs, colstats_col, &why)) return 1;
+    MxWhy why;
+    if (mx_gather_takes(mx_c9(n, H, W, Cin, true, Ct, N, ldc, 0, ldcs, colstats_col, 0, 0, flags), why)) return 1;
     vcx_set_error("vcx_conv3x3_tail_mxfp8_ok(n=%lld, H=%lld, W=%lld, Cin=%lld, Ct=%lld, N=%lld, ldc=%lld, ldcs=%lld, col=%lld, flags=0x%x): %s", (long long)n,
                   (long long)H, (long long)W, (long long)Cin, (long long)Ct, (long long)N, (long long)ldc, (long long)ldcs, (long long)colstats_col, flags, why);
     return 0;
@@ -679,56 +733,20 @@ extern "C" int vcx_conv3x3_tail_mxfp8(const void* a, const void* a_scales, const
                                       int64_t ldcs, int flags, void* stream) {
     VCX_REQUIRE(a && a_scales && t && t_scales && w && w_scales && out && bias, "vcx_conv3x3_tail_mxfp8: null pointer");
     VCX_REQUIRE(!(flags & VCX_GEMM_COLSTATS) || colstats, "vcx_conv3x3_tail_mxfp8: VCX_GEMM_COLSTATS needs a colstats buffer");
-    const char* why;
-    // (the moments' first column is in the pointer: its parity shows in the pointer's alignment, checked below)
-    VCX_REQUIRE(c9t_takes(n, H, W, Cin, Ct, N, flags, ldc, ldcs, 0, &why),
-                "vcx_conv3x3_tail_mxfp8(n=%lld, H=%lld, W=%lld, Cin=%lld, Ct=%lld, N=%lld, flags=0x%x, ldc=%lld, ldcs=%lld): %s", (long long)n, (long long)H,
-                (long long)W, (long long)Cin, (long long)Ct, (long long)N, flags, (long long)ldc, (long long)ldcs, why);
+    const MxCall c = mx_c9(n, H, W, Cin, true, Ct, N, ldc, 0, ldcs, 0, 0, 0, flags);
+    MxWhy why;
+    VCX_REQUIRE(mx_gather_takes(c, why), "vcx_conv3x3_tail_mxfp8(n=%lld, H=%lld, W=%lld, Cin=%lld, Ct=%lld, N=%lld, flags=0x%x, ldc=%lld, ldcs=%lld): %s",
+                (long long)n, (long long)H, (long long)W, (long long)Cin, (long long)Ct, (long long)N, flags, (long long)ldc, (long long)ldcs, why);
     VCX_REQUIRE((((uintptr_t)a | (uintptr_t)t | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)colstats) & 15) == 0
                     && (((uintptr_t)a_scales | (uintptr_t)t_scales | (uintptr_t)w_scales) & 3) == 0,
                 "vcx_conv3x3_tail_mxfp8: operands, output, bias and colstats must be 16-byte aligned, scale arrays 4-byte aligned");
-    const int64_t M = n * H * W;
-    MxArgs p{};
-    p.A = (const unsigned char*)a;
-    p.As = (const unsigned char*)a_scales;
-    p.Tl = (const unsigned char*)t;
-    p.Tls = (const unsigned char*)t_scales;
-    p.W = (const unsigned char*)w;
-    p.Ws = (const unsigned char*)w_scales;
-    p.C = out;
-    p.bias = bias;
-    p.M = (int)M;
-    p.N = (int)N;
-    p.kp = (int)mx_kp(Cin);
-    p.kpt = (int)mx_kp(Ct);
-    p.GH = (int)H;
-    p.GW = (int)W;
-    p.rowadd_div = 1;
-    p.ldc = (int)ldc;
-    p.flags = flags;
-    p.colstats = colstats;
-    p.ldcs = ldcs;
-    const int64_t wrow = 9ll * p.kp + p.kpt;      // bytes of a weight row
-    const int cfg = mx_cfg_launch(N, flags, 2, (unsigned long long)wrow);
-    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
-    p.tiles_n = (int)((N + (cfg ? Cfg160::TBN : Cfg128::TBN) - 1) / (cfg ? Cfg160::TBN : Cfg128::TBN));
-    p.a_bytes = (unsigned)(M * p.kp);
-    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
-    p.t_bytes = (unsigned)(M * p.kpt);
-    p.ts_bytes = (unsigned)(M * (p.kpt / MX_BLOCK));
-    p.w_bytes = (unsigned)(N * wrow);
-    p.ws_bytes = (unsigned)(N * (wrow / MX_BLOCK));
-    p.c_bytes = (unsigned)(2 * ((M - 1) * ldc + N));
-    hipStream_t s = (hipStream_t)stream;
-    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * (9.0 * Cin + Ct), (double)(M + N) * (double)wrow - 8.0 * M * p.kp + 2.0 * M * N);
-    if (flags & VCX_GEMM_COLSTATS) return cfg ? launch_mx<Cfg160, 3, 2, true>(p, s) : launch_mx<Cfg128, 3, 2, true>(p, s);
-    return cfg ? launch_mx<Cfg160, 0, 2, true>(p, s) : launch_mx<Cfg128, 0, 2, true>(p, s);
+    return mx_launch(c, {a, a_scales, t, t_scales, w, w_scales, out, nullptr, bias, nullptr, nullptr, colstats}, stream);
 }
 
 extern "C" int vcx_conv_t3_mxfp8_ok(int64_t B, int64_t T, int64_t P, int64_t Cin, int64_t N, int64_t ldc, int64_t ldr, int64_t ldcs, int64_t colstats_col,
                                     int flags) {
-    const char* why;
-    if (t3_takes(B, T, P, Cin, N, flags, ldc, ldr, ldcs, colstats_col, &why)) return 1;
+    MxWhy why;
+    if (mx_gather_takes(mx_t3(B, T, P, Cin, N, ldc, ldr, ldcs, colstats_col, flags), why)) return 1;
     vcx_set_error("vcx_conv_t3_mxfp8_ok(B=%lld, T=%lld, P=%lld, Cin=%lld, N=%lld, ldc=%lld, ldr=%lld, ldcs=%lld, col=%lld, flags=0x%x): %s", (long long)B,
                   (long long)T, (long long)P, (long long)Cin, (long long)N, (long long)ldc, (long long)ldr, (long long)ldcs, (long long)colstats_col, flags, why);
     return 0;
@@ -740,51 +758,20 @@ extern "C" int vcx_conv_t3_mxfp8(const void* a, const void* a_scales, const void
     VCX_REQUIRE(a && a_scales && w && w_scales && out && bias, "vcx_conv_t3_mxfp8: null pointer");
     VCX_REQUIRE(!(flags & VCX_GEMM_RESIDUAL) || residual, "vcx_conv_t3_mxfp8: VCX_GEMM_RESIDUAL needs a residual");
     VCX_REQUIRE(!(flags & VCX_GEMM_COLSTATS) || colstats, "vcx_conv_t3_mxfp8: VCX_GEMM_COLSTATS needs a colstats buffer");
-    const char* why;
-    // (the moments' first column is in the pointer: its parity shows in the pointer's alignment, checked below)
-    VCX_REQUIRE(t3_takes(B, T, P, Cin, N, flags, ldc, ldr, ldcs, 0, &why), "vcx_conv_t3_mxfp8(B=%lld, T=%lld, P=%lld, Cin=%lld, N=%lld, flags=0x%x, ldc=%lld, ldr=%lld, ldcs=%lld): %s",
+    const MxCall c = mx_t3(B, T, P, Cin, N, ldc, ldr, ldcs, 0, flags);
+    MxWhy why;
+    VCX_REQUIRE(mx_gather_takes(c, why), "vcx_conv_t3_mxfp8(B=%lld, T=%lld, P=%lld, Cin=%lld, N=%lld, flags=0x%x, ldc=%lld, ldr=%lld, ldcs=%lld): %s",
                 (long long)B, (long long)T, (long long)P, (long long)Cin, (long long)N, flags, (long long)ldc, (long long)ldr, (long long)ldcs, why);
     VCX_REQUIRE((((uintptr_t)a | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)colstats) & 15) == 0
                     && (((uintptr_t)a_scales | (uintptr_t)w_scales) & 3) == 0,
                 "vcx_conv_t3_mxfp8: operands, output, bias, residual and colstats must be 16-byte aligned, scale arrays 4-byte aligned");
-    const int64_t M = B * T * P;
-    MxArgs p{};
-    p.A = (const unsigned char*)a;
-    p.As = (const unsigned char*)a_scales;
-    p.W = (const unsigned char*)w;
-    p.Ws = (const unsigned char*)w_scales;
-    p.C = out;
-    p.bias = bias;
-    p.R = (const half_t*)residual;
-    p.M = (int)M;
-    p.N = (int)N;
-    p.kp = (int)mx_kp(Cin);
-    p.T = (int)T;
-    p.P = (int)P;
-    p.ldc = (int)ldc;
-    p.ldr = (int)ldr;
-    p.flags = flags;
-    p.colstats = colstats;
-    p.ldcs = ldcs;
-    const int cfg = mx_cfg_launch(N, flags, 1, 3ull * (unsigned long long)p.kp);
-    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
-    p.tiles_n = (int)((N + (cfg ? Cfg160::TBN : Cfg128::TBN) - 1) / (cfg ? Cfg160::TBN : Cfg128::TBN));
-    p.a_bytes = (unsigned)(M * p.kp);
-    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
-    p.w_bytes = (unsigned)(N * 3 * p.kp);
-    p.ws_bytes = (unsigned)(N * 3 * (p.kp / MX_BLOCK));
-    p.c_bytes = (unsigned)(2 * ((M - 1) * ldc + N));
-    p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + N)) : 0u;
-    hipStream_t s = (hipStream_t)stream;
-    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * 3.0 * Cin, (double)(M + 3 * N) * p.kp + 2.0 * M * N);
-    if (flags & VCX_GEMM_COLSTATS) return cfg ? launch_mx<Cfg160, 3, 1>(p, s) : launch_mx<Cfg128, 3, 1>(p, s);
-    return cfg ? launch_mx<Cfg160, 0, 1>(p, s) : launch_mx<Cfg128, 0, 1>(p, s);
+    return mx_launch(c, {a, a_scales, nullptr, nullptr, w, w_scales, out, nullptr, bias, nullptr, residual, colstats}, stream);
 }
 
 extern "C" int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags) {
-    const char* why;
+    MxWhy why;
     const int64_t nout = (flags & VCX_GEMM_GEGLU) ? N / 2 : N;
-    if (mx_takes(M, N, K, flags, nout, nout, &why)) return 1;
+    if (mx_takes(mx_linear(M, N, K, nout, nout, flags), why)) return 1;
     vcx_set_error("vcx_gemm_mxfp8_ok(M=%lld, N=%lld, K=%lld, flags=0x%x): %s", (long long)M, (long long)N, (long long)K, flags, why);
     return 0;
 }
@@ -792,48 +779,15 @@ extern "C" int vcx_gemm_mxfp8_ok(int64_t M, int64_t N, int64_t K, int flags) {
 extern "C" int vcx_gemm_mxfp8(const void* a, const void* a_scales, const void* w, const void* w_scales, void* out, void* out_scales,
                               const float* bias, const void* residual, int64_t M, int64_t N, int64_t K, int64_t ldc, int64_t ldr, int flags,
                               void* stream) {
-    const int epi = epi_of(flags);
     VCX_REQUIRE(a && a_scales && w && w_scales && out && bias, "vcx_gemm_mxfp8: null pointer");
-    VCX_REQUIRE(epi != 2 || out_scales, "vcx_gemm_mxfp8: VCX_GEMM_MXFP8_OUT needs out_scales");
+    VCX_REQUIRE(epi_of(flags) != 2 || out_scales, "vcx_gemm_mxfp8: VCX_GEMM_MXFP8_OUT needs out_scales");
     VCX_REQUIRE(!(flags & VCX_GEMM_RESIDUAL) || residual, "vcx_gemm_mxfp8: VCX_GEMM_RESIDUAL needs a residual");
-    const char* why;
-    VCX_REQUIRE(mx_takes(M, N, K, flags, ldc, ldr, &why), "vcx_gemm_mxfp8(M=%lld, N=%lld, K=%lld, flags=0x%x, ldc=%lld, ldr=%lld): %s", (long long)M,
-                (long long)N, (long long)K, flags, (long long)ldc, (long long)ldr, why);
+    const MxCall c = mx_linear(M, N, K, ldc, ldr, flags);
+    MxWhy why;
+    VCX_REQUIRE(mx_takes(c, why), "vcx_gemm_mxfp8(M=%lld, N=%lld, K=%lld, flags=0x%x, ldc=%lld, ldr=%lld): %s", (long long)M, (long long)N, (long long)K, flags,
+                (long long)ldc, (long long)ldr, why);
     VCX_REQUIRE((((uintptr_t)a | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)residual) & 15) == 0 && ldc % 8 == 0 && ldr % 8 == 0
                     && (((uintptr_t)a_scales | (uintptr_t)w_scales | (uintptr_t)out_scales) & 3) == 0,
                 "vcx_gemm_mxfp8: operands, output, bias and residual must be 16-byte aligned (ldc, ldr %% 8 == 0), scale arrays 4-byte aligned");
-    MxArgs p{};
-    p.A = (const unsigned char*)a;
-    p.As = (const unsigned char*)a_scales;
-    p.W = (const unsigned char*)w;
-    p.Ws = (const unsigned char*)w_scales;
-    p.C = out;
-    p.Cs = (unsigned char*)out_scales;
-    p.bias = bias;
-    p.R = (const half_t*)residual;
-    p.M = (int)M;
-    p.N = (int)N;
-    p.kp = (int)mx_kp(K);
-    const int64_t nout = epi ? N / 2 : N;
-    p.kpo = (int)mx_kp(nout);
-    p.ldc = (int)ldc;
-    p.ldr = (int)ldr;
-    p.flags = flags;
-    const int cfg = mx_cfg_launch(N, flags, 0, (unsigned long long)p.kp);      // (1 for the plain epilogue only)
-    p.tiles_m = (int)((M + Cfg128::TBM - 1) / Cfg128::TBM);
-    p.tiles_n = epi == 2 ? 2 * p.kpo / Cfg128::TBN : (int)((N + (cfg ? Cfg160::TBN : Cfg128::TBN) - 1) / (cfg ? Cfg160::TBN : Cfg128::TBN));
-    p.a_bytes = (unsigned)(M * p.kp);
-    p.as_bytes = (unsigned)(M * (p.kp / MX_BLOCK));
-    p.w_bytes = (unsigned)(N * p.kp);
-    p.ws_bytes = (unsigned)(N * (p.kp / MX_BLOCK));
-    p.c_bytes = epi == 2 ? (unsigned)(M * p.kpo) : (unsigned)(2 * ((M - 1) * ldc + nout));
-    p.cs_bytes = epi == 2 ? (unsigned)(M * (p.kpo / MX_BLOCK)) : 0u;
-    p.r_bytes = (flags & VCX_GEMM_RESIDUAL) ? (unsigned)(2 * ((M - 1) * ldr + nout)) : 0u;
-    hipStream_t s = (hipStream_t)stream;
-    VcxProfScope prof(VCX_FAM_GEMM, s, 2.0 * M * N * K, (double)(M + N) * p.kp + 2.0 * M * nout);
-    switch (epi) {
-        case 0: return cfg ? launch_mx<Cfg160, 0>(p, s) : launch_mx<Cfg128, 0>(p, s);
-        case 1: return launch_mx<Cfg128, 1>(p, s);
-        default: return launch_mx<Cfg128, 2>(p, s);
-    }
+    return mx_launch(c, {a, a_scales, nullptr, nullptr, w, w_scales, out, out_scales, bias, nullptr, residual, nullptr}, stream);
 }

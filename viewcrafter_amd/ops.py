@@ -44,6 +44,36 @@ def _dev32(*tensors):
             raise VcxError(f"expected a GPU fp32 tensor, got {t.dtype} on {t.device}")
 
 
+def _out_arg(out, ldc, M, n_out, like, dtype=_f16, what=None):
+    """(out, ldc) of a launcher's `out` / `ldc` keywords: a fresh dense [M, n_out] tensor on the device of `like`, or the caller's with its
+    row stride where ldc is not given.  `what` (the MXFP8 convolutions): the caller's buffer must hold M rows of that pitch."""
+    if out is None:
+        return torch.empty((M, n_out), dtype=dtype, device=like.device), n_out
+    if ldc is None:
+        ldc = out.stride(0)
+    if what is not None and out.numel() < (M - 1) * ldc + n_out:
+        raise VcxError(f"{what}: out holds {out.numel()} elements, [{M}] rows of pitch {ldc} need {(M - 1) * ldc + n_out}")
+    return out, ldc
+
+
+def _colstats_arg(colstats, colstats_ld, colstats_col, M, n_out):
+    """(pointer to the moments of the call's first column, ldcs) of a launcher's colstats* keywords; (None, 0) without a buffer."""
+    if colstats is None:
+        return None, 0
+    _dev32(colstats)
+    cld = n_out if colstats_ld is None else int(colstats_ld)
+    if colstats.numel() != (M // 64) * cld * 2 or colstats_col < 0 or colstats_col + n_out > cld:
+        raise VcxError(f"colstats must hold [M / 64, {cld}, 2] floats (M={M}, N={n_out}, first column {colstats_col}), got {tuple(colstats.shape)}")
+    return colstats.data_ptr() + 8 * int(colstats_col), cld
+
+
+def _rowstats_arg(rowstats, M):
+    _dev32(rowstats)
+    if rowstats.numel() != 2 * M or not rowstats.is_contiguous():
+        raise VcxError(f"rowstats must hold [M = {M}, 2] floats, got {tuple(rowstats.shape)}")
+    return rowstats.data_ptr()
+
+
 def require_gpu():
     """Raise unless a gfx950 device and the built library are available (no fallback path)."""
     if not torch.cuda.is_available():
@@ -104,11 +134,7 @@ def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, res
     n_out = N // 2 if geglu else N
     _dev16(a, w, residual)
     _dev32(bias, rowadd)
-    if out is None:
-        out = torch.empty((M, n_out), dtype=_f32 if out_f32 else _f16, device=a.device)
-        ldc = n_out
-    elif ldc is None:
-        ldc = out.stride(0)
+    out, ldc = _out_arg(out, ldc, M, n_out, a, _f32 if out_f32 else _f16)
     if tail and len(tail) > 2:
         raise VcxError("gemm: a K tail has one or two sources")
     for j, t in enumerate(tail or ()):
@@ -140,18 +166,10 @@ def gemm(a, w, *, M, N, K, lda, out=None, ldc=None, bias=None, bias_m=False, res
         d.ln_stats, d.ln_colsum = ln_stats.data_ptr(), ln_colsum.data_ptr()
         flags |= GEMM_LNFOLD_T if ln_t else GEMM_LNFOLD
     if colstats is not None:
-        _dev32(colstats)
-        cld = n_out if colstats_ld is None else int(colstats_ld)
-        if colstats.numel() != (M // 64) * cld * 2 or colstats_col < 0 or colstats_col + n_out > cld:
-            raise VcxError(f"colstats must hold [M / 64, {cld}, 2] floats (M={M}, N={n_out}, first column {colstats_col}), got {tuple(colstats.shape)}")
-        d.colstats = colstats.data_ptr() + 8 * int(colstats_col)
-        d.ldcs = cld
+        d.colstats, d.ldcs = _colstats_arg(colstats, colstats_ld, colstats_col, M, n_out)
         flags |= GEMM_COLSTATS
     if rowstats is not None:
-        _dev32(rowstats)
-        if rowstats.numel() != 2 * M or not rowstats.is_contiguous():
-            raise VcxError(f"rowstats must hold [M = {M}, 2] floats, got {tuple(rowstats.shape)}")
-        d.rowstats, d.rowstats_eps = rowstats.data_ptr(), float(rowstats_eps)
+        d.rowstats, d.rowstats_eps = _rowstats_arg(rowstats, M), float(rowstats_eps)
         flags |= GEMM_ROWSTATS
     if tail:
         _dev16(*tail)
@@ -197,15 +215,11 @@ def gemm_units(a, wn, bn, *, unit_rows, out=None, rowstats=None, rowstats_eps=1e
     _dev32(bn)
     if K2 != K or M != units * unit_rows or tuple(bn.shape) != (units, N) or not wn.is_contiguous() or not bn.is_contiguous():
         raise VcxError(f"gemm_units: a {tuple(a.shape)} / wn {tuple(wn.shape)} / bn {tuple(bn.shape)} do not describe {units} units of {unit_rows} rows")
-    if out is None:
-        out = torch.empty((M, N), dtype=_f16, device=a.device)
-    d = _gemm_desc(M, N, K, a.stride(0), out.stride(0), flags=GEMM_BIAS_N)
+    out, ldc = _out_arg(out, None, M, N, a)
+    d = _gemm_desc(M, N, K, a.stride(0), ldc, flags=GEMM_BIAS_N)
     d.A, d.W, d.C, d.bias = a.data_ptr(), wn.data_ptr(), out.data_ptr(), bn.data_ptr()
     if rowstats is not None:
-        _dev32(rowstats)
-        if rowstats.numel() != 2 * M or not rowstats.is_contiguous():
-            raise VcxError(f"rowstats must hold [M = {M}, 2] floats, got {tuple(rowstats.shape)}")
-        d.rowstats, d.rowstats_eps = rowstats.data_ptr(), float(rowstats_eps)
+        d.rowstats, d.rowstats_eps = _rowstats_arg(rowstats, M), float(rowstats_eps)
         d.flags |= GEMM_ROWSTATS
     check(lib().vcx_gemm_units_f16(ctypes.byref(d), int(unit_rows), N * K, N, _stream()), "vcx_gemm_units_f16")
     return out
@@ -388,41 +402,35 @@ def group_norm_fold_linear(w32, bias, gamma, beta, stats, eps, groups=32):
     return wn, bn
 
 
+def _group_norm_arg(what, x, x2, gamma, beta, stats, groups, quant, out=None):
+    """What group_norm, group_norm_mxfp8 and group_norm_mxfp8_raw (`what`) share: the checks of x [n_outer, pixels, c1] and of the optional
+    second half x2 of a channel concat (`quant`: the quantising forms' own - a dense x, whole MX blocks over the concat), the type of a
+    caller's `out`, and the statistics pass where `stats` is not handed in.  -> (n_outer, pixels, c1, C, stats)"""
+    n_outer, pixels, c1 = x.shape
+    C = c1 + (0 if x2 is None else x2.shape[2])
+    _dev16(x, x2, out)
+    _dev32(gamma, beta, stats)
+    if quant and not x.is_contiguous():
+        raise VcxError(f"{what}: a contiguous [n_outer, pixels, C] tensor needed")
+    if x2 is not None and (stats is None or tuple(x2.shape[:2]) != (n_outer, pixels) or c1 % 8 != 0 or (quant and C % 32 != 0) or not x.is_contiguous()
+                           or not x2.is_contiguous()):
+        raise VcxError(f"{what} over a split concat needs statistics, contiguous halves{', c1 % 8 == 0 and C % 32 == 0' if quant else ' and c1 % 8 == 0'} "
+                       f"(x1 {tuple(x.shape)}, x2 {tuple(x2.shape)})")
+    return n_outer, pixels, c1, C, group_norm_stats(x, groups) if stats is None else stats
+
+
 def group_norm(x, gamma, beta, eps, silu, groups=32, out=None, stats=None, x2=None):
     """x [n_outer, pixels, C] fp16 (contiguous).  Statistics over (pixels, C/groups) - computed here, or handed in (`stats`
     [n_outer, groups, 2] = (mean, variance), from group_norm_stats_from_colstats).  x2 [n_outer, pixels, C2]: the norm runs over the
     channel concat [x | x2] without materialising it (vcx_groupnorm_apply2_f16; `stats` required)."""
-    if x2 is not None:
-        return _group_norm2(x, x2, gamma, beta, eps, silu, groups, out, stats)
-    n_outer, pixels, C = x.shape
-    _dev16(x, out)
-    _dev32(gamma, beta)
-    L = lib()
-    s = _stream()
-    if stats is None:
-        stats = torch.empty((n_outer, groups, 2), dtype=_f32, device=x.device)
-        ws = torch.empty((L.vcx_groupnorm_ws_bytes(n_outer, pixels, groups),), dtype=torch.uint8, device=x.device)
-        check(L.vcx_groupnorm_stats_f16(x.data_ptr(), stats.data_ptr(), ws.data_ptr(), n_outer, pixels, C, groups, s), "groupnorm_stats")
+    n_outer, pixels, c1, C, stats = _group_norm_arg("group_norm", x, x2, gamma, beta, stats, groups, False, out)
+    rest = (stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), n_outer, pixels, C, groups, eps, 1 if silu else 0, _stream())
+    if x2 is None:
+        out = torch.empty_like(x) if out is None else out
+        check(lib().vcx_groupnorm_apply_f16(x.data_ptr(), out.data_ptr(), *rest), "groupnorm_apply")
     else:
-        _dev32(stats)
-    if out is None:
-        out = torch.empty_like(x)
-    check(L.vcx_groupnorm_apply_f16(x.data_ptr(), out.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                    n_outer, pixels, C, groups, eps, 1 if silu else 0, s), "groupnorm_apply")
-    return out
-
-
-def _group_norm2(x1, x2, gamma, beta, eps, silu, groups, out, stats):
-    n_outer, pixels, c1 = x1.shape
-    C = c1 + x2.shape[2]
-    _dev16(x1, x2, out)
-    _dev32(gamma, beta, stats)
-    if stats is None or tuple(x2.shape[:2]) != (n_outer, pixels) or c1 % 8 != 0 or not x1.is_contiguous() or not x2.is_contiguous():
-        raise VcxError(f"group_norm over a split concat needs statistics, contiguous halves and c1 % 8 == 0 (x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)})")
-    if out is None:
-        out = torch.empty((n_outer, pixels, C), dtype=_f16, device=x1.device)
-    check(lib().vcx_groupnorm_apply2_f16(x1.data_ptr(), c1, x2.data_ptr(), out.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                         n_outer, pixels, C, groups, eps, 1 if silu else 0, _stream()), "groupnorm_apply2")
+        out = torch.empty((n_outer, pixels, C), dtype=_f16, device=x.device) if out is None else out
+        check(lib().vcx_groupnorm_apply2_f16(x.data_ptr(), c1, x2.data_ptr(), out.data_ptr(), *rest), "groupnorm_apply2")
     return out
 
 
@@ -484,12 +492,30 @@ def _mx_buffers(rows, K, device):
     return torch.empty((rows, kp), dtype=_u8, device=device), torch.empty((rows, kp // 32), dtype=_u8, device=device)
 
 
-def _dev_mx(pair, rows, K, what):
-    q, s = pair
-    kp = mx_kp(K)
-    for t, shape in ((q, (rows, kp)), (s, (rows, kp // 32))):
+def _mx_weight_arg(pair, rows, k_bytes, what):
+    """An MXFP8 pair with rows of k_bytes element bytes (a convolution's weight rows: its taps, each padded on its own, and its tail)."""
+    for t, shape in zip(pair, ((rows, k_bytes), (rows, k_bytes // 32))):
         if t.dtype is not _u8 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
             raise VcxError(f"{what}: expected contiguous GPU uint8 {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _dev_mx(pair, rows, K, what):
+    _mx_weight_arg(pair, rows, mx_kp(K), what)
+
+
+def _mx_bias_residual_arg(bias, residual, ldr, M, n_out, what, bias_n=None):
+    """The bias every MXFP8 GEMM entry point requires (bias_n entries where that is not n_out: packed GEGLU columns) and its optional
+    residual [M, n_out]; -> ldr (the residual's row stride where not given, 0 without a residual or a value)."""
+    bias_n = n_out if bias_n is None else bias_n
+    _dev32(bias)
+    _dev16(residual)
+    if bias is None or bias.numel() != bias_n or not bias.is_contiguous():
+        raise VcxError(f"{what}: a contiguous fp32 bias [N = {bias_n}] is required")
+    if residual is None:
+        return ldr or 0
+    if tuple(residual.shape) != (M, n_out) or residual.stride(1) != 1:
+        raise VcxError(f"{what}: residual must be [{M}, {n_out}] with unit column stride, got {tuple(residual.shape)}")
+    return residual.stride(0) if ldr is None else ldr
 
 
 def quant_mxfp8(x):
@@ -541,13 +567,10 @@ def linear_mxfp8(a, w, bias, *, K, residual=None, geglu=False, mx_out=False):
     rows, N = a[0].shape[0], w[0].shape[0]
     _dev_mx(a, rows, K, "linear_mxfp8 a")
     _dev_mx(w, N, K, "linear_mxfp8 w")
-    _dev32(bias)
-    _dev16(residual)
-    if bias is None or bias.numel() != N or not bias.is_contiguous() or (mx_out and not geglu):
-        raise VcxError(f"linear_mxfp8: a contiguous fp32 bias [N = {N}] is required; mx_out goes with geglu")
     n_out = N // 2 if geglu else N
-    if residual is not None and (tuple(residual.shape) != (rows, n_out) or residual.stride(1) != 1):
-        raise VcxError(f"linear_mxfp8: residual must be [{rows}, {n_out}] with unit column stride, got {tuple(residual.shape)}")
+    ldr = _mx_bias_residual_arg(bias, residual, None, rows, n_out, "linear_mxfp8", bias_n=N)
+    if mx_out and not geglu:
+        raise VcxError("linear_mxfp8: mx_out goes with geglu")
     if mx_out:
         out = _mx_buffers(rows, n_out, a[0].device)
         c, cs = out[0].data_ptr(), out[1].data_ptr()
@@ -555,7 +578,7 @@ def linear_mxfp8(a, w, bias, *, K, residual=None, geglu=False, mx_out=False):
         out = torch.empty((rows, n_out), dtype=_f16, device=a[0].device)
         c, cs = out.data_ptr(), None
     check(lib().vcx_gemm_mxfp8(a[0].data_ptr(), a[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(), c, cs, bias.data_ptr(), _ptr(residual), rows, N, K,
-                               n_out, residual.stride(0) if residual is not None else 0, _mx_flags(residual is not None, geglu, mx_out), _stream()),
+                               n_out, ldr, _mx_flags(residual is not None, geglu, mx_out), _stream()),
           "gemm_mxfp8")
     return out
 
@@ -591,39 +614,13 @@ def group_norm_mxfp8(x, gamma, beta, eps, silu, groups=32, stats=None, x2=None):
     [n_outer, pixels, C2]: the norm runs over the channel concat [x | x2] without materialising it (vcx_groupnorm_apply2_mxfp8_f16;
     `stats` required, as for group_norm).
     -> (element bytes [n_outer * pixels, Kp], scale bytes [n_outer * pixels, Kp / 32])."""
-    if x2 is not None:
-        return _group_norm2_mxfp8(x, x2, gamma, beta, eps, silu, groups, stats)
-    n_outer, pixels, C = x.shape
-    _dev16(x)
-    _dev32(gamma, beta)
-    if not x.is_contiguous():
-        raise VcxError("group_norm_mxfp8: a contiguous [n_outer, pixels, C] tensor needed")
-    L = lib()
-    s = _stream()
-    if stats is None:
-        stats = torch.empty((n_outer, groups, 2), dtype=_f32, device=x.device)
-        ws = torch.empty((L.vcx_groupnorm_ws_bytes(n_outer, pixels, groups),), dtype=torch.uint8, device=x.device)
-        check(L.vcx_groupnorm_stats_f16(x.data_ptr(), stats.data_ptr(), ws.data_ptr(), n_outer, pixels, C, groups, s), "groupnorm_stats")
-    else:
-        _dev32(stats)
+    n_outer, pixels, c1, C, stats = _group_norm_arg("group_norm_mxfp8", x, x2, gamma, beta, stats, groups, quant=True)
     q, sc = _mx_buffers(n_outer * pixels, C, x.device)
-    check(L.vcx_groupnorm_apply_mxfp8_f16(x.data_ptr(), q.data_ptr(), sc.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                          n_outer, pixels, C, groups, eps, 1 if silu else 0, s), "groupnorm_apply_mxfp8")
-    return q, sc
-
-
-def _group_norm2_mxfp8(x1, x2, gamma, beta, eps, silu, groups, stats):
-    n_outer, pixels, c1 = x1.shape
-    C = c1 + x2.shape[2]
-    _dev16(x1, x2)
-    _dev32(gamma, beta, stats)
-    if (stats is None or tuple(x2.shape[:2]) != (n_outer, pixels) or c1 % 8 != 0 or C % 32 != 0 or not x1.is_contiguous()
-            or not x2.is_contiguous()):
-        raise VcxError(f"group_norm_mxfp8 over a split concat needs statistics, contiguous halves, c1 % 8 == 0 and C % 32 == 0 "
-                       f"(x1 {tuple(x1.shape)}, x2 {tuple(x2.shape)})")
-    q, sc = _mx_buffers(n_outer * pixels, C, x1.device)
-    check(lib().vcx_groupnorm_apply2_mxfp8_f16(x1.data_ptr(), c1, x2.data_ptr(), q.data_ptr(), sc.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
-                                               beta.data_ptr(), n_outer, pixels, C, groups, eps, 1 if silu else 0, _stream()), "groupnorm_apply2_mxfp8")
+    rest = (q.data_ptr(), sc.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), n_outer, pixels, C, groups, eps, 1 if silu else 0, _stream())
+    if x2 is None:
+        check(lib().vcx_groupnorm_apply_mxfp8_f16(x.data_ptr(), *rest), "groupnorm_apply_mxfp8")
+    else:
+        check(lib().vcx_groupnorm_apply2_mxfp8_f16(x.data_ptr(), c1, x2.data_ptr(), *rest), "groupnorm_apply2_mxfp8")
     return q, sc
 
 
@@ -632,45 +629,47 @@ def group_norm_mxfp8_raw(x, gamma, beta, eps, silu, groups=32, stats=None, x2=No
     group_norm_mxfp8's, the second byte for byte quant_mxfp8 of the input rows themselves - with x2 of the channel concat [x | x2], which is
     never materialised (vcx_groupnorm_apply_mxfp8_raw_f16 / vcx_groupnorm_apply2_mxfp8_raw_f16).  The raw pair is the tail operand of
     conv3x3_tail_mxfp8.  Arguments as group_norm_mxfp8 (`stats` required with x2)."""
-    n_outer, pixels, c1 = x.shape
-    C = c1 + (0 if x2 is None else x2.shape[2])
-    _dev16(x, x2)
-    _dev32(gamma, beta, stats)
-    if not x.is_contiguous():
-        raise VcxError("group_norm_mxfp8_raw: a contiguous [n_outer, pixels, C] tensor needed")
-    if x2 is not None and (stats is None or tuple(x2.shape[:2]) != (n_outer, pixels) or c1 % 8 != 0 or C % 32 != 0 or not x2.is_contiguous()):
-        raise VcxError(f"group_norm_mxfp8_raw over a split concat needs statistics, contiguous halves, c1 % 8 == 0 and C % 32 == 0 "
-                       f"(x1 {tuple(x.shape)}, x2 {tuple(x2.shape)})")
-    L = lib()
-    s = _stream()
-    if stats is None:
-        stats = torch.empty((n_outer, groups, 2), dtype=_f32, device=x.device)
-        ws = torch.empty((L.vcx_groupnorm_ws_bytes(n_outer, pixels, groups),), dtype=torch.uint8, device=x.device)
-        check(L.vcx_groupnorm_stats_f16(x.data_ptr(), stats.data_ptr(), ws.data_ptr(), n_outer, pixels, C, groups, s), "groupnorm_stats")
+    n_outer, pixels, c1, C, stats = _group_norm_arg("group_norm_mxfp8_raw", x, x2, gamma, beta, stats, groups, quant=True)
     q, sc = _mx_buffers(n_outer * pixels, C, x.device)
     rq, rsc = _mx_buffers(n_outer * pixels, C, x.device)
+    rest = (q.data_ptr(), sc.data_ptr(), rq.data_ptr(), rsc.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), n_outer, pixels, C, groups, eps,
+            1 if silu else 0, _stream())
     if x2 is None:
-        check(L.vcx_groupnorm_apply_mxfp8_raw_f16(x.data_ptr(), q.data_ptr(), sc.data_ptr(), rq.data_ptr(), rsc.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
-                                                  beta.data_ptr(), n_outer, pixels, C, groups, eps, 1 if silu else 0, s), "groupnorm_apply_mxfp8_raw")
+        check(lib().vcx_groupnorm_apply_mxfp8_raw_f16(x.data_ptr(), *rest), "groupnorm_apply_mxfp8_raw")
     else:
-        check(L.vcx_groupnorm_apply2_mxfp8_raw_f16(x.data_ptr(), c1, x2.data_ptr(), q.data_ptr(), sc.data_ptr(), rq.data_ptr(), rsc.data_ptr(), stats.data_ptr(),
-                                                   gamma.data_ptr(), beta.data_ptr(), n_outer, pixels, C, groups, eps, 1 if silu else 0, s),
-              "groupnorm_apply2_mxfp8_raw")
+        check(lib().vcx_groupnorm_apply2_mxfp8_raw_f16(x.data_ptr(), c1, x2.data_ptr(), *rest), "groupnorm_apply2_mxfp8_raw")
     return (q, sc), (rq, rsc)
 
 
-def _t3_flags(residual, colstats):
-    return GEMM_BIAS_N | (GEMM_RESIDUAL if residual else 0) | (GEMM_COLSTATS if colstats else 0)
+def _mx_conv_flags(rowadd, residual, colstats):
+    return GEMM_BIAS_N | (GEMM_ROWADD if rowadd else 0) | (GEMM_RESIDUAL if residual else 0) | (GEMM_COLSTATS if colstats else 0)
+
+
+def _mx_conv_pitches(cout, ldc, residual, ldr, colstats, colstats_ld, colstats_col):
+    """(ldc, ldr, ldcs, first moments column) as an MXFP8 convolution's *_ok predicate sends them: the launcher's defaults, 0 for what a call
+    without a residual / without moments does not have."""
+    return (cout if ldc is None else ldc, (cout if ldr is None else ldr) if residual else 0,
+            (cout if colstats_ld is None else colstats_ld) if colstats else 0, colstats_col if colstats else 0)
+
+
+def _mx_conv_args(what, a, w, bias, M, cin, k_bytes, residual, ldr, out, ldc, colstats, colstats_ld, colstats_col):
+    """The checks and defaults the MXFP8 convolution launchers (`what`) share: activation pair [M, cin], weight pair with rows of k_bytes,
+    bias, residual, out / ldc, colstats*.  -> (cout, ldr, out, ldc, moments pointer, ldcs)"""
+    cout = w[0].shape[0]
+    _dev_mx(a, M, cin, what + " a")
+    _mx_weight_arg(w, cout, k_bytes, what + " w")
+    ldr = _mx_bias_residual_arg(bias, residual, ldr, M, cout, what)
+    _dev16(out)
+    out, ldc = _out_arg(out, ldc, M, cout, a[0], what=what)
+    return (cout, ldr, out, ldc) + _colstats_arg(colstats, colstats_ld, colstats_col, M, cout)
 
 
 def temporal_conv3_mxfp8_ok(B, T, P, cin, cout, *, residual=False, ldc=None, ldr=None, colstats=False, colstats_ld=None, colstats_col=0):
     """Does vcx_conv_t3_mxfp8 take a (3,1,1) convolution of B videos x T frames x P pixels x cin channels onto cout channels with these
     keywords (those of temporal_conv3_mxfp8: `residual` / `colstats` as booleans, pitches as that call would pass them)?  The library's
     answer - shape, flags, alignment, 32-bit extents; the reason of a refusal is in vcx_last_error()."""
-    ldc = cout if ldc is None else ldc
-    ldr = (cout if ldr is None else ldr) if residual else 0
-    ldcs = (cout if colstats_ld is None else colstats_ld) if colstats else 0
-    return lib().vcx_conv_t3_mxfp8_ok(B, T, P, cin, cout, ldc, ldr, ldcs, colstats_col if colstats else 0, _t3_flags(residual, colstats)) == 1
+    return lib().vcx_conv_t3_mxfp8_ok(B, T, P, cin, cout, *_mx_conv_pitches(cout, ldc, residual, ldr, colstats, colstats_ld, colstats_col),
+                                      _mx_conv_flags(False, residual, colstats)) == 1
 
 
 def temporal_conv3_mxfp8(a, w, bias, *, B, T, P, cin, residual=None, ldr=None, out=None, ldc=None, colstats=None, colstats_ld=None, colstats_col=0):
@@ -678,42 +677,11 @@ def temporal_conv3_mxfp8(a, w, bias, *, B, T, P, cin, residual=None, ldr=None, o
     [B * T * P, cin] (group_norm_mxfp8 / quant_mxfp8), w = the pair packing.pack_conv_t3_mxfp8 made of the Conv3d weight.  Returns fp16
     [B, T, P, cout] (or [.., ldc] when written into `out`); residual / out / ldc / colstats* as in gemm.  Shapes: temporal_conv3_mxfp8_ok -
     a call the kernel does not take is an error here, not a fall-back."""
-    M = B * T * P
-    kp = mx_kp(cin)
-    cout = w[0].shape[0]
-    _dev_mx(a, M, cin, "temporal_conv3_mxfp8 a")
-    for t, shape in ((w[0], (cout, 3 * kp)), (w[1], (cout, 3 * kp // 32))):
-        if t.dtype is not _u8 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
-            raise VcxError(f"temporal_conv3_mxfp8 w: expected contiguous GPU uint8 {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    _dev32(bias)
-    _dev16(residual, out)
-    if bias is None or bias.numel() != cout or not bias.is_contiguous():
-        raise VcxError(f"temporal_conv3_mxfp8: a contiguous fp32 bias [N = {cout}] is required")
-    if residual is not None:
-        if tuple(residual.shape) != (M, cout) or residual.stride(1) != 1:
-            raise VcxError(f"temporal_conv3_mxfp8: residual must be [{M}, {cout}] with unit column stride, got {tuple(residual.shape)}")
-        ldr = residual.stride(0) if ldr is None else ldr
-    if out is None:
-        out = torch.empty((M, cout), dtype=_f16, device=a[0].device)
-        ldc = cout
-    elif ldc is None:
-        ldc = out.stride(0)
-    if out.numel() < (M - 1) * ldc + cout:
-        raise VcxError(f"temporal_conv3_mxfp8: out holds {out.numel()} elements, [{M}] rows of pitch {ldc} need {(M - 1) * ldc + cout}")
-    cs_ptr, cld = None, 0
-    if colstats is not None:
-        _dev32(colstats)
-        cld = cout if colstats_ld is None else int(colstats_ld)
-        if colstats.numel() != (M // 64) * cld * 2 or colstats_col < 0 or colstats_col + cout > cld:
-            raise VcxError(f"colstats must hold [M / 64, {cld}, 2] floats (M={M}, N={cout}, first column {colstats_col}), got {tuple(colstats.shape)}")
-        cs_ptr = colstats.data_ptr() + 8 * int(colstats_col)
+    cout, ldr, out, ldc, cs_ptr, cld = _mx_conv_args("temporal_conv3_mxfp8", a, w, bias, B * T * P, cin, 3 * mx_kp(cin), residual, ldr, out, ldc, colstats,
+                                                     colstats_ld, colstats_col)
     check(lib().vcx_conv_t3_mxfp8(a[0].data_ptr(), a[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(), out.data_ptr(), bias.data_ptr(), _ptr(residual), cs_ptr,
-                                  B, T, P, cin, cout, ldc, ldr or 0, cld, _t3_flags(residual is not None, colstats is not None), _stream()), "conv_t3_mxfp8")
+                                  B, T, P, cin, cout, ldc, ldr, cld, _mx_conv_flags(False, residual is not None, colstats is not None), _stream()), "conv_t3_mxfp8")
     return out.view(B, T, P, -1)
-
-
-def _c9_flags(rowadd, residual, colstats):
-    return GEMM_BIAS_N | (GEMM_ROWADD if rowadd else 0) | (GEMM_RESIDUAL if residual else 0) | (GEMM_COLSTATS if colstats else 0)
 
 
 def conv3x3_mxfp8_ok(n, H, W, cin, cout, *, rowadd=False, rowadd_div=0, residual=False, ldc=None, ldr=None, colstats=False, colstats_ld=None,
@@ -721,11 +689,8 @@ def conv3x3_mxfp8_ok(n, H, W, cin, cout, *, rowadd=False, rowadd_div=0, residual
     """Does vcx_conv3x3_mxfp8 take a 3x3 / padding-1 convolution of n frames x H x W pixels x cin channels onto cout channels with these
     keywords (those of conv3x3_mxfp8: `rowadd` / `residual` / `colstats` as booleans, pitches as that call would pass them)?  The
     library's answer - shape, flags, alignment, 32-bit extents; the reason of a refusal is in vcx_last_error()."""
-    ldc = cout if ldc is None else ldc
-    ldr = (cout if ldr is None else ldr) if residual else 0
-    ldcs = (cout if colstats_ld is None else colstats_ld) if colstats else 0
-    return lib().vcx_conv3x3_mxfp8_ok(n, H, W, cin, cout, ldc, ldr, ldcs, colstats_col if colstats else 0, rowadd_div if rowadd else 0,
-                                      _c9_flags(rowadd, residual, colstats)) == 1
+    return lib().vcx_conv3x3_mxfp8_ok(n, H, W, cin, cout, *_mx_conv_pitches(cout, ldc, residual, ldr, colstats, colstats_ld, colstats_col),
+                                      rowadd_div if rowadd else 0, _mx_conv_flags(rowadd, residual, colstats)) == 1
 
 
 def conv3x3_mxfp8(a, w, bias, *, n, H, W, cin, rowadd=None, rowadd_div=0, residual=None, ldr=None, out=None, ldc=None, colstats=None,
@@ -735,43 +700,18 @@ def conv3x3_mxfp8(a, w, bias, *, n, H, W, cin, rowadd=None, rowadd_div=0, residu
     [n, H, W, cout] (or [.., ldc] when written into `out`); rowadd / rowadd_div / residual / out / ldc / colstats* as in gemm.  Shapes:
     conv3x3_mxfp8_ok - a call the kernel does not take is an error here, not a fall-back."""
     M = n * H * W
-    kp = mx_kp(cin)
-    cout = w[0].shape[0]
-    _dev_mx(a, M, cin, "conv3x3_mxfp8 a")
-    for t, shape in ((w[0], (cout, 9 * kp)), (w[1], (cout, 9 * kp // 32))):
-        if t.dtype is not _u8 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
-            raise VcxError(f"conv3x3_mxfp8 w: expected contiguous GPU uint8 {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    _dev32(bias, rowadd)
-    _dev16(residual, out)
-    if bias is None or bias.numel() != cout or not bias.is_contiguous():
-        raise VcxError(f"conv3x3_mxfp8: a contiguous fp32 bias [N = {cout}] is required")
+    cout, ldr, out, ldc, cs_ptr, cld = _mx_conv_args("conv3x3_mxfp8", a, w, bias, M, cin, 9 * mx_kp(cin), residual, ldr, out, ldc, colstats, colstats_ld,
+                                                     colstats_col)
     rld = 0
     if rowadd is not None:
+        _dev32(rowadd)
         if rowadd.dim() != 2 or rowadd.stride(1) != 1 or rowadd.shape[1] != cout or rowadd_div <= 0 or rowadd.shape[0] * rowadd_div < M:
             raise VcxError(f"conv3x3_mxfp8: rowadd must be [>= M / rowadd_div rows, N = {cout}] fp32 with unit column stride and rowadd_div > 0, "
                            f"got {tuple(rowadd.shape)}, rowadd_div={rowadd_div}, M={M}")
         rld = rowadd.stride(0) if rowadd.shape[0] > 1 else cout
-    if residual is not None:
-        if tuple(residual.shape) != (M, cout) or residual.stride(1) != 1:
-            raise VcxError(f"conv3x3_mxfp8: residual must be [{M}, {cout}] with unit column stride, got {tuple(residual.shape)}")
-        ldr = residual.stride(0) if ldr is None else ldr
-    if out is None:
-        out = torch.empty((M, cout), dtype=_f16, device=a[0].device)
-        ldc = cout
-    elif ldc is None:
-        ldc = out.stride(0)
-    if out.numel() < (M - 1) * ldc + cout:
-        raise VcxError(f"conv3x3_mxfp8: out holds {out.numel()} elements, [{M}] rows of pitch {ldc} need {(M - 1) * ldc + cout}")
-    cs_ptr, cld = None, 0
-    if colstats is not None:
-        _dev32(colstats)
-        cld = cout if colstats_ld is None else int(colstats_ld)
-        if colstats.numel() != (M // 64) * cld * 2 or colstats_col < 0 or colstats_col + cout > cld:
-            raise VcxError(f"colstats must hold [M / 64, {cld}, 2] floats (M={M}, N={cout}, first column {colstats_col}), got {tuple(colstats.shape)}")
-        cs_ptr = colstats.data_ptr() + 8 * int(colstats_col)
     check(lib().vcx_conv3x3_mxfp8(a[0].data_ptr(), a[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(), out.data_ptr(), bias.data_ptr(), _ptr(rowadd),
-                                  _ptr(residual), cs_ptr, n, H, W, cin, cout, ldc, ldr or 0, cld, rld, rowadd_div if rowadd is not None else 0,
-                                  _c9_flags(rowadd is not None, residual is not None, colstats is not None), _stream()), "conv3x3_mxfp8")
+                                  _ptr(residual), cs_ptr, n, H, W, cin, cout, ldc, ldr, cld, rld, rowadd_div if rowadd is not None else 0,
+                                  _mx_conv_flags(rowadd is not None, residual is not None, colstats is not None), _stream()), "conv3x3_mxfp8")
     return out.view(n, H, W, -1)
 
 
@@ -780,10 +720,9 @@ def conv3x3_tail_mxfp8_ok(n, H, W, cin, ct, cout, *, rowadd=False, residual=Fals
     a ct-channel tail onto cout channels with these keywords (those of conv3x3_tail_mxfp8, `colstats` as a boolean)?  `rowadd` / `residual`
     / `bias` exist to be asked about: the tailed form refuses a row addend, a residual and a missing bias.  The library's answer - shape,
     flags, alignment, 32-bit extents; the reason of a refusal is in vcx_last_error()."""
-    ldc = cout if ldc is None else ldc
-    ldcs = (cout if colstats_ld is None else colstats_ld) if colstats else 0
-    flags = _c9_flags(rowadd, residual, colstats) & ~(0 if bias else GEMM_BIAS_N)
-    return lib().vcx_conv3x3_tail_mxfp8_ok(n, H, W, cin, ct, cout, ldc, ldcs, colstats_col if colstats else 0, flags) == 1
+    ldc, _, ldcs, col = _mx_conv_pitches(cout, ldc, False, None, colstats, colstats_ld, colstats_col)
+    flags = _mx_conv_flags(rowadd, residual, colstats) & ~(0 if bias else GEMM_BIAS_N)
+    return lib().vcx_conv3x3_tail_mxfp8_ok(n, H, W, cin, ct, cout, ldc, ldcs, col, flags) == 1
 
 
 def conv3x3_tail_mxfp8(a, tail, w, bias, *, n, H, W, cin, ct, out=None, ldc=None, colstats=None, colstats_ld=None, colstats_col=0):
@@ -792,35 +731,12 @@ def conv3x3_tail_mxfp8(a, tail, w, bias, *, n, H, W, cin, ct, out=None, ldc=None
     (group_norm_mxfp8_raw's second output), w = the pair packing.pack_conv3x3_tail_mxfp8 made of the two weights, bias = the two biases
     summed.  Returns fp16 [n, H, W, cout] (or [.., ldc] when written into `out`); out / ldc / colstats* as in conv3x3_mxfp8; no rowadd, no
     residual.  Shapes: conv3x3_tail_mxfp8_ok - a call the kernel does not take is an error here, not a fall-back."""
-    M = n * H * W
-    kw = 9 * mx_kp(cin) + mx_kp(ct)
-    cout = w[0].shape[0]
-    _dev_mx(a, M, cin, "conv3x3_tail_mxfp8 a")
-    _dev_mx(tail, M, ct, "conv3x3_tail_mxfp8 tail")
-    for t, shape in ((w[0], (cout, kw)), (w[1], (cout, kw // 32))):
-        if t.dtype is not _u8 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
-            raise VcxError(f"conv3x3_tail_mxfp8 w: expected contiguous GPU uint8 {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    _dev32(bias)
-    _dev16(out)
-    if bias is None or bias.numel() != cout or not bias.is_contiguous():
-        raise VcxError(f"conv3x3_tail_mxfp8: a contiguous fp32 bias [N = {cout}] is required")
-    if out is None:
-        out = torch.empty((M, cout), dtype=_f16, device=a[0].device)
-        ldc = cout
-    elif ldc is None:
-        ldc = out.stride(0)
-    if out.numel() < (M - 1) * ldc + cout:
-        raise VcxError(f"conv3x3_tail_mxfp8: out holds {out.numel()} elements, [{M}] rows of pitch {ldc} need {(M - 1) * ldc + cout}")
-    cs_ptr, cld = None, 0
-    if colstats is not None:
-        _dev32(colstats)
-        cld = cout if colstats_ld is None else int(colstats_ld)
-        if colstats.numel() != (M // 64) * cld * 2 or colstats_col < 0 or colstats_col + cout > cld:
-            raise VcxError(f"colstats must hold [M / 64, {cld}, 2] floats (M={M}, N={cout}, first column {colstats_col}), got {tuple(colstats.shape)}")
-        cs_ptr = colstats.data_ptr() + 8 * int(colstats_col)
+    _dev_mx(tail, n * H * W, ct, "conv3x3_tail_mxfp8 tail")
+    cout, _, out, ldc, cs_ptr, cld = _mx_conv_args("conv3x3_tail_mxfp8", a, w, bias, n * H * W, cin, 9 * mx_kp(cin) + mx_kp(ct), None, None, out, ldc, colstats,
+                                                   colstats_ld, colstats_col)
     check(lib().vcx_conv3x3_tail_mxfp8(a[0].data_ptr(), a[1].data_ptr(), tail[0].data_ptr(), tail[1].data_ptr(), w[0].data_ptr(), w[1].data_ptr(),
                                        out.data_ptr(), bias.data_ptr(), cs_ptr, n, H, W, cin, ct, cout, ldc, cld,
-                                       _c9_flags(False, False, colstats is not None), _stream()), "conv3x3_tail_mxfp8")
+                                       _mx_conv_flags(False, False, colstats is not None), _stream()), "conv3x3_tail_mxfp8")
     return out.view(n, H, W, -1)
 
 
