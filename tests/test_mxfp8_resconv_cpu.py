@@ -369,12 +369,13 @@ def test_split_concat_without_moments_is_materialised(monkeypatch):
 def test_blocks_that_stay_on_fp16_make_the_calls_they_make_with_the_switch_off(monkeypatch, why):
     kw = dict(up=dict(up=True), down=dict(down=True), scale_shift=dict(use_scale_shift_norm=True)).get(why, {})
     cin = 48 if why == "cin" else 64           # (GroupNorm(32) wants cin % 32 == 0 for its groups; 48 % 32 != 0 would need 16 groups:
-    if why == "cin":                           #  the rule is checked on the route function directly)
+    if why == "cin":                           #  the rule is checked on the decision function directly)
         U, blk = _block(64)
         _switch(monkeypatch, U)
         rec = _Recorder(monkeypatch)
         x = torch.zeros((N_FRAMES, HH, WW, 48), dtype=torch.float16)
-        assert blk._forward_mx(x, torch.zeros((2, EMB), dtype=torch.float16), 2, False, None, None, None) is None and rec.calls == []
+        plan = blk._plan(x, torch.zeros((2, EMB), dtype=torch.float16), 2, False, None, None, None)
+        assert (plan.conv1, plan.conv2) == ("fp16", "fp16") and rec.calls == []
         return
     U, blk = _block(cin, **kw)
     rec = _Recorder(monkeypatch, accept=lambda q: False)

@@ -45,7 +45,7 @@ def block(H, W, c1, c2, cout):
     emb = torch.randn(B, EMB, device=DEV, generator=g).half()
     whole = (H * W) % 64 == 0
     cs_in = colstats_of(torch.cat([x, x2], dim=-1).view(M, cin)) if (c2 and whole) else None
-    inplace = cs_in is not None          # the concat is read in place where its moments exist (ResBlock._forward_mx), else materialised once
+    inplace = cs_in is not None          # the concat is read in place where its moments exist (ResBlock._plan), else materialised once
     gn1 = blk.in_layers[0]
     gw, gb = gn1.weight.detach().float(), gn1.bias.detach().float()
     xc = x if x2 is None else torch.cat([x, x2], dim=-1).contiguous()

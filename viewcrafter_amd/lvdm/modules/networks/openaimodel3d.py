@@ -14,6 +14,7 @@ MI355X-first differences from the reference implementation (none changes the res
 There is no PyTorch compute fallback: without libvcx.so and a gfx950 device forward() raises.
 """
 import os
+from collections import namedtuple
 
 import torch
 from torch import nn
@@ -201,6 +202,23 @@ class Upsample(PackedModule):
         return ops.conv2d(x, pk["w"], pk["b"], kh=3, kw=3, ups=1, **kw), cs
 
 
+def _moments_ok(engine, M, pixels, cin, cout, in_rows=None):
+    """May a ResBlock convolution of `engine` write the column moments of its [M, cout] output for a GroupNorm whose statistics span
+    `pixels` rows?  The rule differs per engine: the fp16 one asks its dispatcher (ops.colstats_ok); an MX one applies the host graph's
+    rule - whole 64-row strips per statistics unit - and hands the answer to its own predicate as `colstats`."""
+    if not GN_EPILOGUE_STATS:
+        return False
+    return ops.colstats_ok(M, pixels, cin, cout, in_rows=in_rows) if engine == "fp16" else pixels % 64 == 0
+
+
+def _with_moments_buffer(kw, M, cout, device):
+    """A convolution's output keywords with their moments request served: `colstats=True` - decided before anything ran, so no buffer
+    yet - becomes a fresh buffer.  -> (keywords for the launch, the moments its output's GroupNorm can use or None)"""
+    if kw.get("colstats") is True:
+        kw = dict(kw, colstats=ops.colstats_buffer(M, cout, device))
+    return kw, kw.get("colstats")
+
+
 class TemporalConvBlock(PackedModule):
     """Reference openaimodel3d.py:239-279: 4 x [GroupNorm(32) over (C/32, T, H, W) -> SiLU -> Conv3d (3,1,1)] + identity.
     Module indices follow the reference (conv1: conv at .2; conv2-4: Dropout at .2, conv at .3)."""
@@ -261,56 +279,47 @@ class TemporalConvBlock(PackedModule):
             plan.append(kw)
         return plan
 
-    def _forward_mx(self, x, colstats, plan):
-        """The block on the MX route: per stage one quantising GroupNorm + SiLU apply and one gathered convolution; statistics, moments,
-        concat target and the residual of the last stage as on the fp16 route."""
-        B, T, P, C = x.shape
-        stages = self.packed()
-        if self._mx is None:
-            with torch.no_grad():
-                self._mx = [tuple(t.to(x.device) for t in pack_conv_t3_mxfp8(seq[-1].weight.detach())) for seq in (self.conv1, self.conv2, self.conv3, self.conv4)]
-        y = x
-        for i, ((gw, gb, eps, w, b), wmx, kw) in enumerate(zip(stages, self._mx, plan)):
-            cy = y.shape[-1]
-            stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, B, T * P, cy)
-            a = ops.group_norm_mxfp8(y.reshape(B, T * P, cy), gw, gb, eps, True, stats=stats)
-            last = i == len(stages) - 1
-            kw = dict(kw)
-            if kw.get("colstats") is True:
-                kw["colstats"] = ops.colstats_buffer(B * T * P, w.shape[0], x.device)
-            colstats = kw.get("colstats")
-            y = ops.temporal_conv3_mxfp8(a, wmx, b, B=B, T=T, P=P, cin=cy, residual=x.reshape(B * T * P, C) if last else None, **kw)
-        return y, colstats
-
     def forward(self, x, colstats=None, want_colstats=False, target=None):
         """x [B, T, P, C] fp16.  `colstats`: column moments of x written by the layer that produced it (ops.gemm colstats=):
         the first norm then needs no statistics pass; the three inner norms get theirs from this block's own convolutions.
         want_colstats: also produce the moments of the OUTPUT (for the per-frame GroupNorm behind this block); target: write the
-        output (and its moments) into a concat buffer.  -> (y, moments of y or None)"""
+        output (and its moments) into a concat buffer.  -> (y, moments of y or None)
+        One loop for both engines: with a plan (_mx_plan) each stage is one quantising GroupNorm + SiLU apply and one gathered MX
+        convolution with the plan's keywords, without one the fp16 pair; statistics, moments, concat target and the residual of the
+        last stage are the same on both."""
         B, T, P, C = x.shape
-        if TCONV_MXFP8:
-            plan = self._mx_plan(B, T, P, want_colstats, target)
-            if plan is not None:
-                return self._forward_mx(x, colstats, plan)
-        y = x
+        M = B * T * P
+        plan = self._mx_plan(B, T, P, want_colstats, target) if TCONV_MXFP8 else None
         stages = self.packed()
+        if plan is not None and self._mx is None:
+            with torch.no_grad():
+                self._mx = [tuple(t.to(x.device) for t in pack_conv_t3_mxfp8(seq[-1].weight.detach())) for seq in (self.conv1, self.conv2, self.conv3, self.conv4)]
+        y = x
         for i, (gw, gb, eps, w, b) in enumerate(stages):
-            cy = y.shape[-1]
-            stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, B, T * P, cy)
-            a = ops.group_norm(y.reshape(B, T * P, cy), gw, gb, eps, True, stats=stats)
+            cy, cout = y.shape[-1], w.shape[0]
             last = i == len(stages) - 1
-            cout = w.shape[0]
-            kw = {}
-            if last and target is not None:
-                kw = target.kwargs(cy, B * T * P)
-                colstats = target.moments
+            stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, B, T * P, cy)
+            a = (ops.group_norm if plan is None else ops.group_norm_mxfp8)(y.reshape(B, T * P, cy), gw, gb, eps, True, stats=stats)
+            if plan is not None:
+                kw = plan[i]
+            elif last and target is not None:
+                kw = target.kwargs(cy, M)
+            else:       # the fp16 engine's moment rule: the dispatcher's answer for the statistics unit (T P rows; P behind the block)
+                need = (want_colstats if last else True) and ops.colstats_ok(M, P if last else T * P, cy, cout)
+                kw = dict(colstats=True) if GN_EPILOGUE_STATS and need else {}
+            kw, colstats = _with_moments_buffer(kw, M, cout, x.device)
+            residual = x.reshape(M, C) if last else None
+            if plan is None:
+                y = ops.temporal_conv3(a.view(B, T, P, -1), w, b, residual=residual, **kw)
             else:
-                need = (not last and ops.colstats_ok(B * T * P, T * P, cy, cout)) or (last and want_colstats and ops.colstats_ok(B * T * P, P, cy, cout))
-                colstats = ops.colstats_buffer(B * T * P, cout, x.device) if (GN_EPILOGUE_STATS and need) else None
-                if colstats is not None:
-                    kw = dict(colstats=colstats)
-            y = ops.temporal_conv3(a.view(B, T, P, -1), w, b, residual=x.reshape(B * T * P, C) if last else None, **kw)
+                y = ops.temporal_conv3_mxfp8(a, self._mx[i], b, B=B, T=T, P=P, cin=cy, residual=residual, **kw)
         return y, colstats
+
+
+# What ResBlock._plan decides: how a split concat [x | x2] enters (None: there is none; "inplace": both halves are read where they are; "copy":
+# materialised), whether the 1x1 skip convolution rides as the K tail of the fp16 second convolution, the engine of each 3x3 convolution
+# ("fp16" / "mx"; the second also "mx_tail": MX with the skip as its K tail) and the second convolution's output keywords (_out_kw).
+ResPlan = namedtuple("ResPlan", "concat fold_skip conv1 conv2 kw2")
 
 
 class ResBlock(PackedModule, TimestepBlock):
@@ -367,102 +376,63 @@ class ResBlock(PackedModule, TimestepBlock):
                 self._mx["w2s"] = tuple(t.to(device) for t in pack_conv3x3_tail_mxfp8(self.out_layers[3].weight.detach(), self.skip_connection.weight.detach()))
         return self._mx["w2s"]
 
-    def _forward_mx(self, x, emb, batch_size, want_colstats, colstats, target, x2):
-        """RESCONV_MXFP8: the block with one or both 3x3 convolutions on the MX route, or None - the block stays on the fp16 route,
-        nothing launched - where the library's predicate takes neither.  Each convolution is decided on its own, asked about ONE
-        video's frames (a row's route must not depend on the batch it runs in) and about the call's (only the 32-bit extents depend on
-        n); the GroupNorm + SiLU apply in front of a convolution is the quantising one iff that convolution is MX.  Moments are asked
-        for where the host graph's rule allows them: whole 64-row strips per statistics unit.  A block with a skip convolution keeps
-        its second convolution on the fp16 engine with the folded K tail under RESCONV_MXFP8_KEEP_FOLD, and wherever the skip's input
-        is a split concat read in place (the K tail takes two sources, a separate skip convolution does not); otherwise the second
-        convolution is MX with the fp16 skip convolution's result as its residual.  RESCONV_MXFP8_TAIL (KEEP_FOLD off): a block with a
-        skip convolution whose first convolution is MX and whose tailed second convolution the library takes with the call's keywords
-        runs the skip as the K tail of the MX second convolution, fed by the raw output of the quantising apply in front of the first -
-        over both halves where the concat is read in place; decided, like everything here, before anything is launched."""
+    def _out_kw(self, engine, n, H, W, batch_size, want_colstats, target):
+        """The output keywords of the block's last 3x3 convolution (`colstats=True`: moments wanted, the buffer comes later): moments per
+        video for the first norm of the temporal block behind it; else the concat target's; else moments per frame where the caller
+        wants them.  `engine` picks the moment rule (_moments_ok)."""
+        cout, M = self.out_channels, n * H * W
+        if self.use_temporal_conv and batch_size:
+            wanted, pixels = True, (n // batch_size) * H * W
+        elif target is not None:
+            return target.kwargs(cout, M)
+        else:
+            wanted, pixels = want_colstats, H * W
+        return dict(colstats=True) if wanted and _moments_ok(engine, M, pixels, cout, cout) else {}
+
+    def _plan(self, x, emb, batch_size, want_colstats, colstats, target, x2):
+        """Every routing decision of one forward, made before anything is launched or allocated -> ResPlan.
+        The concat [x | x2] is read in place where the kernels can (statistics from `colstats`, the skip convolution folded as a K tail
+        of two sources) and materialised otherwise.  RESCONV_MXFP8: each 3x3 convolution is decided on its own, asked about ONE video's
+        frames (a row's route must not depend on the batch it runs in) and about the call's (only the 32-bit extents depend on n); up /
+        down blocks, scale-shift norm, a skipped width, cin % 32 != 0 and a strided x (the quantising apply reads dense rows) stay on
+        fp16 unasked.  A block with a skip convolution keeps its second convolution on the fp16 engine with the folded K tail under
+        RESCONV_MXFP8_KEEP_FOLD, and wherever the skip's input is a split concat read in place (the K tail takes two sources, a separate
+        skip convolution does not); otherwise the second convolution is MX with the fp16 skip convolution's result as its residual.
+        RESCONV_MXFP8_TAIL (KEEP_FOLD off): a block with a skip convolution whose first convolution is MX and whose tailed second
+        convolution the library takes with the call's keywords runs the skip as the K tail of the MX second convolution, fed by the raw
+        output of the quantising apply in front of the first - over both halves where the concat is read in place."""
         n, H, W, c1 = x.shape
         cin = c1 + (0 if x2 is None else x2.shape[-1])
         cout = self.out_channels
-        if cin % 32 != 0 or not x.is_contiguous():      # (the quantising apply reads dense rows; a strided view stays on the fp16 route)
-            return None
-        pk = self.packed()
-        has_skip = "ws" in pk
-        B = emb.shape[0]
-        M, fpv = n * H * W, n // B
-        fold_skip = SKIP_FOLD and has_skip and ops.conv_tail_ok(M, cout, cout, 9, [cin] if x2 is None else [c1, cin - c1])
-        inplace = x2 is not None and fold_skip and colstats is not None and c1 % 8 == 0 and x2.is_contiguous()
-        if x2 is not None and not inplace:
-            fold_skip = SKIP_FOLD and has_skip and ops.conv_tail_ok(M, cout, cout, 9, [cin])
-        frames = sorted({fpv, n})
-        cs1_mx = GN_EPILOGUE_STATS and (H * W) % 64 == 0
-        mx1 = all(ops.conv3x3_mxfp8_ok(f, H, W, cin, cout, rowadd=True, rowadd_div=fpv * H * W, colstats=cs1_mx) for f in frames)
-        temporal = self.use_temporal_conv and batch_size
-        if temporal:
-            kw2 = dict(colstats=True) if GN_EPILOGUE_STATS and ((n // batch_size) * H * W) % 64 == 0 else {}
-        elif target is not None:
-            kw2 = target.kwargs(cout, M)
-        else:
-            kw2 = dict(colstats=True) if GN_EPILOGUE_STATS and want_colstats and (H * W) % 64 == 0 else {}
-        mx2 = (not has_skip or (not RESCONV_MXFP8_KEEP_FOLD and not inplace)) and all(
-            ops.conv3x3_mxfp8_ok(f, H, W, cout, cout, residual=True, ldr=cout, ldc=kw2.get("ldc"), colstats="colstats" in kw2,
-                                 colstats_ld=kw2.get("colstats_ld"), colstats_col=kw2.get("colstats_col", 0)) for f in frames)
-        tail = RESCONV_MXFP8_TAIL and has_skip and not RESCONV_MXFP8_KEEP_FOLD and mx1 and all(
-            ops.conv3x3_tail_mxfp8_ok(f, H, W, cout, cin, cout, ldc=kw2.get("ldc"), colstats="colstats" in kw2, colstats_ld=kw2.get("colstats_ld"),
-                                      colstats_col=kw2.get("colstats_col", 0)) for f in frames)
-        if not (mx1 or mx2):
-            return None
-        if x2 is not None and not inplace:
-            x, x2 = ops.concat_channels(x.reshape(M, c1), x2.reshape(M, cin - c1)).view(n, H, W, -1), None      # the materialised concat
-        stats_in = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, H * W, cin)
-        xin, x2in = x.view(n, H * W, -1), None if x2 is None else x2.view(n, H * W, -1)
-        if tail:
-            a, xq = ops.group_norm_mxfp8_raw(xin, *pk["g1"], True, stats=stats_in, x2=x2in)
-        else:
-            a = (ops.group_norm_mxfp8 if mx1 else ops.group_norm)(xin, *pk["g1"], True, stats=stats_in, x2=x2in)
-        emb_out = self._emb_all[:B] if self._emb_all is not None else ops.linear(emb, pk["we"], pk["be"], out_f32=True)
-        if mx1:
-            cs1 = ops.colstats_buffer(M, cout, x.device) if cs1_mx else None
-            h = ops.conv3x3_mxfp8(a, self._mx_weight("w1", self.in_layers[2], x.device), pk["b1"], n=n, H=H, W=W, cin=cin, rowadd=emb_out,
-                                  rowadd_div=fpv * H * W, colstats=cs1)
-        else:
-            cs1 = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and ops.colstats_ok(M, H * W, cin, cout, in_rows=M)) else None
-            h = ops.conv2d(a.view(n, H, W, cin), pk["w1"], pk["b1"], kh=3, kw=3, rowadd=emb_out, rowadd_div=fpv * H * W, colstats=cs1)
-        stats = None if cs1 is None else ops.group_norm_stats_from_colstats(cs1, n, H * W, cout)
-        if tail:
-            a = ops.group_norm_mxfp8(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
-            kw2 = dict(kw2)
-            if kw2.get("colstats") is True:
-                kw2["colstats"] = ops.colstats_buffer(M, cout, x.device)
-            cs_out = kw2.get("colstats")
-            h = ops.conv3x3_tail_mxfp8(a, tail=xq, w=self._mx_tail_weight(x.device), bias=pk["b2s"], n=n, H=H, W=W, cin=cout, ct=cin, **kw2)
-        elif mx2:
-            a = ops.group_norm_mxfp8(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
-            residual = ops.conv2d(x, pk["ws"], pk["bs"], kh=1, kw=1).view(M, cout) if has_skip else x.reshape(M, cout)
-            kw2 = dict(kw2)
-            if kw2.get("colstats") is True:
-                kw2["colstats"] = ops.colstats_buffer(M, cout, x.device)
-            cs_out = kw2.get("colstats")
-            h = ops.conv3x3_mxfp8(a, self._mx_weight("w2", self.out_layers[3], x.device), pk["b2"], n=n, H=H, W=W, cin=cout, residual=residual, **kw2)
-        else:
-            a = ops.group_norm(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
-            if fold_skip:
-                w2, b2 = pk["w2s"], pk["b2s"]
-                skip_kw = dict(tail=[x.reshape(M, -1)] + ([] if x2 is None else [x2.reshape(M, -1)]))
-            else:
-                w2, b2 = pk["w2"], pk["b2"]
-                skip_kw = dict(residual=ops.conv2d(x, pk["ws"], pk["bs"], kh=1, kw=1).view(M, cout) if has_skip else x.reshape(M, cout))
-            if temporal:
-                cs_out = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and ops.colstats_ok(M, (n // batch_size) * H * W, cout, cout)) else None
-                kw2 = {} if cs_out is None else dict(colstats=cs_out)
-            elif target is not None:
-                cs_out = target.moments
-            else:
-                cs_out = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and want_colstats and ops.colstats_ok(M, H * W, cout, cout)) else None
-                kw2 = {} if cs_out is None else dict(colstats=cs_out)
-            h = ops.conv2d(a.view(n, H, W, cout), w2, b2, kh=3, kw=3, **skip_kw, **kw2)
-        if temporal:
-            h, cs_out = self.temopral_conv(h.view(batch_size, n // batch_size, H * W, cout), colstats=cs_out, want_colstats=want_colstats, target=target)
-            return h.view(n, H, W, -1), cs_out
-        return h, cs_out
+        has_skip = not isinstance(self.skip_connection, nn.Identity)
+        fold = lambda rows, tail_ks: SKIP_FOLD and has_skip and ops.conv_tail_ok(rows, cout, cout, 9, tail_ks)
+        fold_skip = fold(n * H * W, [cin] if x2 is None else [c1, cin - c1])
+        concat = None
+        if x2 is not None:
+            concat = "inplace" if fold_skip and colstats is not None and c1 % 8 == 0 and x.is_contiguous() and x2.is_contiguous() else "copy"
+            if concat == "copy":
+                fold_skip = fold(n * H * W, [cin])
+        if self.updown:       # the convolutions run on the sampled grid
+            H, W = (2 * H, 2 * W) if self.up else (H // 2, W // 2)
+            fold_skip = fold(n * H * W, [cin])
+        conv1 = conv2 = "fp16"
+        if (RESCONV_MXFP8 and not self.updown and not self.use_scale_shift_norm and cout not in RESCONV_MXFP8_SKIP_DIMS
+                and cin % 32 == 0 and x.is_contiguous()):
+            fpv = n // emb.shape[0]
+            frames = sorted({fpv, n})
+            kw2 = self._out_kw("mx", n, H, W, batch_size, want_colstats, target)
+            out2 = dict(ldc=kw2.get("ldc"), colstats="colstats" in kw2, colstats_ld=kw2.get("colstats_ld"), colstats_col=kw2.get("colstats_col", 0))
+            mx1 = all(ops.conv3x3_mxfp8_ok(f, H, W, cin, cout, rowadd=True, rowadd_div=fpv * H * W, colstats=_moments_ok("mx", n * H * W, H * W, cin, cout))
+                      for f in frames)
+            mx2 = (not has_skip or (not RESCONV_MXFP8_KEEP_FOLD and concat != "inplace")) and all(
+                ops.conv3x3_mxfp8_ok(f, H, W, cout, cout, residual=True, ldr=cout, **out2) for f in frames)
+            tail = RESCONV_MXFP8_TAIL and has_skip and not RESCONV_MXFP8_KEEP_FOLD and mx1 and all(
+                ops.conv3x3_tail_mxfp8_ok(f, H, W, cout, cin, cout, **out2) for f in frames)
+            conv1, conv2 = "mx" if mx1 else "fp16", "mx_tail" if tail else "mx" if mx2 else "fp16"
+        if conv2 == "fp16":
+            kw2 = self._out_kw("fp16", n, H, W, batch_size, want_colstats, target)
+        return ResPlan(concat, fold_skip and conv2 == "fp16", conv1, conv2, kw2)
+
 
     def _pack(self):
         gn1, c1 = self.in_layers[0], self.in_layers[2]
@@ -488,24 +458,23 @@ class ResBlock(PackedModule, TimestepBlock):
         needs no statistics pass); want_colstats: produce the moments of the output for a per-frame GroupNorm behind this block
         (SpatialTransformer.norm, the next block's in_layers); target: write output and moments into a concat buffer.
         -> (h, moments of h or None)"""
-        if RESCONV_MXFP8 and not self.updown and not self.use_scale_shift_norm and self.out_channels not in RESCONV_MXFP8_SKIP_DIMS:
-            routed = self._forward_mx(x, emb, batch_size, want_colstats, colstats, target, x2)
-            if routed is not None:
-                return routed
-        n, H, W, cin = x.shape
+        plan = self._plan(x, emb, batch_size, want_colstats, colstats, target, x2)
+        mx1, mx2, tail = plan.conv1 == "mx", plan.conv2 != "fp16", plan.conv2 == "mx_tail"
+        n, H, W, c1 = x.shape
         pk = self.packed()
         cout = self.out_channels
         B = emb.shape[0]
-        M = n * H * W
-        tail_ks = [cin] if x2 is None else [cin, x2.shape[-1]]
-        fold_skip = SKIP_FOLD and "ws" in pk and ops.conv_tail_ok(M, cout, cout, 9, tail_ks)
-        if x2 is not None and not (fold_skip and colstats is not None and cin % 8 == 0 and x.is_contiguous() and x2.is_contiguous()):
-            x, x2 = ops.concat_channels(x.reshape(M, cin), x2.reshape(M, x2.shape[-1])).view(n, H, W, -1), None      # the materialised concat
-            tail_ks = [x.shape[-1]]
-            fold_skip = SKIP_FOLD and "ws" in pk and ops.conv_tail_ok(M, cout, cout, 9, tail_ks)
-        c1, cin = cin, sum(tail_ks) if x2 is not None else x.shape[-1]
+        M, fpv = n * H * W, n // B
+        if plan.concat == "copy":
+            x, x2 = ops.concat_channels(x.reshape(M, c1), x2.reshape(M, x2.shape[-1])).view(n, H, W, -1), None      # the materialised concat
+        cin = x.shape[-1] + (0 if x2 is None else x2.shape[-1])
         stats_in = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, H * W, cin)
-        a = ops.group_norm(x.view(n, H * W, c1 if x2 is not None else cin), *pk["g1"], True, stats=stats_in, x2=None if x2 is None else x2.view(n, H * W, -1))
+        # the GroupNorm + SiLU apply in front of a convolution is the quantising one iff that convolution is MX; in front of a tailed
+        # second convolution the first one also writes quant(x), the tail's one source
+        norm1 = ops.group_norm_mxfp8_raw if tail else ops.group_norm_mxfp8 if mx1 else ops.group_norm
+        a = norm1(x.view(n, H * W, -1), *pk["g1"], True, stats=stats_in, x2=None if x2 is None else x2.view(n, H * W, -1))
+        if tail:
+            a, xq = a
         conv1_kw = {}
         if self.updown:
             if x2 is not None:
@@ -516,51 +485,50 @@ class ResBlock(PackedModule, TimestepBlock):
             else:
                 a, x, H, W = ops.avgpool2x2(a), ops.avgpool2x2(x), H // 2, W // 2
             M = n * H * W
-            fold_skip = SKIP_FOLD and "ws" in pk and ops.conv_tail_ok(M, cout, cout, 9, [cin])
         # [B, Cout] fp32: this block's columns of the one projection UNetModel made of the embedding, or its own launch (a block used alone)
         emb_out = self._emb_all[:B] if self._emb_all is not None else ops.linear(emb, pk["we"], pk["be"], out_f32=True)
         # The norms behind this block's own convolutions take their statistics from those convolutions' epilogues (column moments
         # per 64-row strip, VCX_GEMM_COLSTATS) instead of a pass over the tensor: out_layers' norm (per frame) from conv 1, the
         # first norm of the temporal block (per video) from conv 2 - where frames are whole strips (not at 9x16 = 144 pixels).
         hin, win = a.shape[1:3] if self.updown else (H, W)       # the first convolution's INPUT grid (up: half the output's)
-        cs1 = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and ops.colstats_ok(M, H * W, cin, cout, in_rows=n * hin * win)) else None
+        cs1 = ops.colstats_buffer(M, cout, x.device) if _moments_ok(plan.conv1, M, H * W, cin, cout, in_rows=n * hin * win) else None
+        if mx1:
+            h = ops.conv3x3_mxfp8(a, self._mx_weight("w1", self.in_layers[2], x.device), pk["b1"], n=n, H=H, W=W, cin=cin, rowadd=emb_out,
+                                  rowadd_div=fpv * H * W, colstats=cs1)
+        else:       # (scale-shift: the embedding enters through the second norm instead)
+            rowadd_kw = {} if self.use_scale_shift_norm else dict(rowadd=emb_out, rowadd_div=fpv * H * W)
+            h = ops.conv2d(a.view(n, hin, win, cin), pk["w1"], pk["b1"], kh=3, kw=3, colstats=cs1, **rowadd_kw, **conv1_kw)
+        stats = None if cs1 is None else ops.group_norm_stats_from_colstats(cs1, n, H * W, cout)
         if not self.use_scale_shift_norm:
-            h = ops.conv2d(a.view(n, hin, win, cin), pk["w1"], pk["b1"], kh=3, kw=3, rowadd=emb_out, rowadd_div=(n // B) * H * W, colstats=cs1, **conv1_kw)
-            stats = None if cs1 is None else ops.group_norm_stats_from_colstats(cs1, n, H * W, cout)
-            a = ops.group_norm(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
+            a = (ops.group_norm_mxfp8 if mx2 else ops.group_norm)(h.view(n, H * W, cout), *pk["g2"], True, stats=stats)
         else:
             # norm(h) * (1 + scale) + shift with (scale, shift) = the two halves of emb_out, one pair per video: the GroupNorm's
             # affine parameters of that video become gamma (1 + scale) and beta (1 + scale) + shift ([C] vectors, a few hundred
             # floats of host-side plumbing per video), the statistics are untouched
-            h = ops.conv2d(a.view(n, hin, win, cin), pk["w1"], pk["b1"], kh=3, kw=3, colstats=cs1, **conv1_kw)
-            stats = None if cs1 is None else ops.group_norm_stats_from_colstats(cs1, n, H * W, cout)
-            h3, a, fpv = h.view(n, H * W, cout), torch.empty((n, H * W, cout), dtype=torch.float16, device=x.device), n // B
+            h3, a = h.view(n, H * W, cout), torch.empty((n, H * W, cout), dtype=torch.float16, device=x.device)
             gam, bet, eps = pk["g2"]
             for v in range(B):
                 sc1 = 1.0 + emb_out[v, :cout]
                 ops.group_norm(h3[v * fpv:(v + 1) * fpv], (gam * sc1).contiguous(), (bet * sc1 + emb_out[v, cout:]).contiguous(), eps, True,
                                stats=None if stats is None else stats[v * fpv:(v + 1) * fpv], out=a[v * fpv:(v + 1) * fpv])
-        if fold_skip:       # skip_connection(x) rides in the K loop of the second convolution: x (both halves of a split concat) is its K tail
+        if tail:                 # skip_connection(x) rides in the K loop of the MX second convolution: quant(x), of the whole concat, is its K tail
+            w2, b2, skip_kw = self._mx_tail_weight(x.device), pk["b2s"], dict(tail=xq)
+        elif plan.fold_skip:     # ... of the fp16 second convolution: x (both halves of a split concat) is its K tail
             w2, b2 = pk["w2s"], pk["b2s"]
             skip_kw = dict(tail=[x.reshape(M, -1)] + ([] if x2 is None else [x2.reshape(M, -1)]))
         else:
-            w2, b2 = pk["w2"], pk["b2"]
+            w2, b2 = self._mx_weight("w2", self.out_layers[3], x.device) if mx2 else pk["w2"], pk["b2"]
             skip_kw = dict(residual=ops.conv2d(x, pk["ws"], pk["bs"], kh=1, kw=1).view(M, cout) if "ws" in pk else x.reshape(M, cout))
-        temporal = self.use_temporal_conv and batch_size
-        if temporal:
-            need2 = ops.colstats_ok(M, (n // batch_size) * H * W, cout, cout)
-            cs2 = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and need2) else None
-            h = ops.conv2d(a.view(n, H, W, cout), w2, b2, kh=3, kw=3, colstats=cs2, **skip_kw)
-            h, cs_out = self.temopral_conv(h.view(batch_size, n // batch_size, H * W, cout), colstats=cs2, want_colstats=want_colstats,
-                                           target=target)
-            return h.view(n, H, W, -1), cs_out
-        if target is not None:
-            kw = target.kwargs(cout, M)
-            cs_out = target.moments
+        kw2, cs_out = _with_moments_buffer(plan.kw2, M, cout, x.device)
+        if tail:
+            h = ops.conv3x3_tail_mxfp8(a, w=w2, bias=b2, n=n, H=H, W=W, cin=cout, ct=cin, **skip_kw, **kw2)
+        elif mx2:
+            h = ops.conv3x3_mxfp8(a, w2, b2, n=n, H=H, W=W, cin=cout, **skip_kw, **kw2)
         else:
-            cs_out = ops.colstats_buffer(M, cout, x.device) if (GN_EPILOGUE_STATS and want_colstats and ops.colstats_ok(M, H * W, cout, cout)) else None
-            kw = {} if cs_out is None else dict(colstats=cs_out)
-        h = ops.conv2d(a.view(n, H, W, cout), w2, b2, kh=3, kw=3, **skip_kw, **kw)
+            h = ops.conv2d(a.view(n, H, W, cout), w2, b2, kh=3, kw=3, **skip_kw, **kw2)
+        if self.use_temporal_conv and batch_size:
+            h, cs_out = self.temopral_conv(h.view(batch_size, n // batch_size, H * W, cout), colstats=cs_out, want_colstats=want_colstats, target=target)
+            h = h.view(n, H, W, -1)
         return h, cs_out
 
 
