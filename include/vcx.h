@@ -402,6 +402,11 @@ int vcx_conv3x3_tail_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int6
  *   V^T rows : vt + (h*64)*ldvt + (g / kv_div)*kv_rows       64 rows (d) x nk cols (keys)
  *   O rows   : o  + (g*nq)*ldo + h*64
  * kv_rows is the row count between consecutive K/V groups (>= nk, multiple of 8).
+ * Pitches and alignment (this entry point, the dual form and vcx_attn_flash_d512_f16 alike; anything else is refused with -1 before
+ * a launch; tests/test_attn_layouts_cpu.py pins the rules, tests/test_attn_layouts_gpu.py runs every kernel at their edge): q, k and
+ * vt (k1 / vt1 / k2 / vt2) are 16-byte aligned and ldq, ldk, ldvt multiples of 8 - rows are fetched in 16-byte pieces; o needs only
+ * 8-byte alignment and ldo % 4 == 0 - the flash kernels store 8 bytes per lane.  The pitches are otherwise free (a window of a
+ * wider buffer; ldvt beyond n_kv_groups * kv_rows); nothing outside the addressed rows x columns is read or written.
  * Padding (this entry point, the dual form and vcx_attn_flash_d512_f16 alike; tests/test_exact_gpu.py poisons it): K rows [nk, kv_rows)
  * and V^T columns from the next multiple of 8 above nk up to kv_rows are never used, whatever they hold - NaN and Inf included.  The V^T
  * columns [nk, (nk + 7) & ~7) are fetched with their 16-byte piece and meet a probability of exactly 0 on the matrix pipe: they must
@@ -413,7 +418,7 @@ int vcx_conv3x3_tail_mxfp8_ok(int64_t n, int64_t H, int64_t W, int64_t Cin, int6
  * Q K^T is already the base-2 logit - `scale` is then ignored and the kernel saves one
  * multiply-add per score.
  * Two kernels sit behind this entry point: with VCX_ATTN_LOG2_LOGITS, nk a multiple of 64,
- * nk >= 4096 and no VCX_ATTN_ACCUMULATE the software-pipelined one-wave-per-SIMD kernel
+ * nk >= 2048 and no VCX_ATTN_ACCUMULATE the software-pipelined one-wave-per-SIMD kernel
  * (csrc/attention_v2.hip), otherwise the phased kernel (csrc/attention.hip); same contract,
  * results agree to fp16 rounding (different summation order).  Knob VCX_TUNE_FLASH_IMPL.
  * Rounding points (every attention entry point; tests/rounding_quality.py MODELS holds them with their source lines and
@@ -439,7 +444,10 @@ int vcx_attn_flash_d64_f16(const void* q, const void* k, const void* vt, void* o
  * for the second as PACKED FP16 - in registers, or parked in LDS by the LDS-resident kernels, which have room for no more - and the sum
  * of that and the fp32 second result is rounded: one rounding point more than the single form (like VCX_ATTN_ACCUMULATE, without
  * the trip through memory).  Only the flash kernel's form with one query block per wave (nq small against 256-row blocks, or knob
- * FLASH_QB = 1 with XATTN_RESIDENT = 0) keeps the first result in fp32 and rounds once.  flags: VCX_ATTN_LOG2_LOGITS. */
+ * FLASH_QB = 1 with XATTN_RESIDENT = 0) keeps the first result in fp32 and rounds once.  flags: VCX_ATTN_LOG2_LOGITS (VCX_ATTN_ACCUMULATE is
+ * refused).  Pitches and alignment: as above.  Of the two LDS-resident kernels the second form stores 16 bytes per lane: where o is only
+ * 8-byte aligned or ldo % 8 != 0 (or a unit's Q / O rows pass 32-bit byte offsets) the entry runs the first-form resident kernel, which
+ * stores 8 bytes per lane - the same contract, results agree to fp16 rounding. */
 int vcx_attn_flash_dual_d64_f16(const void* q, const void* k1, const void* vt1, const void* k2,
                                 const void* vt2, void* o, int n_groups, int heads, int nq,
                                 int nk1, int kv_rows1, int kv_div1, int64_t ldk1, int64_t ldvt1,
@@ -480,14 +488,18 @@ int vcx_attn_flash_dual_d64_mxfp8_ok(int n_groups, int heads, int nq, int nk1, i
  * (lvdm/modules/networks/ae_modules.py:26-78 at 9216 tokens per 576x1024 frame); the score matrix is never materialised.
  * Group g (a frame): Q rows q + (g*nq)*ldq (512 columns), K rows k + (g*kv_rows)*ldk (nk valid), V^T rows vt + d*ldvt + g*kv_rows
  * (512 rows d x nk columns), O rows o + (g*nq)*ldo.  kv_rows >= nk, multiple of 8 (rows [nk, kv_rows) must be readable; padding values: as for
- * vcx_attn_flash_d64_f16 - only the V^T columns [nk, (nk + 7) & ~7) are used, and they must be finite). */
+ * vcx_attn_flash_d64_f16 - only the V^T columns [nk, (nk + 7) & ~7) are used, and they must be finite).  Pitches and alignment as there:
+ * q, k, vt 16-byte aligned, ldq, ldk, ldvt multiples of 8; o 8-byte aligned, ldo % 4 == 0. */
 int vcx_attn_flash_d512_f16(const void* q, const void* k, const void* vt, void* o, int n_groups, int nq, int nk, int kv_rows,
                             int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, float scale, void* stream);
 
 /* Temporal self-attention over T <= 64 frames per pixel (one 32 x 32 score tile per (pixel, head) up to 32 frames, 2 x 2 tiles beyond), head dim 64
  * (TemporalTransformer -> CrossAttention.forward, attention.py:365-412, 81-126).
  * qkv is [(b t p)][ld] with q at col 0, k at col k_off, v at col v_off (+ h*64);
- * token (b, t, p) is row (b*T + t)*P + p.  o is [(b t p)][ldo]. */
+ * token (b, t, p) is row (b*T + t)*P + p.  o is [(b t p)][ldo].
+ * Pitches and alignment (this entry, the masked and the relative-position form; anything else is refused with -1 before a launch): qkv AND o
+ * are 16-byte aligned, ld AND ldo multiples of 8 - these kernels store 16 bytes per lane; k_off and v_off are NON-NEGATIVE multiples of
+ * 8, in any order and with any gap (q | k | v need not be adjacent).  relg / relp of the relative-position form are dense and 2-byte aligned. */
 int vcx_attn_temporal_d64_f16(const void* qkv, void* o, int B, int T, int64_t P, int heads,
                               int64_t ld, int k_off, int v_off, int64_t ldo, float scale,
                               void* stream);
@@ -516,7 +528,7 @@ int vcx_attn_temporal_d64_rel_f16(const void* qkv, void* o, const void* relg, vo
  *   scales  [(b t p)][Kp(D) / 32] scale bytes; head h at columns 2 h, 2 h + 1
  * With an odd head count the last 64 columns are padding: element bytes 0x00, scale bytes 127, written by this call (the buffers need no
  * initialisation).  T <= 32; flags: VCX_ATTN_CAUSAL only (no relative-position form).  qkv / q 16-byte aligned, scales 4-byte aligned; ld,
- * k_off, v_off multiples of 8; B T P x Kp(D) below 4 GiB (vcx_gemm_mxfp8 addresses its operand with 32 bits).  A row's bytes depend on that
+ * k_off, v_off non-negative multiples of 8; B T P x Kp(D) below 4 GiB (vcx_gemm_mxfp8 addresses its operand with 32 bits).  A row's bytes depend on that
  * (b, p)'s inputs alone.  Used by the opt-in route VCX_TATTN_MXFP8=1 of the Python package (default off); accuracy with a real checkpoint and
  * any multi-GPU number are unmeasured (profiles/mxfp8_tattn.md). */
 int vcx_attn_temporal_d64_mxfp8(const void* qkv, void* q, void* scales, int B, int T, int64_t P, int heads, int64_t ld,
@@ -526,7 +538,8 @@ int vcx_attn_temporal_d64_mxfp8(const void* qkv, void* q, void* scales, int B, i
 int vcx_attn_temporal_d64_mxfp8_ok(int B, int T, int64_t P, int heads, int64_t ld, int flags);
 
 /* Row softmax in place on fp16 [rows][ld] over the first n columns (fp32 math): VAE AttnBlock, ae_modules.py:66-69.
- * ld % 8 == 0; when n is not a multiple of 8 the columns up to the next multiple of 8 (ld must cover them) are written as zeros. */
+ * x 16-byte aligned, ld % 8 == 0; when n is not a multiple of 8 the columns up to the next multiple of 8 (ld must cover them: ld >= (n + 7) & ~7)
+ * are written as zeros; nothing behind them is touched. */
 int vcx_softmax_rows_f16(void* x, int64_t rows, int n, int64_t ld, void* stream);
 
 /* ------------------------------------------------------------------------------------

@@ -1704,6 +1704,7 @@ static int tattn_launch(const void* qkv, void* o, const void* relg, void* relp, 
     VCX_REQUIRE(B > 0 && T > 0 && T <= 64 && P > 0 && heads > 0, "vcx_attn_temporal_d64_f16: need 0 < T <= 64 (T=%d)", T);
     VCX_REQUIRE(ld % 8 == 0 && ldo % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0,
                 "vcx_attn_temporal_d64_f16: strides/offsets must be multiples of 8");
+    VCX_REQUIRE(k_off >= 0 && v_off >= 0, "vcx_attn_temporal_d64_f16: k_off / v_off must be non-negative multiples of 8");
     VCX_REQUIRE((((uintptr_t)qkv | (uintptr_t)o) & 15) == 0, "vcx_attn_temporal_d64_f16: pointers must be 16-byte aligned");
     TAttnArgs a;
     a.qkv = (const half_t*)qkv; a.o = (half_t*)o;
