@@ -306,6 +306,55 @@ def test_a_refusal_keeps_todays_calls_and_builds_no_mx_pack(monkeypatch, why):
     assert _mx_packs(st) == [] and y.shape == x.shape
 
 
+def record_every_op(monkeypatch):
+    """Every function of viewcrafter_amd.ops behind a wrapper that notes its name and calls through -> the list of the names called from
+    outside ops (what one of them calls inside ops is its own business)."""
+    import types
+
+    from viewcrafter_amd import ops
+    seen, depth = [], [0]
+
+    def wrap(name, fn):
+        def call(*a, **kw):
+            if depth[0] == 0:
+                seen.append(name)
+            depth[0] += 1
+            try:
+                return fn(*a, **kw)
+            finally:
+                depth[0] -= 1
+        return call
+    for name, fn in list(vars(ops).items()):
+        if isinstance(fn, types.FunctionType) and fn.__module__ == ops.__name__ and not name.startswith("_"):
+            monkeypatch.setattr(ops, name, wrap(name, fn))
+    return seen
+
+
+def is_a_question(name):
+    return name.endswith("_ok") or name in ("tune_get", "units_route")
+
+
+@pytest.mark.parametrize("switches", ["off", "mx", "pool", "both"])
+def test_the_plan_launches_and_allocates_nothing(monkeypatch, switches):
+    A, st = _transformer(2)
+    monkeypatch.setattr(A, "SATTN_MXFP8", switches in ("mx", "both"))
+    monkeypatch.setattr(A, "SATTN_MXFP8_SKIP_DIMS", frozenset())
+    monkeypatch.setattr(A, "SATTN_KV_POOL", "mean" if switches in ("pool", "both") else None)
+    monkeypatch.setattr(A, "SATTN_KV_POOL_MIN_TOKENS", 96)
+    seen = record_every_op(monkeypatch)
+    plans = [st._plan(_x(FPV, H, W), _context(A, st, 2), FPV, 2) for H, W in ((6, 8), (6, 10), (8, 12))]
+    assert seen and all(is_a_question(n) for n in seen), [n for n in seen if not is_a_question(n)]
+    assert [p.N for p in plans] == [48, 64, 96] and all(p.fold is False for p in plans)
+    pooled = switches in ("pool", "both")
+    small = "mx" if switches in ("mx", "both") else "fp16"          # 6x8 and 6x10 are below the pooling threshold
+    assert [p.engine for p in plans] == [small, small, {"off": "fp16", "mx": "mx", "pool": "pool", "both": "pool"}[switches]]
+    assert [p.pool for p in plans] == [None, None, (4, 6) if pooled else None]
+    assert ("layer_norm_pool2x2_ok" in seen) == pooled and any("mxfp8" in n for n in seen) == (switches in ("mx", "both"))
+    assert not any(p.rowstats for p in plans if p.engine == "mx")
+    with pytest.raises(AttributeError):
+        plans[0].engine = "mx"
+
+
 # ------------------------------------------------------------------------------------------------------------------ the predicates
 def _ok1(n_groups=50, heads=10, nq=2304, nk=2304, kv_rows=2304, kv_div=1, ldq=1280, ldk=1280, ldvt=50 * 2304, flags=LOG2):
     return _lib.lib().vcx_attn_flash_d64_mxfp8_ok(n_groups, heads, nq, nk, kv_rows, kv_div, ldq, ldk, ldvt, flags)

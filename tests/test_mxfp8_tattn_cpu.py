@@ -211,6 +211,25 @@ def test_a_refusal_keeps_todays_calls_and_builds_no_mx_pack(monkeypatch, why):
     assert _mx_packs(tr) == [] and y.shape == (B, Tn, P, 64)
 
 
+@pytest.mark.parametrize("switch", [False, True])
+def test_the_plan_launches_and_allocates_nothing(monkeypatch, switch):
+    from tests.test_mxfp8_sattn_cpu import is_a_question, record_every_op
+    A, tr = _transformer(depth=2)
+    monkeypatch.setattr(A, "TATTN_MXFP8", switch)
+    monkeypatch.setattr(A, "TATTN_MXFP8_SKIP_DIMS", frozenset())
+    monkeypatch.setattr(A, "GN_FOLD_MIN_BYTES", 0)
+    seen = record_every_op(monkeypatch)
+    plans = [tr._plan(_x(T_=Tn)) for Tn in (T, 33)]
+    assert seen and all(is_a_question(n) for n in seen), [n for n in seen if not is_a_question(n)]
+    assert [p.engine for p in plans] == ["mx" if switch else "fp16", "fp16"], "T = 33 keeps fp16"
+    assert all(p.fold is True for p in plans) and ("temporal_attn_mxfp8_ok" in seen) == switch
+    assert not any(p.rowstats for p in plans if p.engine == "mx")
+    monkeypatch.setattr(A, "GN_FOLD", False)
+    assert tr._plan(_x()).fold is False
+    with pytest.raises(AttributeError):
+        plans[0].engine = "mx"
+
+
 # ------------------------------------------------------------------------------------------------------------------ the shape predicate
 def _ok(B, T, P, heads, ld, flags=0):
     return _lib.lib().vcx_attn_temporal_d64_mxfp8_ok(B, T, P, heads, ld, flags)

@@ -231,8 +231,9 @@ def test_with_sattn_mxfp8_the_eligible_call_pools_and_the_others_keep_mx(monkeyp
     with torch.no_grad():
         st(_x(2 * FPV, 8, 12), context_kv=kv, frames_per_video=FPV)           # 96 tokens: pools
     names = rec.names(skip=())
-    assert not any("mxfp8" in n for n in names), "neither an MX op nor an MX predicate: _mx_route answers None for a pooled call"
-    assert st._mx_route(_x(2 * FPV, 8, 12), kv, FPV, 1, 96, C, pool=(4, 6)) is None
+    assert not any("mxfp8" in n for n in names), "neither an MX op nor an MX predicate: a pooled call asks none"
+    plan = st._plan(_x(2 * FPV, 8, 12), kv, FPV, 1)
+    assert plan.engine == "pool" and plan.pool == (4, 6)
     assert names[2:8] == ["row_stats", "linear", "layer_norm_pool2x2", "linear", "gemm", "flash_attn"] and names[8:] == today[6:]
     rec.calls.clear()
     with torch.no_grad():

@@ -61,9 +61,8 @@ def level(N, D):
     txt[:, :77] = torch.randn(B, 77, CDIM, device=DEV, generator=g).half()
     img = torch.randn(B * N_IMG, CDIM, device=DEV, generator=g).half()
     kv = st.project_context(dict(txt=txt.view(B * 80, CDIM), img=img, n_img=N_IMG, per_frame=False))[0]
-    geo1 = dict(n_groups=n, heads=heads, nq=N, nk=N, kv_rows=N, kv_div=1, ldq=2 * D, ldk=2 * D, ldvt=tokens)
-    geo2 = dict(n_groups=n, heads=heads, nq=N, nk1=kv.n_txt, kv_rows1=80, kv_div1=T, ldk1=D, ldvt1=kv.n_txt_rows, nk2=kv.n_img, kv_rows2=kv.n_img, kv_div2=T,
-                ldk2=D, ldvt2=kv.vt_img.shape[1], ldq=D)
+    geo1, geo2 = A._self_attn_geometry(n, heads, N, N, D), A._cross_attn_geometry(kv, n, heads, N, D, T)
+    ctx = (kv.k_txt, kv.vt_txt, kv.k_img, kv.vt_img)
     assert (ops.linear_mxfp8_ok(tokens, 2 * D, D) and ops.linear_t_mxfp8_ok(tokens, D, D) and ops.linear_mxfp8_ok(tokens, D, D, residual=True)
             and ops.flash_attn_mxfp8_ok(**geo1) and ops.flash_attn_dual_mxfp8_ok(**geo2))
     for what, pj, tr in (("q|k", a1["qk"], False), ("V^T", a1["v"], True), ("q2", a2["q"], False)):
@@ -93,7 +92,9 @@ def level(N, D):
         return run
 
     def mx_layer():
-        A._sattn_mx_block(blk, kv, ln, t, t, n, N, N, D, heads, T, 1)
+        t1 = A._to_out(A._sattn_mx(blk, ln[0], t, geo1, None, None), m1, t, True)           # a block's two attentions on the MX route, as SpatialTransformer.forward runs them
+        q2 = ops.linear_mxfp8(ops.layer_norm_mxfp8(t1, *ln[1]), m2["wq"], m2["zero"], K=D)
+        A._to_out(A._attend(q2, ctx, geo2, blk.attn2.scale, True), m2, t1, True)
 
     return dict(f16_layer=f16_layer(True), mx_layer=mx_layer, f16_layer_again=f16_layer(True), f16_layer_own_stats=f16_layer(False),
                 f16_pre=lambda: ops.row_stats(t, ln[0][2]), mx_pre=lambda: ops.layer_norm_mxfp8(t, *ln[0]),

@@ -73,7 +73,7 @@ def level(H, W, D):
         def run():
             prev, A.SATTN_KV_POOL = A.SATTN_KV_POOL, mode
             try:
-                A._sattn_kv_pool(blk, lnp, t, n, H, W, (H // 2, W // 2), heads, None)
+                A._sattn_kv_pool(blk, lnp, t, A._self_attn_geometry(n, heads, N, N, D, (H // 2, W // 2)), None, (H, W))
             finally:
                 A.SATTN_KV_POOL = prev
         return run

@@ -12,6 +12,7 @@ temporal attention kernel itself walks frames with a stride of h*w rows).
 """
 import math
 import os
+from collections import namedtuple
 
 import torch
 from torch import nn
@@ -19,7 +20,7 @@ from torch import nn
 from ... import ops
 from ...packing import fold_layernorm, pack_ff_out_folded, pack_geglu, pack_mxfp8
 from ..common import default
-from .flow import GN_STATS_LEVEL, out_kwargs
+from .flow import GN_STATS_LEVEL, env_dims, out_kwargs
 
 
 def _f16(t):
@@ -50,7 +51,7 @@ FF_MXFP8 = os.environ.get("VCX_FF_MXFP8", "0") == "1"
 # Widths whose feed-forward stays on the fp16 route although the switch is on.  320 (level 0) by default: isolated, its GEGLU projection is
 # slower in MXFP8 than on the weight-stationary fp16 kernel (1.08 against 0.98 ms at 460800 rows; the pair 1.49 against 1.45 ms), while
 # the 640- and 1280-wide pairs are 1.25x / 1.29x faster (profiles/mxfp8_ff.md).  VCX_FF_MXFP8_SKIP_DIMS="" puts every width on MX.
-FF_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_FF_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+FF_MXFP8_SKIP_DIMS = env_dims("VCX_FF_MXFP8_SKIP_DIMS", "320")
 # Opt-in (VCX_TATTN_MXFP8=1, default off): the two self-attentions of every block of a TemporalTransformer on the MXFP8 matrix pipe -
 # LayerNorm + quantiser in one pass, the q|k|v projection reading those bytes (un-folded weights, a zero bias: the reference has none),
 # the temporal attention kernel writing MXFP8 bytes + scales itself (vcx_attn_temporal_d64_mxfp8: a head's 64 columns are two MX blocks
@@ -62,7 +63,7 @@ TATTN_MXFP8 = os.environ.get("VCX_TATTN_MXFP8", "0") == "1"
 # its fp16 layer by more than the fp16 layer's own spread on the same box.  320 by default: its MX layer is 0.80x of the fp16 one (Kp = 384
 # pads a sixth of K, N = 320 half-fills the third column tile), 640 / 1280 are 1.05x / 1.26x against a spread of 0.5 % (profiles/mxfp8_tattn.md).
 # VCX_TATTN_MXFP8_SKIP_DIMS="" puts every width on MX.
-TATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_TATTN_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+TATTN_MXFP8_SKIP_DIMS = env_dims("VCX_TATTN_MXFP8_SKIP_DIMS", "320")
 # Opt-in (VCX_SATTN_MXFP8=1, default off; independent of the other four switches): the attention projections of every block of a
 # SpatialTransformer on the MXFP8 matrix pipe - LayerNorm + quantiser in one pass in front of q|k, V^T (vcx_gemm_mxfp8 with its operands
 # swapped: ops.linear_t_mxfp8) and the cross-attention's query projection, un-folded weights carrying the base-2 logit scale; the three
@@ -76,7 +77,7 @@ SATTN_MXFP8 = os.environ.get("VCX_SATTN_MXFP8", "0") == "1"
 # fp16 unless its isolated MX layer beats the fp16 layer by more than the fp16 layer's own spread in the same run.  320 by default: the two
 # attentions of a 320-wide block are 0.94x of fp16 on MX (Kp = 384 pads a sixth of K; to_out 0.74x, q|k 0.91x), 640 / 1280 are 1.04x / 1.15x
 # against a spread of 0.2 - 0.7 % (profiles/mxfp8_sattn.md).  VCX_SATTN_MXFP8_SKIP_DIMS="" puts every width on MX.
-SATTN_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_SATTN_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+SATTN_MXFP8_SKIP_DIMS = env_dims("VCX_SATTN_MXFP8_SKIP_DIMS", "320")
 # Opt-in (VCX_SATTN_KV_POOL=mean | nearest, default off): the spatial self-attention keeps every query but takes its keys and values from
 # the 2x2-pooled token grid of the frame (token downsampling: "ToDo", Smith et al. 2024; the spatial-reduction attention of PVT; training-
 # free) - a quarter of the key tiles, K and V^T projected from a quarter of the rows.  The pooled operand is LayerNorm + pool in one pass
@@ -123,7 +124,7 @@ def kv_pool_plan(H, W, C):
 # is 13 % / 9 % faster than the pair at D = 320 / 640, but at D = 1280 (K = 6400, compute-bound either way) its 2-5 % lies inside the pair's
 # own round-to-round spread, and the step is level with those twelve transformers folded or not (profiles/ff_out_fold.md).
 FF_OUT_FOLD = os.environ.get("VCX_FF_OUT_FOLD", "1") != "0"
-FF_OUT_FOLD_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_FF_OUT_FOLD_SKIP_DIMS", "1280").split(",") if v.strip())
+FF_OUT_FOLD_SKIP_DIMS = env_dims("VCX_FF_OUT_FOLD_SKIP_DIMS", "1280")
 
 
 # TemporalTransformer.norm -> proj_in (reference attention.py:331-336,369-372) and SpatialTransformer.norm -> proj_in (:265-269,299):
@@ -162,8 +163,15 @@ def fold_extent_ok(rows, C):
     return 2 * (rows + 256) * C < 0xFFFF0000
 
 
+def temporal_fold_ok(rows, C, D):
+    """Does the norm of a TemporalTransformer run as per-video weights / bias of proj_in (vcx_gemm_units_f16, unit = the `rows` rows of a
+    video)?  From ONE video's size, like spatial_fold_ok."""
+    return GN_FOLD and C % 64 == 0 and 2 * rows * C >= GN_FOLD_MIN_BYTES and 2 * rows * max(C, D) < 0xFFFF0000 and ops.tune_get("GEMM_DMA") != 0
+
+
 def _folded(pj, rows, K, lda, transposed=False):
-    """Will ln_linear / ln_linear_t run this pack as a folded projection (and so want row statistics)?"""
+    """Does this pack run as a folded projection (and so want row statistics)?  THE rule of _ln_operands: the pack is folded AND the
+    kernel takes the shape."""
     return pj["colsum"] is not None and ops.lnfold_ok(rows, pj["w"].shape[0], K, lda=lda, transposed=transposed)
 
 
@@ -189,28 +197,30 @@ def _plain_of(pj):
     return pj["_plain"]
 
 
-def ln_linear(t, pj, lnp, alpha=1.0, stats=None, **kw):
-    """Linear(LayerNorm(t)) * alpha for a pack of _ln_projection: the folded projection of the un-normalised rows where the pack
-    is folded AND the kernel takes the shape, layer_norm + plain projection otherwise.  lnp = (gamma, beta, eps); `stats` =
-    row statistics of t when the caller already has them."""
-    rows, K = t.shape
-    if pj["colsum"] is not None and ops.lnfold_ok(rows, pj["w"].shape[0], K, lda=t.stride(0)):
+def _ln_operands(t, pj, lnp, stats=None, transposed=False, plain=_plain_of):
+    """What a projection of LayerNorm(t) by the pack pj (keys w / colsum / bias) runs on -> (rows, weights, bias, fold keywords): the
+    un-normalised rows, the folded weights and ln_stats / ln_colsum where _folded says so; layer_norm(t), the plain weights (a folded
+    pack's: plain(pj)) and no keywords otherwise.  lnp = (gamma, beta, eps); `stats` = row statistics of t when the caller has them."""
+    if _folded(pj, t.shape[0], t.shape[1], t.stride(0), transposed):
         st = stats if stats is not None else ops.row_stats(t, lnp[2])
-        return ops.linear(t, pj["w"], pj["bias"], alpha=alpha, ln_stats=st, ln_colsum=pj["colsum"], **kw)
-    w, bias = (pj["w"], pj["bias"]) if pj["colsum"] is None else _plain_of(pj)
-    return ops.linear(ops.layer_norm(t, *lnp), w, bias, alpha=alpha, **kw)
+        return t, pj["w"], pj["bias"], dict(ln_stats=st, ln_colsum=pj["colsum"])
+    w, bias = (pj["w"], pj["bias"]) if pj["colsum"] is None else plain(pj)
+    return ops.layer_norm(t, *lnp), w, bias, {}
+
+
+def ln_linear(t, pj, lnp, alpha=1.0, stats=None, **kw):
+    """Linear(LayerNorm(t)) * alpha for a pack of _ln_projection: folded or layer_norm + plain projection, by _ln_operands."""
+    a, w, bias, fold = _ln_operands(t, pj, lnp, stats)
+    return ops.linear(a, w, bias, alpha=alpha, **fold, **kw)
 
 
 def ln_linear_t(t, pj, lnp, stats=None):
     """The transposed projection out[D, tokens] = W LayerNorm(t)^T (V^T of the spatial self-attention), same rule as ln_linear."""
     tokens, K = t.shape
-    D = pj["w"].shape[0]
-    if pj["colsum"] is not None and ops.lnfold_ok(tokens, D, K, lda=t.stride(0), transposed=True):
-        st = stats if stats is not None else ops.row_stats(t, lnp[2])
-        return ops.gemm(pj["w"], t, M=D, N=tokens, K=K, lda=K, ldw=t.stride(0), bias=pj["bias"], bias_m=True, ln_stats=st,
-                        ln_colsum=pj["colsum"], ln_t=True)
-    w, bias = (pj["w"], pj["bias"]) if pj["colsum"] is None else _plain_of(pj)
-    return ops.gemm(w, ops.layer_norm(t, *lnp), M=D, N=tokens, K=K, lda=K, bias=bias, bias_m=bias is not None)
+    a, w, bias, fold = _ln_operands(t, pj, lnp, stats, transposed=True)
+    if fold:
+        fold.update(ldw=t.stride(0), ln_t=True)
+    return ops.gemm(w, a, M=w.shape[0], N=tokens, K=K, lda=K, bias=bias, bias_m=bias is not None, **fold)
 
 
 def _sig(tensors):
@@ -253,6 +263,15 @@ class PackedModule(nn.Module):
 
     def _pack(self):
         raise NotImplementedError
+
+    def packed_with(self, key, build):
+        """packed() with entries in it that only some routes need: build() -> dict of the entries to add (`key` among them), called at the
+        first use of the route.  They live inside the pack: dropped and rebuilt with it."""
+        pk = self.packed()
+        if key not in pk:
+            with torch.no_grad():
+                pk.update(build(pk))
+        return pk
 
 
 class RelativePosition(nn.Module):
@@ -339,36 +358,31 @@ class CrossAttention(PackedModule):
         """TATTN_MXFP8 (temporal self-attention): the MXFP8 pairs of the UN-folded cat(Wq, Wk, Wv) and of to_out's weight, a zero bias [3D]
         for the projection that has none (vcx_gemm_mxfp8 wants one) and bo.  SATTN_MXFP8 (kind "spatial"): self-attention - the pairs of
         sqrt(scale log2 e) * cat(Wq, Wk) (scaled in fp32, one fp16 rounding), of Wv and of to_out's weight, a zero bias [2D]; cross-attention -
-        the pairs of scale log2 e * Wq and of to_out's weight, a zero bias [D].  Built at first use of the route, inside the pack: dropped with it."""
-        pk = self.packed()
-        if "mx" not in pk:
-            with torch.no_grad():
-                wq, wk, wv = self.to_q.weight.detach().float(), self.to_k.weight.detach().float(), self.to_v.weight.detach().float()
-                zeros = lambda n: torch.zeros(n, dtype=torch.float32, device=wq.device)
-                if self.kind == "temporal":
-                    wqkv = _f16(torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach(), self.to_v.weight.detach()], 0))
-                    mx = dict(wqkv=pack_mxfp8(wqkv), zero=zeros(wqkv.shape[0]))
-                elif self.is_self:
-                    wqk = _f16(torch.cat([wq, wk], 0) * math.sqrt(self.scale * ops.LOG2E))
-                    mx = dict(wqk=pack_mxfp8(wqk), wv=pack_mxfp8(_f16(wv)), zero=zeros(wqk.shape[0]))
-                else:
-                    wq2 = _f16(wq * (self.scale * ops.LOG2E))
-                    mx = dict(wq=pack_mxfp8(wq2), zero=zeros(wq2.shape[0]))
-                pk["mx"] = dict(mx, wo=pack_mxfp8(pk["wo"]), bo=pk["bo"])
-        return pk["mx"]
+        the pairs of scale log2 e * Wq and of to_out's weight, a zero bias [D].  Built at first use of the route (packed_with)."""
+        def build(pk):
+            wq, wk, wv = self.to_q.weight.detach().float(), self.to_k.weight.detach().float(), self.to_v.weight.detach().float()
+            zeros = lambda n: torch.zeros(n, dtype=torch.float32, device=wq.device)
+            if self.kind == "temporal":
+                wqkv = _f16(torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach(), self.to_v.weight.detach()], 0))
+                mx = dict(wqkv=pack_mxfp8(wqkv), zero=zeros(wqkv.shape[0]))
+            elif self.is_self:
+                wqk = _f16(torch.cat([wq, wk], 0) * math.sqrt(self.scale * ops.LOG2E))
+                mx = dict(wqk=pack_mxfp8(wqk), wv=pack_mxfp8(_f16(wv)), zero=zeros(wqk.shape[0]))
+            else:
+                wq2 = _f16(wq * (self.scale * ops.LOG2E))
+                mx = dict(wq=pack_mxfp8(wq2), zero=zeros(wq2.shape[0]))
+            return dict(mx=dict(mx, wo=pack_mxfp8(pk["wo"]), bo=pk["bo"]))
+        return self.packed_with("mx", build)["mx"]
 
     def kv_pool_packed(self):
         """SATTN_KV_POOL (spatial self-attention): Q alone in the form today's Q|K pack has - folded where that is folded, carrying
         sqrt(scale log2 e) - and the plain fp16 weights of K and V, which project the pooled, already normalised rows.  Built at first use
-        of the route, inside the pack: dropped with it."""
-        pk = self.packed()
-        if "kv_pool" not in pk:
-            with torch.no_grad():
-                ln = self._pre_norm[0] if pk["qk"]["colsum"] is not None else None
-                pv = pk["v"]
-                pk["kv_pool"] = dict(q=_ln_projection(self.to_q.weight.detach(), ln, alpha=math.sqrt(self.scale * ops.LOG2E)),
-                                     wk=_f16(self.to_k.weight), wv=pv["w"] if pv["colsum"] is None else _plain_of(pv)[0])
-        return pk["kv_pool"]
+        of the route (packed_with)."""
+        def build(pk):
+            ln, pv = self._pre_norm[0] if pk["qk"]["colsum"] is not None else None, pk["v"]
+            return dict(kv_pool=dict(q=_ln_projection(self.to_q.weight.detach(), ln, alpha=math.sqrt(self.scale * ops.LOG2E)),
+                                     wk=_f16(self.to_k.weight), wv=pv["w"] if pv["colsum"] is None else _plain_of(pv)[0]))
+        return self.packed_with("kv_pool", build)["kv_pool"]
 
     def forward(self, *args, **kwargs):
         raise RuntimeError("CrossAttention is driven by SpatialTransformer/TemporalTransformer in this package")
@@ -400,7 +414,7 @@ class FeedForward(PackedModule):
         p1 = _ln_projection(proj.weight.detach(), ln, bias=proj.bias)
         w1, b1 = pack_geglu(p1["w"], p1["bias"])
         colsum = None if p1["colsum"] is None else pack_geglu(p1["w"], p1["colsum"])[1]
-        return dict(w1=w1, b1=b1, colsum=colsum, w2=_f16(self.net[2].weight), b2=_f32(self.net[2].bias))
+        return dict(w=w1, bias=b1, colsum=colsum, w2=_f16(self.net[2].weight), b2=_f32(self.net[2].bias))      # (w / colsum / bias: a pack _ln_operands takes)
 
     def _mx_ok(self, t):
         """FF_MXFP8: does vcx_gemm_mxfp8 take BOTH linears at this row count (its own predicate)?  Either side refusing keeps the fp16 route."""
@@ -410,32 +424,28 @@ class FeedForward(PackedModule):
                 and ops.linear_mxfp8_ok(rows, proj.out_features, self.dim, geglu=True, mx_out=True)
                 and ops.linear_mxfp8_ok(rows, out.out_features, out.in_features, residual=True))
 
-    def on_fp16_route(self, t):
-        return not (FF_MXFP8 and self._mx_ok(t))
+    def _plain_glu(self):
+        return pack_geglu(_f16(self.net[0].proj.weight), _f32(self.net[0].proj.bias))
 
     def glu(self, t, ln_params):
-        """x * gelu(gate) of the GEGLU projection of LayerNorm(t), [rows, 4 dim]: the operand of net[2].  The fp16 route (on_fp16_route)."""
-        pk = self.packed()
-        if pk["colsum"] is not None and ops.lnfold_ok(t.shape[0], pk["w1"].shape[0], t.shape[1], lda=t.stride(0)):
-            return ops.linear(t, pk["w1"], pk["b1"], geglu=True, ln_stats=ops.row_stats(t, ln_params[2]), ln_colsum=pk["colsum"])
-        if pk["colsum"] is not None and "w1_plain" not in pk:      # folded pack, shape the folded kernel cannot take
-            proj = self.net[0].proj
-            pk["w1_plain"], pk["b1_plain"] = pack_geglu(_f16(proj.weight), _f32(proj.bias))
-        w1, b1 = (pk["w1"], pk["b1"]) if pk["colsum"] is None else (pk["w1_plain"], pk["b1_plain"])
-        return ops.linear(ops.layer_norm(t, *ln_params), w1, b1, geglu=True)
+        """x * gelu(gate) of the GEGLU projection of LayerNorm(t), [rows, 4 dim]: the operand of net[2].  The fp16 route (FF_MXFP8 off, or _mx_ok refusing)."""
+        def plain(pk):      # folded pack, shape the folded kernel cannot take: the un-folded (w1, b1), built at first use
+            return self.packed_with("plain", lambda _: dict(plain=self._plain_glu()))["plain"]
+        a, w1, b1, fold = _ln_operands(t, self.packed(), ln_params, plain=plain)
+        return ops.linear(a, w1, b1, geglu=True, **fold)
 
-    def run(self, t, ln_params):
-        """t + FF(LayerNorm(t)); ln_params = (gamma, beta, eps) of the LayerNorm in front (used when it is not folded into w1)."""
+    def run(self, t, ln_params, mx=None):
+        """t + FF(LayerNorm(t)); ln_params = (gamma, beta, eps) of the LayerNorm in front (used when it is not folded into w1).  mx: the
+        answer of FF_MXFP8 and _mx_ok(t) where the caller has asked already (ff_proj_out)."""
         pk = self.packed()
-        if FF_MXFP8 and self._mx_ok(t):
-            if "mx" not in pk:          # built lazily beside the fp16 packs, from the un-folded weights
-                proj = self.net[0].proj
-                w1, b1 = pack_geglu(_f16(proj.weight), _f32(proj.bias))
-                pk["mx"] = dict(w1=pack_mxfp8(w1), b1=b1, w2=pack_mxfp8(pk["w2"]))
-            mx = pk["mx"]
+        if (FF_MXFP8 and self._mx_ok(t)) if mx is None else mx:
+            def build(pk):          # beside the fp16 packs, from the un-folded weights
+                w1, b1 = self._plain_glu()
+                return dict(mx=dict(w1=pack_mxfp8(w1), b1=b1, w2=pack_mxfp8(pk["w2"])))
+            pm = self.packed_with("mx", build)["mx"]
             a = ops.layer_norm_mxfp8(t, *ln_params)
-            g = ops.linear_mxfp8(a, mx["w1"], mx["b1"], K=self.dim, geglu=True, mx_out=True)
-            return ops.linear_mxfp8(g, mx["w2"], pk["b2"], K=pk["w2"].shape[1], residual=t)
+            g = ops.linear_mxfp8(a, pm["w1"], pm["b1"], K=self.dim, geglu=True, mx_out=True)
+            return ops.linear_mxfp8(g, pm["w2"], pk["b2"], K=pk["w2"].shape[1], residual=t)
         return ops.linear(self.glu(t, ln_params), pk["w2"], pk["b2"], residual=t)
 
 
@@ -486,19 +496,31 @@ def ff_proj_out(tr, t, ln_params, xin, kw, video_rows):
     pk, ff = tr.packed(), tr.transformer_blocks[-1].ff
     tokens, D = t.shape
     C = pk["wout"].shape[0]
-    fold = (FF_OUT_FOLD and t.is_cuda and D not in FF_OUT_FOLD_SKIP_DIMS and ff.net[2].bias is not None and ff.on_fp16_route(t)
+    mx = FF_MXFP8 and ff._mx_ok(t)      # the feed-forward's engine, asked once: for the fold and for ff.run
+    fold = (FF_OUT_FOLD and t.is_cuda and D not in FF_OUT_FOLD_SKIP_DIMS and ff.net[2].bias is not None and not mx
             and all(ops.linear_tail_ok(m, C, ff.net[2].in_features, [D], ldc=kw.get("ldc"), residual=True, colstats="colstats" in kw)
                     for m in sorted({video_rows, tokens})))
     if not fold:
-        return ops.linear(ff.run(t, ln_params), pk["wout"], pk["bout"], residual=xin, **kw)
-    if "wcat" not in pk:
-        pk["wcat"], pk["bcat"] = pack_ff_out_folded(ff.net[2].weight, ff.net[2].bias, pk["wout"], pk["bout"])
+        return ops.linear(ff.run(t, ln_params, mx), pk["wout"], pk["bout"], residual=xin, **kw)
+    pk = tr.packed_with("wcat", lambda pk: dict(zip(("wcat", "bcat"), pack_ff_out_folded(ff.net[2].weight, ff.net[2].bias, pk["wout"], pk["bout"]))))
     return ops.linear(ff.glu(t, ln_params), pk["wcat"], pk["bcat"], tail=[t], residual=xin, **kw)
 
 
-def _last_ff_params(tr):
-    ff2 = tr.transformer_blocks[-1].ff.net[2]
-    return [ff2.weight] + ([] if ff2.bias is None else [ff2.bias])
+class _Transformer(PackedModule):
+    """What SpatialTransformer and TemporalTransformer pack alike: the norm, proj_in and proj_out (a linear layer, or its 1x1 / k = 1
+    convolution form: the same matmul on a channels-last row, the weight reshaped)."""
+
+    def _foreign_params(self):
+        ff2 = self.transformer_blocks[-1].ff.net[2]
+        return [ff2.weight] + ([] if ff2.bias is None else [ff2.bias])
+
+    def _pack(self):
+        """+ wcat / bcat, built on first use by ff_proj_out: [Wout W2 | Wout] and Wout b2 + bout, DERIVED FROM transformer_blocks[-1].ff.net[2]
+        (a child's parameters: _foreign_params rebuilds the pack when they change, _drop_packed discards it with the rest)."""
+        win = self.proj_in.weight.detach().reshape(self.proj_in.weight.shape[0], -1)
+        wout = self.proj_out.weight.detach().reshape(self.proj_out.weight.shape[0], -1)
+        return dict(gn_w=_f32(self.norm.weight), gn_b=_f32(self.norm.bias), win=_f16(win), win32=_f32(win), bin=_f32(self.proj_in.bias),
+                    wout=_f16(wout), bout=_f32(self.proj_out.bias))
 
 
 class ContextKV:
@@ -527,7 +549,105 @@ def project_context(attn2, ctx):
     return kv
 
 
-class SpatialTransformer(PackedModule):
+def _norm_proj_in(tr, x, unit_rows, stats, fold, rowstats, pad=None):
+    """GroupNorm -> proj_in of transformer `tr` over x [..., C], `unit_rows` rows a statistics unit (Spatial: a frame, Temporal: a video);
+    stats: the units' statistics where the caller has them.  fold: the norm as per-unit weights / bias of the projection, which reads the
+    un-normalised rows; else the norm is applied.  rowstats: the projection writes the row statistics of its output (VCX_GEMM_ROWSTATS).
+    pad (never with fold): rows -> rows with every frame padded.  -> (token stream, its row statistics or None, the rows of x, padded)"""
+    pk, C = tr.packed(), x.shape[-1]
+    xin = x.reshape(-1, C)
+    units = xin.shape[0] // unit_rows
+    if fold:
+        if stats is None:
+            stats = ops.group_norm_stats(x.view(units, unit_rows, C))
+        wn, bn = ops.group_norm_fold_linear(pk["win32"], pk["bin"], pk["gn_w"], pk["gn_b"], stats, tr.norm.eps)
+    else:
+        a = ops.group_norm(x.view(units, unit_rows, C), pk["gn_w"], pk["gn_b"], tr.norm.eps, False, stats=stats).view(-1, C)
+        if pad is not None:
+            xin, a = pad(xin), pad(a)
+    rs = ops.rowstats_buffer(xin.shape[0], x.device) if rowstats else None
+    rs_eps = tr.transformer_blocks[0].norm1.eps
+    if fold:
+        return ops.gemm_units(xin, wn, bn, unit_rows=unit_rows, rowstats=rs, rowstats_eps=rs_eps), rs, xin
+    return ops.linear(a, pk["win"], pk["bin"], rowstats=rs, rowstats_eps=rs_eps), rs, xin
+
+
+def _to_out(o, ap, t, mx, **kw):
+    """to_out of an attention with the residual t; ap: the attention's pack of its engine (packed() / mx_packed(): wo, bo), o: the fp16
+    attention output / its MXFP8 pair.  kw: further keywords of the fp16 layer (row statistics: the MX route requests none)."""
+    if mx:
+        return ops.linear_mxfp8(o, ap["wo"], ap["bo"], K=t.shape[1], residual=t)
+    return ops.linear(o, ap["wo"], ap["bo"], residual=t, **kw)
+
+
+# ---- the attention calls of a SpatialTransformer: one geometry function per call - the keywords the MX predicate, the fp16 launcher (+ ldo,
+# log2_logits) and the MX launcher all take - and one function per engine.  scale * log2(e) rides in the projections (sqrt of it on Q and on K
+# of the self-attention: one fp16 rounding each, as without it), so the kernels get base-2 logits and the running max can live in the MFMA
+# accumulator (VCX_ATTN_LOG2_LOGITS).
+def _self_attn_geometry(frames, heads, N, N_img, D, pool=None):
+    """Self-attention over `frames` frames of N rows, the first N_img of them tokens (keys; the pad rows' results are dropped): q|k one
+    [tokens, 2D] projection, V^T [D, tokens].  pool (kv_pool_plan): Q alone [tokens, D], keys and values the rows of the pooled grid."""
+    kv_rows, nk, ld = (N, N_img, 2 * D) if pool is None else (pool[0] * pool[1], pool[0] * pool[1], D)
+    return dict(n_groups=frames, heads=heads, nq=N, nk=nk, kv_rows=kv_rows, kv_div=1, ldq=ld, ldk=ld, ldvt=frames * kv_rows)
+
+
+def _cross_attn_geometry(kv, frames, heads, N, D, frames_per_video):
+    """Cross-attention of `frames` frames of N rows to the context kv (ContextKV): text keys (80 rows a video) shared by the frames of a
+    video, and - kv.k_img: the dual kernels, text (+) image in one pass over q and o - image keys per video or per frame."""
+    ldvt = kv.n_txt_rows // 80 * 80
+    if kv.k_img is None:
+        return dict(n_groups=frames, heads=heads, nq=N, nk=kv.n_txt, kv_rows=80, kv_div=frames_per_video, ldq=D, ldk=D, ldvt=ldvt)
+    return dict(n_groups=frames, heads=heads, nq=N, nk1=kv.n_txt, kv_rows1=80, kv_div1=frames_per_video, ldk1=D, ldvt1=ldvt, nk2=kv.n_img,
+                kv_rows2=kv.n_img, kv_div2=1 if kv.img_per_frame else frames_per_video, ldk2=D, ldvt2=kv.vt_img.shape[1], ldq=D)
+
+
+def _attend(q, kvt, geo, scale, mx):
+    """One attention call of a SpatialTransformer: kvt = (k, V^T) with the keywords of _self_attn_geometry, or the context's (k_txt, vt_txt
+    [, k_img, vt_img]) with those of _cross_attn_geometry; mx: the quantising kernel.  -> [tokens, D] fp16, or its MXFP8 pair"""
+    dual, D = len(kvt) == 4, 64 * geo["heads"]
+    if mx:
+        return (ops.flash_attn_dual_mxfp8 if dual else ops.flash_attn_mxfp8)(q, *kvt, **geo, scale=scale)
+    o = torch.empty((q.shape[0], D), dtype=torch.float16, device=q.device)
+    return (ops.flash_attn_dual if dual else ops.flash_attn)(q, *kvt, o, **geo, ldo=D, scale=scale, log2_logits=True)
+
+
+def _sattn_fp16(blk, lnp, t, geo, stats, grid):
+    """The self-attention of one SpatialTransformer block up to its output projection, fp16 engine -> [tokens, D].  lnp = (gamma, beta, eps)
+    of norm1 (folded into both projections wherever _ln_operands says so), stats = the row statistics of t where its producer wrote them."""
+    a1, D = blk.attn1.packed(), t.shape[1]
+    if stats is None and a1["qk"]["colsum"] is not None:
+        stats = ops.row_stats(t, lnp[2])
+    qk = ln_linear(t, a1["qk"], lnp, alpha=math.sqrt(blk.attn1.scale * ops.LOG2E), stats=stats)      # [tokens, 2D]
+    vt = ln_linear_t(t, a1["v"], lnp, stats=stats)                                                   # [D, tokens]
+    return _attend(qk, (qk[:, D:], vt), geo, blk.attn1.scale, False)
+
+
+def _sattn_kv_pool(blk, lnp, t, geo, stats, grid):
+    """The same on the SATTN_KV_POOL route, every query and the keys and values of the 2x2-pooled tokens: five calls (six where the folded Q
+    projection has no row statistics from its producer), in this order.  t [n H W, D] (kv_pool_plan: no padded rows), grid = (H, W)."""
+    pp, D, n = blk.attn1.kv_pool_packed(), t.shape[1], geo["n_groups"]
+    alpha = math.sqrt(blk.attn1.scale * ops.LOG2E)
+    q = ln_linear(t, pp["q"], lnp, alpha=alpha, stats=stats)                                     # [tokens, D], every query
+    p = ops.layer_norm_pool2x2(t, *lnp, n, *grid, _KV_POOL_MODES[SATTN_KV_POOL])                 # [n Np, D], normalised and pooled
+    k = ops.linear(p, pp["wk"], None, alpha=alpha)                                               # [n Np, D]
+    vt = ops.gemm(pp["wv"], p, M=D, N=n * geo["kv_rows"], K=D, lda=D)                            # [D, n Np]
+    return _attend(q, (k, vt), geo, blk.attn1.scale, False)
+
+
+def _sattn_mx(blk, lnp, t, geo, stats, grid):
+    """The same on the SATTN_MXFP8 route: four calls (the quantising LayerNorm computes its own statistics).  -> the MXFP8 pair [tokens, Kp(D)]"""
+    m1, D = blk.attn1.mx_packed(), t.shape[1]
+    an = ops.layer_norm_mxfp8(t, *lnp)
+    qk = ops.linear_mxfp8(an, m1["wqk"], m1["zero"], K=D)                     # [tokens, 2D] fp16, base-2 logit scale in the weights
+    vt = ops.linear_t_mxfp8(an, m1["wv"], K=D)                                # [D, tokens] fp16
+    return _attend(qk, (qk[:, D:], vt), geo, blk.attn1.scale, True)
+
+
+SpatialPlan = namedtuple("SpatialPlan", "N fold engine pool rowstats")
+TemporalPlan = namedtuple("TemporalPlan", "fold engine rowstats")
+
+
+class SpatialTransformer(_Transformer):
     """Reference attention.py:249-310 (use_linear=True, or False = 1x1 Conv2d projections): GN(eps 1e-6) -> proj_in -> [LN, self-attn, LN, text (+) image
     cross-attn, LN, GEGLU-FF] -> proj_out -> + x."""
 
@@ -555,53 +675,47 @@ class SpatialTransformer(PackedModule):
         nn.init.zeros_(self.proj_out.bias)
         self.use_linear = use_linear
 
-    def _foreign_params(self):
-        return _last_ff_params(self)
-
-    def _pack(self):
-        """+ wcat / bcat, built on first use by ff_proj_out: [Wout W2 | Wout] and Wout b2 + bout, DERIVED FROM transformer_blocks[-1].ff.net[2]
-        (a child's parameters: _foreign_params rebuilds the pack when they change, _drop_packed discards it with the rest)."""
-        win = self.proj_in.weight.detach().reshape(self.proj_in.weight.shape[0], -1)       # ([out, in, 1, 1] of the 1x1-conv form)
-        wout = self.proj_out.weight.detach().reshape(self.proj_out.weight.shape[0], -1)
-        return dict(gn_w=_f32(self.norm.weight), gn_b=_f32(self.norm.bias), win=_f16(win), win32=_f32(win),
-                    bin=_f32(self.proj_in.bias), wout=_f16(wout), bout=_f32(self.proj_out.bias))
-
     def project_context(self, ctx):
         return [project_context(blk.attn2, ctx) for blk in self.transformer_blocks]
 
-    def _mx_route(self, x, context_kv, frames_per_video, cfg_repeat, N, D, pool=None):
-        """SATTN_MXFP8: do the attentions of every block of this call run on the MX route?  Decided once per call, before anything runs:
-        width not skipped, GPU tensors, and every predicate of the library - asked about the frames of ONE video (a row's route must not
-        depend on the batch it runs in: B = 2 against two B = 1, the shared CFG prefix against the replicated batch) and about the call
-        itself, before and behind the CFG replication (only the 32-bit extents depend on the batch).  Any refusal keeps the fp16 calls
-        for the whole transformer.  None for a call that kv_pool_plan accepts (`pool`): its self-attention runs the pooled fp16 route."""
-        n, H, W, _ = x.shape
-        if pool is not None:
-            return None
-        if not SATTN_MXFP8 or D in SATTN_MXFP8_SKIP_DIMS:
+    def _mx_accepts(self, n, N, N_img, D, context_kv, frames_per_video, cfg_repeat):
+        """SATTN_MXFP8: the width is not skipped and the library takes the attentions of every block - every predicate asked about the frames
+        of ONE video (a row's route must not depend on the batch it runs in: B = 2 against two B = 1, the shared CFG prefix against the
+        replicated batch) and about the call itself, before and behind the CFG replication (only the 32-bit extents depend on the batch)."""
+        heads = self.n_heads
+        if not SATTN_MXFP8 or D in SATTN_MXFP8_SKIP_DIMS or any(a.to_out[0].bias is None or a.inner_dim != D or a.query_dim != D
+                                                                  for blk in self.transformer_blocks for a in (blk.attn1, blk.attn2)):
             return False
-        attns = [a for blk in self.transformer_blocks for a in (blk.attn1, blk.attn2)]
-        if any(a.to_out[0].bias is None or a.inner_dim != D or a.query_dim != D for a in attns):
-            return False
-        N_img, heads = H * W, self.n_heads
         for frames in sorted({frames_per_video, n, n * cfg_repeat}):
             tokens = frames * N
             if not (ops.linear_mxfp8_ok(tokens, 2 * D, D) and ops.linear_t_mxfp8_ok(tokens, D, D) and ops.linear_mxfp8_ok(tokens, D, D)
-                    and ops.linear_mxfp8_ok(tokens, D, D, residual=True)
-                    and ops.flash_attn_mxfp8_ok(n_groups=frames, heads=heads, nq=N, nk=N_img, kv_rows=N, kv_div=1, ldq=2 * D, ldk=2 * D, ldvt=tokens)):
+                    and ops.linear_mxfp8_ok(tokens, D, D, residual=True) and ops.flash_attn_mxfp8_ok(**_self_attn_geometry(frames, heads, N, N_img, D))):
                 return False
-            for kv in context_kv:
-                nb = kv.n_txt_rows // 80
-                if kv.k_img is not None:
-                    ok = ops.flash_attn_dual_mxfp8_ok(n_groups=frames, heads=heads, nq=N, nk1=kv.n_txt, kv_rows1=80, kv_div1=frames_per_video, ldk1=D,
-                                                      ldvt1=nb * 80, nk2=kv.n_img, kv_rows2=kv.n_img, kv_div2=1 if kv.img_per_frame else frames_per_video,
-                                                      ldk2=D, ldvt2=kv.vt_img.shape[1], ldq=D)
-                else:
-                    ok = ops.flash_attn_mxfp8_ok(n_groups=frames, heads=heads, nq=N, nk=kv.n_txt, kv_rows=80, kv_div=frames_per_video, ldq=D, ldk=D,
-                                                 ldvt=nb * 80)
-                if not ok:
-                    return False
+            if not all((ops.flash_attn_mxfp8_ok if kv.k_img is None else ops.flash_attn_dual_mxfp8_ok)(
+                    **_cross_attn_geometry(kv, frames, heads, N, D, frames_per_video)) for kv in context_kv):
+                return False
         return True
+
+    def _plan(self, x, context_kv, frames_per_video=1, cfg_repeat=1):
+        """Every routing decision of a forward, made before the first launch or buffer (packs aside: built at first use) -> SpatialPlan.  N: the rows of a frame, h*w
+        padded to a multiple of 8 (the attention kernels address a frame's keys / values at 16-byte granularity; e.g. 384x640: 6x10 = 60
+        tokens at the deepest level).  fold: the norm as per-frame weights / bias of proj_in.  engine: "pool" (pool = the grid of
+        kv_pool_plan, asked first: a call that pools asks no MX predicate), "mx" (SATTN_MXFP8: both attentions of every block) or "fp16";
+        any refusal keeps the fp16 calls for the whole transformer.  rowstats: proj_in writes the row statistics norm1 of the first block
+        reads (VCX_GEMM_ROWSTATS: the producer is the weight-stationary kernel, C = 320, and the consumer a folded projection; row_stats,
+        one read of the tensor, otherwise; none on the MX route, whose quantising LayerNorm computes its own).  fold and rowstats change the
+        last bits, so they are decided on the rows of ONE video: the shared CFG prefix must match the replicated batch bit for bit."""
+        n, H, W, C = x.shape
+        N_img, D = H * W, self.packed()["win"].shape[0]
+        N = (N_img + 7) // 8 * 8
+        pool = kv_pool_plan(H, W, D)
+        engine = "pool" if pool is not None else "mx" if self._mx_accepts(n, N, N_img, D, context_kv, frames_per_video, cfg_repeat) else "fp16"
+        fold = bool(N_img % 8 == 0 and spatial_fold_ok(frames_per_video, N_img, C, D) and fold_extent_ok(n * N_img, max(C, D)))
+        attn1 = self.transformer_blocks[0].attn1
+        p1 = attn1.kv_pool_packed()["q"] if pool is not None else attn1.packed()["qk"]      # the projection that reads norm1's statistics
+        rowstats = engine != "mx" and _folded(p1, n * N, D, D) and ops.rowstats_ok(n * N, D, C, lda=C, unit_rows=N_img if fold else None,
+                                                                                   video_rows=frames_per_video * N)
+        return SpatialPlan(N, fold, engine, pool, rowstats)
 
     def forward(self, x, context_kv=None, frames_per_video=1, cfg_repeat=1, colstats=None, want_colstats=False, **kwargs):
         """x [n, H, W, C] fp16 channels-last, n = b*t frames; context_kv from project_context().
@@ -614,91 +728,35 @@ class SpatialTransformer(PackedModule):
         result for the GroupNorm of the layer behind this one.  -> (result, its moments or None)"""
         n, H, W, C = x.shape
         N_img = H * W
-        pk = self.packed()
-        pool = kv_pool_plan(H, W, pk["win"].shape[0])      # SATTN_KV_POOL, decided before anything runs
-        mx = self._mx_route(x, context_kv, frames_per_video, cfg_repeat, (N_img + 7) // 8 * 8, pk["win"].shape[0], pool)      # SATTN_MXFP8, likewise
-        # colstats: column moments of x from the convolution that produced it (ResBlock): the norm then needs no statistics pass
+        plan = self._plan(x, context_kv, frames_per_video, cfg_repeat)
+        N, mx, self_attn = plan.N, plan.engine == "mx", {"fp16": _sattn_fp16, "pool": _sattn_kv_pool, "mx": _sattn_mx}[plan.engine]
         stats = None if colstats is None else ops.group_norm_stats_from_colstats(colstats, n, N_img, C)
-        D_in = pk["win"].shape[0]
-        fold = N_img % 8 == 0 and spatial_fold_ok(frames_per_video, N_img, C, D_in) and fold_extent_ok(n * N_img, max(C, D_in))     # the norm as per-frame weights / bias of proj_in
-        a = None if fold else ops.group_norm(x.view(n, N_img, C), pk["gn_w"], pk["gn_b"], self.norm.eps, False, stats=stats)
-        # The attention kernels address a frame's keys / values at 16-byte granularity: h*w must be a multiple of 8.  It is at every
-        # level of 576x1024 and 320x512; for other --height / --width (e.g. 384x640: 6x10 = 60 tokens at the deepest level) each
-        # frame's token rows are padded with zero rows up to the next multiple of 8 for the length of this block - all its layers
-        # are row-wise except the attentions, which take nq = padded rows (results of pad rows are dropped) and nk = real keys.
-        N = (N_img + 7) // 8 * 8
-        xin = x.reshape(n * N_img, C)
-        if N != N_img:
-            def pad_frames(src):
-                dst = torch.zeros((n * N, C), dtype=torch.float16, device=x.device)
-                ops.copy2d(src, dst, n, N_img * C, N_img * C, N * C)           # one "row" per frame
-                return dst
-            xin, a = pad_frames(xin), pad_frames(a.view(n * N_img, C))
-        tokens = n * N
-        if fold:
-            if stats is None:
-                stats = ops.group_norm_stats(x.view(n, N_img, C))
-            wn, bn = ops.group_norm_fold_linear(pk["win32"], pk["bin"], pk["gn_w"], pk["gn_b"], stats, self.norm.eps)
-        # LayerNorm statistics of the token stream from the layer that writes it (VCX_GEMM_ROWSTATS, round 6): proj_in for norm1 of the
-        # first block, attn1's output projection for norm2 - where the producer is the weight-stationary kernel (C = 320) and the
-        # consumer a folded projection; row_stats (one read of the tensor) otherwise.  Decided on the rows of one video, like the fold: the two
-        # routes differ in the last bits, and the shared CFG prefix (n = t frames) must match the replicated batch (r t frames) bit for bit
-        blk0 = self.transformer_blocks[0]
-        rs_eps = blk0.norm1.eps
-        rs = None
-        video_rows = frames_per_video * N
-        # (no row statistics on the MX route: the quantising LayerNorm computes its own)
-        p1 = blk0.attn1.kv_pool_packed()["q"] if pool is not None else blk0.attn1.packed()["qk"]      # the projection that reads norm1's statistics
-        if not mx and _folded(p1, tokens, D_in, D_in) and ops.rowstats_ok(tokens, D_in, C, lda=C, unit_rows=N_img if fold else None,
-                                                                                      video_rows=video_rows):
-            rs = ops.rowstats_buffer(tokens, x.device)
-        if fold:
-            t = ops.gemm_units(xin, wn, bn, unit_rows=N_img, rowstats=rs, rowstats_eps=rs_eps)
-        else:
-            t = ops.linear(a.view(tokens, C), pk["win"], pk["bin"], rowstats=rs, rowstats_eps=rs_eps)
-        D, heads = t.shape[1], self.n_heads
+
+        def pad_frames(src):      # zero rows up to N behind each frame for the length of this transformer: all its layers are row-wise
+            dst = torch.zeros((n * N, C), dtype=torch.float16, device=x.device)      # except the attentions, which take nq = N and nk = h*w
+            ops.copy2d(src, dst, n, N_img * C, N_img * C, N * C)           # one "row" per frame
+            return dst
+        t, rs, xin = _norm_proj_in(self, x, N_img, stats, plan.fold, plan.rowstats, pad_frames if N != N_img else None)
+        tokens, video_rows, D, heads = n * N, frames_per_video * N, t.shape[1], self.n_heads
         for bi, (blk, kv) in enumerate(zip(self.transformer_blocks, context_kv)):
             ln = blk.ln_params()
-            if mx:
-                t, n, tokens, xin = _sattn_mx_block(blk, kv, ln, t, xin, n, N, N_img, D, heads, frames_per_video, cfg_repeat if bi == 0 else 1)
-                if bi + 1 < len(self.transformer_blocks):
-                    t = blk.ff.run(t, ln[2])
-                continue
-            a1, a2 = blk.attn1.packed(), blk.attn2.packed()
-            # ---- self-attention over the h*w tokens of each frame
-            # scale * log2(e) rides in the projections (sqrt of it on Q and on K: one fp16 rounding each, as without it), so the
-            # attention kernel gets base-2 logits and its running max can live in the MFMA accumulator (VCX_ATTN_LOG2_LOGITS)
-            pqk, pv, qk_alpha = a1["qk"], a1["v"], math.sqrt(blk.attn1.scale * ops.LOG2E)
-            if pool is not None:        # SATTN_KV_POOL: every query, keys and values of the 2x2-pooled tokens
-                o = _sattn_kv_pool(blk, ln[0], t, n, H, W, pool, heads, rs if bi == 0 else None)
-            else:
-                # norm1 folded into both projections (they read the token stream itself) wherever the pack is folded and the kernel
-                # takes the shape; layer_norm + plain projections otherwise (ln_linear / ln_linear_t)
-                st = rs if (bi == 0 and rs is not None) else (ops.row_stats(t, ln[0][2]) if pqk["colsum"] is not None else None)
-                qk = ln_linear(t, pqk, ln[0], alpha=qk_alpha, stats=st)                 # [tokens, 2D]
-                vt = ln_linear_t(t, pv, ln[0], stats=st)                                # [D, tokens]
-                o = torch.empty((tokens, D), dtype=torch.float16, device=x.device)
-                ops.flash_attn(qk, qk[:, D:], vt, o, n_groups=n, heads=heads, nq=N, nk=N_img, kv_rows=N, kv_div=1, ldq=2 * D,
-                               ldk=2 * D, ldvt=tokens, ldo=D, scale=blk.attn1.scale, log2_logits=True)
-            st2 = ops.rowstats_buffer(tokens, x.device) if (_folded(a2["q"], tokens, D, D) and ops.rowstats_ok(tokens, D, D, ldr=D, video_rows=video_rows)) else None
-            t = ops.linear(o, a1["wo"], a1["bo"], residual=t, rowstats=st2, rowstats_eps=ln[1][2])
+            a1, a2 = [a.mx_packed() if mx else a.packed() for a in (blk.attn1, blk.attn2)]
+            # ---- self-attention over the h*w tokens of each frame; its output projection writes norm2's row statistics as proj_in writes norm1's
+            o = self_attn(blk, ln[0], t, _self_attn_geometry(n, heads, N, N_img, D, plan.pool), rs if bi == 0 else None, (H, W))
+            st2 = ops.rowstats_buffer(tokens, x.device) if (not mx and _folded(a2["q"], tokens, D, D)
+                                                            and ops.rowstats_ok(tokens, D, D, ldr=D, video_rows=video_rows)) else None
+            t = _to_out(o, a1, t, mx, rowstats=st2, rowstats_eps=ln[1][2])
             # ---- cross-attention: softmax(Q K_txt) V_txt + softmax(Q K_img) V_img
-            q2 = ln_linear(t, a2["q"], ln[1], alpha=blk.attn2.scale * ops.LOG2E, stats=st2)
+            if mx:
+                q2 = ops.linear_mxfp8(ops.layer_norm_mxfp8(t, *ln[1]), a2["wq"], a2["zero"], K=D)
+            else:
+                q2 = ln_linear(t, a2["q"], ln[1], alpha=blk.attn2.scale * ops.LOG2E, stats=st2)
             if bi == 0 and cfg_repeat > 1:      # from here on the r conditionings differ
                 t, q2, xin = ops.repeat_rows(t, cfg_repeat), ops.repeat_rows(q2, cfg_repeat), ops.repeat_rows(xin, cfg_repeat)
                 n, tokens = n * cfg_repeat, tokens * cfg_repeat
-            o2 = torch.empty((tokens, D), dtype=torch.float16, device=x.device)
-            nb = kv.n_txt_rows // 80
-            if kv.k_img is not None:     # text (+) image in one pass over q2 / o2
-                ops.flash_attn_dual(q2, kv.k_txt, kv.vt_txt, kv.k_img, kv.vt_img, o2, n_groups=n, heads=heads, nq=N,
-                                    nk1=kv.n_txt, kv_rows1=80, kv_div1=frames_per_video, ldk1=D, ldvt1=nb * 80,
-                                    nk2=kv.n_img, kv_rows2=kv.n_img, kv_div2=1 if kv.img_per_frame else frames_per_video,
-                                    ldk2=D, ldvt2=kv.vt_img.shape[1], ldq=D, ldo=D, scale=blk.attn2.scale, log2_logits=True)
-            else:
-                ops.flash_attn(q2, kv.k_txt, kv.vt_txt, o2, n_groups=n, heads=heads, nq=N, nk=kv.n_txt,
-                               kv_rows=80, kv_div=frames_per_video, ldq=D, ldk=D, ldvt=nb * 80, ldo=D, scale=blk.attn2.scale,
-                               log2_logits=True)
-            t = ops.linear(o2, a2["wo"], a2["bo"], residual=t)
+            ctx = (kv.k_txt, kv.vt_txt) if kv.k_img is None else (kv.k_txt, kv.vt_txt, kv.k_img, kv.vt_img)
+            o2 = _attend(q2, ctx, _cross_attn_geometry(kv, n, heads, N, D, frames_per_video), blk.attn2.scale, mx)
+            t = _to_out(o2, a2, t, mx)
             # ---- feed-forward (the last block's: with proj_out, below)
             if bi + 1 < len(self.transformer_blocks):
                 t = blk.ff.run(t, ln[2])
@@ -711,52 +769,7 @@ class SpatialTransformer(PackedModule):
         return out.view(n, H, W, C), cs_out
 
 
-def _sattn_kv_pool(blk, lnp, t, n, H, W, pool, heads, rs):
-    """The self-attention of one SpatialTransformer block on the SATTN_KV_POOL route, up to its output projection: five calls (six where
-    the folded Q projection has no row statistics from its producer, `rs`), in this order.  lnp = (gamma, beta, eps) of norm1; t
-    [n H W, D] (kv_pool_plan: no padded rows).  -> the attention output [n H W, D]."""
-    pp = blk.attn1.kv_pool_packed()
-    tokens, D = t.shape
-    N, Np = H * W, pool[0] * pool[1]
-    alpha = math.sqrt(blk.attn1.scale * ops.LOG2E)
-    q = ln_linear(t, pp["q"], lnp, alpha=alpha, stats=rs)                                        # [tokens, D], every query
-    p = ops.layer_norm_pool2x2(t, *lnp, n, H, W, _KV_POOL_MODES[SATTN_KV_POOL])                   # [n Np, D], normalised and pooled
-    k = ops.linear(p, pp["wk"], None, alpha=alpha)                                               # [n Np, D]
-    vt = ops.gemm(pp["wv"], p, M=D, N=n * Np, K=D, lda=D)                                        # [D, n Np]
-    o = torch.empty((tokens, D), dtype=torch.float16, device=t.device)
-    return ops.flash_attn(q, k, vt, o, n_groups=n, heads=heads, nq=N, nk=Np, kv_rows=Np, kv_div=1, ldq=D, ldk=D, ldvt=n * Np, ldo=D,
-                          scale=blk.attn1.scale, log2_logits=True)
-
-
-def _sattn_mx_block(blk, kv, ln, t, xin, n, N, N_img, D, heads, frames_per_video, cfg_repeat):
-    """The two attentions of one SpatialTransformer block on the SATTN_MXFP8 route: ten calls, in this order.  -> (t, n, tokens, xin), the
-    last three as the CFG replication in front of the cross-attention leaves them."""
-    m1, m2 = blk.attn1.mx_packed(), blk.attn2.mx_packed()
-    tokens = n * N
-    an = ops.layer_norm_mxfp8(t, *ln[0])
-    qk = ops.linear_mxfp8(an, m1["wqk"], m1["zero"], K=D)                     # [tokens, 2D] fp16, base-2 logit scale in the weights
-    vt = ops.linear_t_mxfp8(an, m1["wv"], K=D)                                # [D, tokens] fp16
-    o = ops.flash_attn_mxfp8(qk, qk[:, D:], vt, n_groups=n, heads=heads, nq=N, nk=N_img, kv_rows=N, kv_div=1, ldq=2 * D, ldk=2 * D, ldvt=tokens,
-                             scale=blk.attn1.scale)                           # MXFP8 pair [tokens, Kp(D)]
-    t = ops.linear_mxfp8(o, m1["wo"], m1["bo"], K=D, residual=t)
-    an2 = ops.layer_norm_mxfp8(t, *ln[1])
-    q2 = ops.linear_mxfp8(an2, m2["wq"], m2["zero"], K=D)
-    if cfg_repeat > 1:      # from here on the r conditionings differ
-        t, q2, xin = ops.repeat_rows(t, cfg_repeat), ops.repeat_rows(q2, cfg_repeat), ops.repeat_rows(xin, cfg_repeat)
-        n, tokens = n * cfg_repeat, tokens * cfg_repeat
-    nb = kv.n_txt_rows // 80
-    if kv.k_img is not None:
-        o2 = ops.flash_attn_dual_mxfp8(q2, kv.k_txt, kv.vt_txt, kv.k_img, kv.vt_img, n_groups=n, heads=heads, nq=N, nk1=kv.n_txt, kv_rows1=80,
-                                       kv_div1=frames_per_video, ldk1=D, ldvt1=nb * 80, nk2=kv.n_img, kv_rows2=kv.n_img,
-                                       kv_div2=1 if kv.img_per_frame else frames_per_video, ldk2=D, ldvt2=kv.vt_img.shape[1], ldq=D, scale=blk.attn2.scale)
-    else:
-        o2 = ops.flash_attn_mxfp8(q2, kv.k_txt, kv.vt_txt, n_groups=n, heads=heads, nq=N, nk=kv.n_txt, kv_rows=80, kv_div=frames_per_video, ldq=D, ldk=D,
-                                  ldvt=nb * 80, scale=blk.attn2.scale)
-    t = ops.linear_mxfp8(o2, m2["wo"], m2["bo"], K=D, residual=t)
-    return t, n, tokens, xin
-
-
-class TemporalTransformer(PackedModule):
+class TemporalTransformer(_Transformer):
     """Reference attention.py:313-412 with only_self_att=True: GN over (C/32, T, H, W) -> proj_in -> [LN, self-attn
     over T, LN, self-attn over T again (context None, :389-390), LN, GEGLU-FF] -> proj_out -> + x."""
 
@@ -797,95 +810,81 @@ class TemporalTransformer(PackedModule):
             blk.set_kind("temporal")
         self.use_linear = use_linear
 
-    def _foreign_params(self):
-        return _last_ff_params(self)
-
-    def _pack(self):
-        """+ wcat / bcat, built on first use by ff_proj_out: [Wout W2 | Wout] and Wout b2 + bout, DERIVED FROM transformer_blocks[-1].ff.net[2]
-        (a child's parameters: _foreign_params rebuilds the pack when they change, _drop_packed discards it with the rest)."""
-        win = self.proj_in.weight.detach().reshape(self.proj_in.weight.shape[0], -1)
-        wout = self.proj_out.weight.detach().reshape(self.proj_out.weight.shape[0], -1)
-        return dict(gn_w=_f32(self.norm.weight), gn_b=_f32(self.norm.bias), win=_f16(win), win32=_f32(win), bin=_f32(self.proj_in.bias),
-                    wout=_f16(wout), bout=_f32(self.proj_out.bias))
-
-    def _mx_route(self, x, D):
-        """TATTN_MXFP8: do all self-attentions of this call run on the MX route?  Decided once per call, before anything runs: width not
-        skipped, T <= 32, no relative position, dense rows, and the library's three predicates - asked about ONE video (a row's route must
-        not depend on the batch it runs in) and about the call itself (only the 32-bit extents depend on B).  Any refusal keeps the fp16
-        calls for the whole transformer."""
+    def _mx_accepts(self, x, D):
+        """TATTN_MXFP8: width not skipped, T <= 32, no relative position, dense rows, and the library's three predicates - asked about ONE
+        video (a row's route must not depend on the batch it runs in) and about the call itself (only the 32-bit extents depend on B)."""
         B, T, P, _ = x.shape
-        if not TATTN_MXFP8 or D in TATTN_MXFP8_SKIP_DIMS or T > 32 or not x.is_contiguous():
+        if not TATTN_MXFP8 or D in TATTN_MXFP8_SKIP_DIMS or T > 32 or not x.is_contiguous() or any(
+                a.relative_position or a.to_out[0].bias is None or a.inner_dim != D or a.query_dim != D
+                for blk in self.transformer_blocks for a in (blk.attn1, blk.attn2)):
             return False
-        attns = [a for blk in self.transformer_blocks for a in (blk.attn1, blk.attn2)]
-        if any(a.relative_position or a.to_out[0].bias is None or a.inner_dim != D or a.query_dim != D for a in attns):
-            return False
+        attn_ok = lambda g: ops.temporal_attn_mxfp8_ok(g["B"], g["T"], g["P"], g["heads"], g["ld"], causal=g["causal"])      # (no use for the offsets)
         return all(ops.linear_mxfp8_ok(b * T * P, 3 * D, D) and ops.linear_mxfp8_ok(b * T * P, D, D, residual=True)
-                   and ops.temporal_attn_mxfp8_ok(b, T, P, self.n_heads, 3 * D, causal=self.causal_attention) for b in sorted({1, B}))
+                   and attn_ok(self._attn_geometry(b, T, P, D)) for b in sorted({1, B}))
+
+    def _attn_geometry(self, B, T, P, D):
+        """The keywords every temporal attention kernel takes: q|k|v one [tokens, 3D] projection."""
+        return dict(B=B, T=T, P=P, heads=self.n_heads, ld=3 * D, k_off=D, v_off=2 * D, causal=self.causal_attention)
+
+    def _plan(self, x):
+        """Every routing decision of a forward, made before the first launch or activation buffer -> TemporalPlan.  fold: temporal_fold_ok.
+        engine of all self-attentions: "mx" (TATTN_MXFP8) or "fp16"; any refusal keeps the fp16 calls for the whole transformer.  rowstats:
+        proj_in writes the row statistics norm1 of the first block reads (as SpatialTransformer._plan; none on the MX route)."""
+        B, T, P, C = x.shape
+        D, rows, tokens = self.packed()["win"].shape[0], T * P, B * T * P
+        engine = "mx" if self._mx_accepts(x, D) else "fp16"
+        fold = bool(temporal_fold_ok(rows, C, D))
+        rowstats = engine != "mx" and _folded(self.transformer_blocks[0].attn1.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(
+            tokens, D, C, lda=C, unit_rows=rows if fold else None, video_rows=rows)
+        return TemporalPlan(fold, engine, rowstats)
 
     def forward(self, x, context=None, colstats=None, want_colstats=False, target=None):
         """x [B, T, P, C] fp16 channels-last (P = h*w).  colstats: column moments of x (the per-video norm then needs no statistics
         pass); want_colstats / target: proj_out writes the moments of the result / the result itself into a concat buffer
         (lvdm/modules/flow.py).  -> (result [B, T, P, C or ld], its moments or None)"""
         B, T, P, C = x.shape
-        pk = self.packed()
-        tokens = B * T * P
-        xin = x.reshape(tokens, C)
-        D, heads = pk["win"].shape[0], self.n_heads
-        mx = self._mx_route(x, D)
-        stats = None if (colstats is None or GN_STATS_LEVEL < 2) else ops.group_norm_stats_from_colstats(colstats, B, T * P, C)
-        rows = T * P
-        if GN_FOLD and C % 64 == 0 and 2 * rows * C >= GN_FOLD_MIN_BYTES and 2 * rows * max(C, D) < 0xFFFF0000 and ops.tune_get("GEMM_DMA") != 0:
-            # the norm as per-video weights / bias of proj_in; the projection reads the un-normalised rows of each video
-            if stats is None:
-                stats = ops.group_norm_stats(x.view(B, rows, C))
-            wn, bn = ops.group_norm_fold_linear(pk["win32"], pk["bin"], pk["gn_w"], pk["gn_b"], stats, self.norm.eps)
-            fold = True
-        else:
-            a = ops.group_norm(x.view(B, rows, C), pk["gn_w"], pk["gn_b"], self.norm.eps, False, stats=stats)
-            fold = False
-        # LayerNorm statistics from the producing layer (VCX_GEMM_ROWSTATS): proj_in for norm1, attn1's output projection for norm2
-        blk0 = self.transformer_blocks[0]
-        st = None
-        # (none on the MX route: the quantising LayerNorm computes its own)
-        if not mx and _folded(blk0.attn1.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, C, lda=C, unit_rows=rows if fold else None, video_rows=rows):
-            st = ops.rowstats_buffer(tokens, x.device)
-        if fold:
-            t = ops.gemm_units(xin, wn, bn, unit_rows=rows, rowstats=st, rowstats_eps=blk0.norm1.eps)
-        else:
-            t = ops.linear(a.view(tokens, C), pk["win"], pk["bin"], rowstats=st, rowstats_eps=blk0.norm1.eps)
+        rows, tokens = T * P, B * T * P
+        plan = self._plan(x)
+        mx, self_attn = plan.engine == "mx", _tattn_mx if plan.engine == "mx" else _tattn_fp16
+        stats = None if (colstats is None or GN_STATS_LEVEL < 2) else ops.group_norm_stats_from_colstats(colstats, B, rows, C)
+        t, st, xin = _norm_proj_in(self, x, rows, stats, plan.fold, plan.rowstats)
+        D = t.shape[1]
+        geo = self._attn_geometry(B, T, P, D)
         for blk in self.transformer_blocks:
             ln = blk.ln_params()
             for ai, (attn, lnp) in enumerate(((blk.attn1, ln[0]), (blk.attn2, ln[1]))):
-                if mx:
-                    am = attn.mx_packed()
-                    an = ops.layer_norm_mxfp8(t, *lnp)
-                    qkv = ops.linear_mxfp8(an, am["wqkv"], am["zero"], K=D)           # [tokens, 3D] fp16
-                    o = ops.temporal_attn_mxfp8(qkv, B=B, T=T, P=P, heads=heads, ld=3 * D, k_off=D, v_off=2 * D, scale=attn.scale,
-                                                causal=self.causal_attention)        # MXFP8 pair [tokens, Kp(D)]
-                    t = ops.linear_mxfp8(o, am["wo"], am["bo"], K=D, residual=t)
-                    continue
-                ap = attn.packed()
-                qkv = ln_linear(t, ap["qkv"], lnp, stats=st)                         # [tokens, 3D]
-                o = torch.empty((tokens, D), dtype=torch.float16, device=x.device)
-                if attn.relative_position:
-                    # logits += q Ek^T (per head: a [tokens, 64] x [64, 64] GEMM on the q columns of qkv), out += (probabilities by clipped distance) Ev
-                    relg = torch.empty((tokens, heads, 64), dtype=torch.float16, device=x.device)
-                    relp = torch.zeros((tokens, heads, 64), dtype=torch.float16, device=x.device)
-                    for h_ in range(heads):
-                        ops.gemm(qkv[:, h_ * 64:], ap["rel_k"], M=tokens, N=64, K=64, lda=3 * D, out=relg[:, h_], ldc=heads * 64)
-                    ops.temporal_attn_rel(qkv, o, relg, relp, R=ap["rel_R"], B=B, T=T, P=P, heads=heads, ld=3 * D, k_off=D, v_off=2 * D, ldo=D,
-                                          scale=attn.scale, causal=self.causal_attention)
-                    for h_ in range(heads):
-                        ops.gemm(relp[:, h_], ap["rel_v"], M=tokens, N=64, K=64, lda=heads * 64, out=o[:, h_ * 64:], ldc=D, residual=o[:, h_ * 64:], ldr=D)
-                else:
-                    ops.temporal_attn(qkv, o, B=B, T=T, P=P, heads=heads, ld=3 * D, k_off=D, v_off=2 * D, ldo=D,
-                                      scale=attn.scale, causal=self.causal_attention)
-                st = None
-                if ai == 0 and _folded(blk.attn2.packed()["qkv"], tokens, D, D) and ops.rowstats_ok(tokens, D, D, ldr=D, video_rows=rows):
-                    st = ops.rowstats_buffer(tokens, x.device)
-                t = ops.linear(o, ap["wo"], ap["bo"], residual=t, rowstats=st, rowstats_eps=ln[1][2])
+                o = self_attn(attn, lnp, t, geo, st)
+                st = ops.rowstats_buffer(tokens, x.device) if (not mx and ai == 0 and _folded(blk.attn2.packed()["qkv"], tokens, D, D)
+                                                               and ops.rowstats_ok(tokens, D, D, ldr=D, video_rows=rows)) else None
+                t = _to_out(o, attn.mx_packed() if mx else attn.packed(), t, mx, rowstats=st, rowstats_eps=ln[1][2])
             if blk is not self.transformer_blocks[-1]:      # (the last block's feed-forward: with proj_out, below)
                 t = blk.ff.run(t, ln[2])
         kw, cs_out = out_kwargs(target, want_colstats, tokens, P, D, C, x.device)
         out = ff_proj_out(self, t, ln[2], xin, kw, rows)
         return out.view(B, T, P, -1), cs_out
+
+
+def _tattn_fp16(attn, lnp, t, geo, stats):
+    """One self-attention over T of a TemporalTransformer block up to its output projection, fp16 engine -> [tokens, D].  lnp = (gamma,
+    beta, eps) of the norm in front, geo = _attn_geometry, stats = the row statistics of t where its producer wrote them."""
+    ap, (tokens, D), heads = attn.packed(), t.shape, geo["heads"]
+    qkv = ln_linear(t, ap["qkv"], lnp, stats=stats)                         # [tokens, 3D]
+    o = torch.empty((tokens, D), dtype=torch.float16, device=t.device)
+    if not attn.relative_position:
+        return ops.temporal_attn(qkv, o, **geo, ldo=D, scale=attn.scale)
+    # logits += q Ek^T (per head: a [tokens, 64] x [64, 64] GEMM on the q columns of qkv), out += (probabilities by clipped distance) Ev
+    relg = torch.empty((tokens, heads, 64), dtype=torch.float16, device=t.device)
+    relp = torch.zeros((tokens, heads, 64), dtype=torch.float16, device=t.device)
+    for h_ in range(heads):
+        ops.gemm(qkv[:, h_ * 64:], ap["rel_k"], M=tokens, N=64, K=64, lda=3 * D, out=relg[:, h_], ldc=heads * 64)
+    ops.temporal_attn_rel(qkv, o, relg, relp, R=ap["rel_R"], **geo, ldo=D, scale=attn.scale)
+    for h_ in range(heads):
+        ops.gemm(relp[:, h_], ap["rel_v"], M=tokens, N=64, K=64, lda=heads * 64, out=o[:, h_ * 64:], ldc=D, residual=o[:, h_ * 64:], ldr=D)
+    return o
+
+
+def _tattn_mx(attn, lnp, t, geo, stats):
+    """The same on the TATTN_MXFP8 route (the quantising LayerNorm computes its own statistics) -> the MXFP8 pair [tokens, Kp(D)]"""
+    am = attn.mx_packed()
+    qkv = ops.linear_mxfp8(ops.layer_norm_mxfp8(t, *lnp), am["wqkv"], am["zero"], K=t.shape[1])           # [tokens, 3D] fp16
+    return ops.temporal_attn_mxfp8(qkv, **geo, scale=attn.scale)

@@ -17,6 +17,11 @@ GN_STATS_LEVEL = int(os.environ.get("VCX_GN_EPILOGUE_STATS", "2"))
 GN_EPILOGUE_STATS = GN_STATS_LEVEL >= 1
 
 
+def env_dims(name, default):
+    """The channel widths a *_SKIP_DIMS environment variable names: a comma-separated list, `default` (a string) where it is not set."""
+    return frozenset(int(v) for v in os.environ.get(name, default).split(",") if v.strip())
+
+
 # Round 6: the channel concat of the up path (reference openaimodel3d.py:596) is not materialised where the consuming ResBlock can read
 # its two halves in place - the in_layers norm through vcx_groupnorm_apply2_f16, the 1x1 skip convolution as a K tail of the block's
 # second 3x3 convolution (SKIP_FOLD in openaimodel3d.py) - so the copy of the skip tensor behind the producer's columns disappears; the

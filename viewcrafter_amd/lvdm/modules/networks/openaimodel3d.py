@@ -22,7 +22,7 @@ from torch import nn
 from .... import ops
 from ....packing import pack_conv, pack_conv3x3_mxfp8, pack_conv3x3_tail_mxfp8, pack_conv_t3_mxfp8, pack_conv_ups_folded
 from ..attention import PackedModule, SpatialTransformer, TemporalTransformer, _f16, _f32
-from ..flow import CAT_SPLIT, GN_EPILOGUE_STATS, GN_STATS_LEVEL, CatTarget, Flow, out_kwargs as _out_kwargs
+from ..flow import CAT_SPLIT, GN_EPILOGUE_STATS, GN_STATS_LEVEL, CatTarget, Flow, env_dims, out_kwargs as _out_kwargs
 
 # A ResBlock's 1x1 skip convolution as a K tail of its second 3x3 convolution (round 6, include/vcx.h tail_a0 / tail_a1).  VCX_SKIP_FOLD=0: the
 # separate convolution + residual of rounds 1-5 (A/B runs; also switches the split concat off, which needs the fold).
@@ -37,7 +37,7 @@ EMB_BATCHED = os.environ.get("VCX_EMB_BATCHED", "1") != "0"
 TCONV_MXFP8 = os.environ.get("VCX_TCONV_MXFP8", "0") == "1"
 # Block widths that stay on the fp16 route although the switch is on: those whose MX block was measured no faster than its fp16 block
 # (profiles/mxfp8_tconv.md).  VCX_TCONV_MXFP8_SKIP_DIMS="" puts every width on MX.
-TCONV_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_TCONV_MXFP8_SKIP_DIMS", "320").split(",") if v.strip())
+TCONV_MXFP8_SKIP_DIMS = env_dims("VCX_TCONV_MXFP8_SKIP_DIMS", "320")
 # Opt-in (VCX_RESCONV_MXFP8=1, default off): the two 3x3 convolutions of a ResBlock on the block-scaled MXFP8 matrix pipe (include/vcx.h
 # vcx_conv3x3_mxfp8, the second gathered mode of csrc/gemm_mx.hip) - the GroupNorm + SiLU apply pass in front of an MX convolution writes
 # MXFP8 bytes + block scales (vcx_groupnorm_apply_mxfp8_f16 / apply2 over a split concat).  Independent of VCX_FF_MXFP8 and
@@ -46,7 +46,7 @@ TCONV_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_TCONV_MXFP
 RESCONV_MXFP8 = os.environ.get("VCX_RESCONV_MXFP8", "0") == "1"
 # Block widths (out_channels) that stay on the fp16 route although the switch is on: those whose MX block was measured no faster than its
 # fp16 block - none (profiles/mxfp8_resconv.md: 1.04x at the least), so the default list is empty.
-RESCONV_MXFP8_SKIP_DIMS = frozenset(int(v) for v in os.environ.get("VCX_RESCONV_MXFP8_SKIP_DIMS", "").split(",") if v.strip())
+RESCONV_MXFP8_SKIP_DIMS = env_dims("VCX_RESCONV_MXFP8_SKIP_DIMS", "")
 # A block with a 1x1 skip convolution: 1 = its second convolution stays on the fp16 engine with the skip folded in as a K tail and only the
 # first one is MX; 0 (default: the faster one in the isolated A/B, 1.22x / 1.29x against 1.06x / 1.11x, profiles/mxfp8_resconv.md) = the
 # second one is MX too and takes the separate fp16 skip convolution's result as its residual.
